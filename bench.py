@@ -7,8 +7,15 @@ Adagrad(DNN) + FTRL(linear) — full training step (fwd + bwd + all-reduce + opt
 timed region. Data: synthetic transformed-taxi records resident in HBM (no network for the
 real CSV); random-init weights. Weak scaling: fixed batch per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch-per-gpu B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch-per-gpu B] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...
+
+A plain run does only what the headline figure needs: set up, warm up, time the K steps, validate the replicas
+(multi-rank), write the outputs if asked, print the result line. `--full` adds what takes runs of its own: the
+gradient check against fp32 autograd and the reference-batch (B=40) timing; without it the result line carries
+null for both. `--dump-outputs DIR` writes what the timed path left after its last step (master weights, both
+optimizer slots, the last step's mean loss) as DIR/<name>.npy; the inputs are seeded, so two builds run with the
+same arguments can be compared output for output.
 
 `python bench.py --gpus N` (N > 1, no torchrun env) starts its own N ranks -- one process per GPU with
 torchrun-style env, spawned before this process touches the GPU -- relays rank 0's JSON line and exits with the
@@ -125,6 +132,18 @@ def gradient_check(batch: int, device, seed: int) -> float:
         worst = max(worst, float(np.linalg.norm(gk - r) / (np.linalg.norm(r) + 1e-8)))
     del tr
     return worst
+
+
+def dump_outputs(tr, batch: int, out_dir: str) -> None:
+    """What a caller of the timed path holds after its last step, as float32/float64 .npy files: the fp32 master
+    weights and both optimizer slots in canonical order (a few hundred KB in all) and the last step's mean loss."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    sd = tr.state_dict()
+    for name in ("param", "s0", "s1"):
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(sd[name].detach().cpu().numpy(), dtype=np.float32))
+    np.save(os.path.join(out_dir, "loss.npy"), np.asarray([tr.last_loss() / batch], dtype=np.float64))
 
 
 def make_trainer(batch: int, device, pg, seed: int, n_data: int, graph: bool, dp: str = "xgmi",
@@ -270,12 +289,18 @@ def main(argv=None) -> int:
     argv = list(sys.argv[1:] if argv is None else argv)
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
-    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 200; 20 on the CPU fallback)")
+    ap.add_argument("--warmup", type=int, default=None, help="untimed steps first (default 20; 2 on the CPU fallback)")
     ap.add_argument("--batch-per-gpu", type=int, default=65536,
                     help="throughput batch per replica (BASELINE.md protocol: 8K-64K); 40 = reference batch")
-    ap.add_argument("--ref-batch", type=int, default=40, help="also time the reference batch (0 = skip)")
-    ap.add_argument("--ref-steps", type=int, default=2000)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the gradient check against fp32 autograd "
+                         "and the reference-batch timing (--ref-batch / --ref-steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the trained state of the timed run (param, s0, s1, loss) as "
+                         "DIR/<name>.npy")
+    ap.add_argument("--ref-batch", type=int, default=40, help="with --full: also time the reference batch (0 = skip)")
+    ap.add_argument("--ref-steps", type=int, default=None, help="default 2000; 50 on the CPU fallback")
     ap.add_argument("--ref-steps-per-graph", type=int, default=100,
                     help="steps per hipGraph for the reference-batch run (its 2000 steps amortise graph boundaries; "
                          "profiles/archive/bench_ref_spg_sweep_r3.txt)")
@@ -315,17 +340,22 @@ def main(argv=None) -> int:
     else:  # CPU dev fallback: keep it quick
         a.batch_per_gpu = min(a.batch_per_gpu, 4096)
         a.data_per_gpu = min(a.data_per_gpu, 1 << 16)
-        a.steps, a.warmup, a.ref_steps = min(a.steps, 20), min(a.warmup, 2), min(a.ref_steps, 50)
+    # step counts given on the command line are taken as they are; only the defaults shrink on the CPU fallback
+    dflt = (200, 20, 2000) if use_cuda else (20, 2, 50)
+    a.steps, a.warmup, a.ref_steps = (d if v is None else v for v, d in zip((a.steps, a.warmup, a.ref_steps), dflt))
+    if a.steps < 1:
+        raise SystemExit("[bench] --steps must be at least 1")
     pg = torch.distributed.group.WORLD if env.world_size > 1 else None
     n = env.world_size
     seen = torch.distributed.get_world_size() if pg is not None else 1
     if seen != a.gpus:
         raise SystemExit(f"[bench] process group has {seen} ranks, --gpus {a.gpus}")
 
-    def measure(batch, seed, n_data, steps, warmup, spg_req=None):
+    def measure(batch, seed, n_data, steps, warmup, spg_req=None, dump_dir=None):
         """Build, time `steps` steps, validate after the timed region. A multi-rank xGMI run that fails the
         post-run validation (a timed-out wait, replicas that differ) is discarded and re-measured on the direct
-        RCCL path; a failing direct run fails the benchmark (no number from a broken step)."""
+        RCCL path; a failing direct run fails the benchmark (no number from a broken step). `dump_dir`: rank 0
+        writes the state the validated run left (dump_outputs)."""
         dp = a.dp
         while True:
             tr = make_trainer(batch, device, pg, seed, n_data, not a.no_graph, dp, spg_req or a.steps_per_graph,
@@ -339,6 +369,8 @@ def main(argv=None) -> int:
                 paths = [None] * n
                 torch.distributed.all_gather_object(paths, res["dp_path"])
                 res["dp_per_rank"] = paths
+            if ok and dump_dir and env.is_main:
+                dump_outputs(tr, batch, dump_dir)
             if getattr(tr, "_xg", None) is not None:
                 tr.disable_xgmi()
             del tr
@@ -353,18 +385,18 @@ def main(argv=None) -> int:
                   flush=True)
             dp = "direct"
 
-    r = measure(a.batch_per_gpu, 1234 + env.rank, a.data_per_gpu, a.steps, a.warmup)
+    r = measure(a.batch_per_gpu, 1234 + env.rank, a.data_per_gpu, a.steps, a.warmup, dump_dir=a.dump_outputs)
     dt, dp_path, spg, ranks_agree, loss = r["dt"], r["dp_path"], r["spg"], r["agree"], r["loss"]
     dp_per_rank = r.get("dp_per_rank")
     value = a.batch_per_gpu * n * a.steps / dt
     grad_err = None
-    if use_cuda and env.is_main:  # after the timed region: the kernel's gradient vs fp32 autograd on one batch
+    if a.full and use_cuda and env.is_main:  # after the timed region: the kernel's gradient vs fp32 autograd
         grad_err = gradient_check(a.batch_per_gpu, device, 4321)
         if not grad_err < 0.1:
             raise SystemExit(f"[bench] gradient check failed: relative error {grad_err:.3g} vs fp32 autograd")
 
     ref = None
-    if a.ref_batch:
+    if a.full and a.ref_batch:
         r2 = measure(a.ref_batch, 99 + env.rank, 1 << 16, a.ref_steps, max(10, a.warmup),
                      min(a.ref_steps_per_graph, max(1, a.ref_steps)))
         ref = {"batch_per_gpu": a.ref_batch, "examples_per_sec": a.ref_batch * n * a.ref_steps / r2["dt"],

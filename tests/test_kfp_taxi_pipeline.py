@@ -1,7 +1,9 @@
 """KFP taxi pipeline (8 container steps) compiled and executed on this host by the local executor."""
 import csv
+import gzip
 import json
 import os
+import shutil
 
 import pytest
 import yaml
@@ -9,7 +11,7 @@ import yaml
 from mifx.data.synthetic import TAXI_COLUMNS, synthetic_taxi_csv_rows
 
 ROOT = os.path.dirname(os.path.dirname(__file__))
-REF_TAXI = "/root/reference/kubeflow-pipelines/taxi"
+GOLDEN_TAXI = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "taxi")
 
 
 def _write_csv(path, rows):
@@ -80,6 +82,7 @@ def test_taxi_pipeline_dnntrainer_data_parallel_two_ranks(tmp_path, monkeypatch)
     """--num-gpus 2: the dnntrainer step launches two ranks of itself (gloo on this CPU host; on GPUs: one
     per device, sparse backward-state all-gather) and the rest of the pipeline consumes rank 0's export."""
     monkeypatch.setenv("CUDA_VISIBLE_DEVICES", "")
+    monkeypatch.setenv("HIP_VISIBLE_DEVICES", "-1")  # the HIP runtime takes an empty list for "not set"
     data = tmp_path / "data"
     data.mkdir()
     _write_csv(data / "train.csv", synthetic_taxi_csv_rows(1200, seed=1))
@@ -95,10 +98,16 @@ def test_taxi_pipeline_dnntrainer_data_parallel_two_ranks(tmp_path, monkeypatch)
     assert 0.5 < float(_outputs(st, "roc")[0]["value"]) <= 1.0
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(REF_TAXI, "train.csv")), reason="reference data not present")
 def test_taxi_pipeline_on_reference_csv(tmp_path):
-    """The reference's own train/eval CSVs (10k/5k Chicago-taxi rows; read as text only)."""
-    st = _run(tmp_path, REF_TAXI, 300, "128")
+    """The reference's own train/eval CSVs (10k/5k Chicago-taxi rows; read as text only), stored gzip-compressed
+    under tests/golden/taxi."""
+    data = tmp_path / "data"
+    data.mkdir()
+    for name in ("train.csv", "eval.csv"):
+        with gzip.open(os.path.join(GOLDEN_TAXI, name + ".gz"), "rb") as src, open(data / name, "wb") as dst:
+            shutil.copyfileobj(src, dst)
+    shutil.copy(os.path.join(GOLDEN_TAXI, "column-names.json"), data / "column-names.json")
+    st = _run(tmp_path, str(data), 300, "128")
     assert st["phase"] == "Succeeded", st["message"]
     assert float(_outputs(st, "roc")[0]["value"]) > 0.8
 
