@@ -9,7 +9,11 @@
   exports the TP=1 state as a ModelExportPath artifact. `custom_config={"tp": N}` runs Megatron-style tensor
   parallelism over N ranks (one per GPU, RCCL over xGMI; gloo processes on a CPU host; `"sequence_parallel": true`:
   token-sharded LayerNorms / dropouts between the TP regions) launched by the component itself
-  (mifx.trainer.distributed); rank 0 gathers the full state and exports.
+  (mifx.trainer.distributed); rank 0 gathers the full state and exports. Optimizer recipe keys of
+  `custom_config` (defaults keep a constant learning rate, no clipping, decay on every parameter):
+  `max_grad_norm` (global-norm clipping, TP = 1 only), `lr_schedule` ("constant" | "linear": warmup then decay
+  to zero at train_args.num_steps), `warmup_proportion` (fraction of num_steps), `no_decay_bias_norm`. The
+  resolved settings are recorded in the result (`metrics.json`, key "optimizer").
 
 Contract mirrored from the TFX Trainer of the reference (`airflow-dags/taxi_pipeline.py:92-99`: examples in,
 ModelExportPath out, lineage in MLMD; train_args / eval_args num_steps)."""
@@ -126,6 +130,24 @@ _CFG_KEYS = ("vocab_size", "hidden", "layers", "heads", "intermediate", "max_pos
              "sequence_parallel")
 
 
+def resolve_optimizer_config(cc: dict, train_steps: int) -> dict:
+    """custom_config -> the BertTrainer optimizer arguments (what the result records under "optimizer")."""
+    kind = cc.get("lr_schedule", "constant")
+    if kind not in ("constant", "linear"):
+        raise ValueError(f'lr_schedule must be "constant" or "linear", got {kind!r}')
+    wp = float(cc.get("warmup_proportion", 0.0))
+    if not 0.0 <= wp < 1.0:
+        raise ValueError(f"warmup_proportion must be in [0, 1), got {wp}")
+    if kind == "constant" and wp:
+        raise ValueError('warmup_proportion needs lr_schedule="linear"')
+    mgn = cc.get("max_grad_norm")
+    return {"learning_rate": float(cc.get("learning_rate", 2e-5)), "lr_schedule": kind, "warmup_proportion": wp,
+            "warmup_steps": int(wp * train_steps) if kind == "linear" else 0,
+            "total_steps": int(train_steps) if kind == "linear" else None,
+            "max_grad_norm": None if mgn is None else float(mgn),
+            "no_decay_bias_norm": bool(cc.get("no_decay_bias_norm", False))}
+
+
 def run_bert_rank(spec: dict) -> dict:
     """One rank (or the only process) of a BertTrainer run: train, evaluate, rank 0 exports the TP=1 state."""
     import torch
@@ -152,12 +174,14 @@ def run_bert_rank(spec: dict) -> dict:
     B = int(cc.get("batch_size", 32))
     S = tr_data["input_ids"].shape[1]
     torch.manual_seed(int(cc.get("seed", 0)))
-    tr = BertTrainer(cfg, B, S, dev, tp, lr=float(cc.get("learning_rate", 2e-5)),
-                     graph=cc.get("graph"))
+    steps = int(spec["train_steps"])
+    opt_cfg = resolve_optimizer_config(cc, steps)
+    tr = BertTrainer(cfg, B, S, dev, tp, lr=opt_cfg["learning_rate"], graph=cc.get("graph"),
+                     max_grad_norm=opt_cfg["max_grad_norm"], warmup_steps=opt_cfg["warmup_steps"],
+                     total_steps=opt_cfg["total_steps"], no_decay_bias_norm=opt_cfg["no_decay_bias_norm"])
     T = {k: torch.from_numpy(v.astype(np.int64) if k != "attention_mask" else v.astype(np.float32))
          for k, v in tr_data.items()}
     n = len(T["labels"])
-    steps = int(spec["train_steps"])
     losses = []
     t0 = time.time()
     for i in range(steps):
@@ -179,7 +203,9 @@ def run_bert_rank(spec: dict) -> dict:
         correct += int((logits.argmax(-1).cpu() == E["labels"][sl]).sum())
     full = gather_full_state(tr.model)  # collective
     res = {"eval": {"accuracy": correct / max(1, ne), "num_eval_examples": ne}, "losses": losses,
-           "train_sequences_per_sec": steps * B / max(secs, 1e-9), "tp": tp.size, "steps": steps}
+           "train_sequences_per_sec": steps * B / max(secs, 1e-9), "tp": tp.size, "steps": steps,
+           "optimizer": dict(opt_cfg, final_lr=tr.last_lr() if steps else None,
+                             final_grad_norm=tr.last_grad_norm() if steps else None)}
     if tp.rank == 0:
         exp = os.path.join(spec["out_dir"], "serving_model_dir", "export", "bert", str(int(time.time() * 1000)))
         os.makedirs(exp, exist_ok=True)

@@ -60,18 +60,45 @@ class BertTrainer:
     GPU work). The model weights are bf16 views of one flat buffer updated by a single fused HIP AdamW
     launch with fp32 master weights that reads autograd's own gradient tensors in place
     (mifx.trainer.optim.FlatAdamW): no per-step weight/grad cast kernels, no gradient zero-fill, no
-    per-parameter accumulate kernels."""
+    per-parameter accumulate kernels.
+
+    The standard BERT fine-tuning recipe is optional (all off by default): `max_grad_norm` clips by the global
+    gradient norm, `warmup_steps` / `total_steps` give linear warmup then linear decay to zero at total_steps
+    (total_steps None: constant learning rate), `no_decay_bias_norm` takes biases and LayerNorm parameters
+    (`p.ndim <= 1`; the embeddings stay decayed) out of the weight decay. With FlatAdamW the norm, the clip
+    coefficient and the learning rate are computed on the device inside the captured step; the stock-PyTorch
+    optimizer path does the same on the host (two param groups, clip_grad_norm_, `group["lr"]` set before
+    each eager step), so there a schedule cannot be combined with graph=True. `last_lr()` / `last_grad_norm()`
+    report the last step's values. Clipping needs TP = 1 (the global norm over sharded plus replicated
+    parameters needs a cross-rank reduction); the schedule and the no-decay set work at any TP degree."""
 
     def __init__(self, cfg: BertConfig, batch: int, seq: int, device, tp: TPGroup | None = None, lr: float = 2e-5,
                  graph: bool | None = None, flat_adamw: bool | None = None, sdpa: str | None = None,
-                 tp_ipc: bool | None = None):
+                 tp_ipc: bool | None = None, max_grad_norm: float | None = None, warmup_steps: int = 0,
+                 total_steps: int | None = None, no_decay_bias_norm: bool = False):
         """tp_ipc (TP > 1 on the GPU; default on, MIFX_TP_IPC=0 turns it off): the TP all-reduces run on the
         peer-memory kernels of mifx.parallel.tp_ipc, so the TP step is captured into a hipGraph like the TP=1
         step (otherwise they are torch.distributed collectives and TP > 1 steps eagerly)."""
         self.cfg, self.batch, self.seq, self.device = cfg, batch, seq, torch.device(device)
         self.tp = tp or TPGroup(None)
-        self.model = BertForSequenceClassification(cfg, self.tp, seed=0).to(self.device)
         cuda = self.device.type == "cuda"
+        self.flat = cuda if flat_adamw is None else (flat_adamw and cuda)
+        if max_grad_norm is not None and self.tp.size > 1:
+            raise ValueError("max_grad_norm needs TP = 1: the global gradient norm over sharded and replicated "
+                             "parameters needs a cross-rank reduction, which is not implemented")
+        if total_steps is None:
+            if warmup_steps:
+                raise ValueError("warmup_steps needs total_steps (the step at which the learning rate reaches zero)")
+            self.schedule = None
+        else:
+            if warmup_steps < 0 or total_steps <= warmup_steps:
+                raise ValueError(f"need 0 <= warmup_steps < total_steps, got {warmup_steps}, {total_steps}")
+            self.schedule = ("linear", int(warmup_steps), int(total_steps))
+        if not self.flat and self.schedule is not None and graph:
+            raise ValueError("a learning-rate schedule on the stock-PyTorch optimizer path is set from the host before "
+                             "each eager step: it cannot be combined with graph=True (use the flat AdamW)")
+        self.lr, self.max_grad_norm, self.no_decay_bias_norm = lr, max_grad_norm, bool(no_decay_bias_norm)
+        self.model = BertForSequenceClassification(cfg, self.tp, seed=0).to(self.device)
         if tp_ipc is None:
             tp_ipc = os.environ.get("MIFX_TP_IPC", "1") != "0"
         if cuda and self.tp.size > 1 and tp_ipc:
@@ -85,12 +112,20 @@ class BertTrainer:
         # torch.distributed collectives it steps eagerly unless graph=True is passed.
         self.use_graph = (cuda and (self.tp.size == 1 or self.tp.ipc is not None)) if graph is None \
             else (graph and cuda)
-        self.flat = cuda if flat_adamw is None else (flat_adamw and cuda)
+        if not self.flat and self.schedule is not None:
+            self.use_graph = False  # the host sets group["lr"] before each step
+        no_decay = (lambda p: p.ndim <= 1) if self.no_decay_bias_norm else None
+        self._host_steps = 0  # stock-PyTorch path: optimizer steps taken (places the schedule)
+        self._host_norm = None
         if self.flat:  # bf16 weights/grads as flat-buffer views + fp32 master, one fused HIP update
-            self.opt = FlatAdamW(self.model.parameters(), lr=lr, weight_decay=0.01)
+            self.opt = FlatAdamW(self.model.parameters(), lr=lr, weight_decay=0.01, max_grad_norm=max_grad_norm,
+                                 schedule=self.schedule, no_decay=no_decay)
         else:
-            self.opt = torch.optim.AdamW(self.model.parameters(), lr=lr, weight_decay=0.01, fused=cuda,
-                                         capturable=self.use_graph)
+            params = list(self.model.parameters())
+            if no_decay is not None:
+                params = [{"params": [p for p in params if not no_decay(p)], "weight_decay": 0.01},
+                          {"params": [p for p in params if no_decay(p)], "weight_decay": 0.0}]
+            self.opt = torch.optim.AdamW(params, lr=lr, weight_decay=0.01, fused=cuda, capturable=self.use_graph)
         if self.model.sequence_parallel:
             if getattr(self.opt, "overlap", False):
                 raise ValueError("sequence parallelism: the overlapped AdamW buckets would update the token-shard "
@@ -168,8 +203,31 @@ class BertTrainer:
                 loss.backward()
         # sequence parallelism: the LayerNorm / row-parallel-bias gradients are per-shard partial sums
         self.model.sync_sequence_parallel_grads()
+        if not self.flat:  # the recipe on the stock optimizer (FlatAdamW does it on the device, inside its step)
+            if self.max_grad_norm is not None:
+                self._host_norm = torch.nn.utils.clip_grad_norm_(self.model.parameters(), self.max_grad_norm)
+            if self.schedule is not None:
+                from ..ops.adamw import scheduled_lr
+
+                for group in self.opt.param_groups:
+                    group["lr"] = scheduled_lr(self.lr, self.schedule, self._host_steps)
+            self._host_steps += 1
         self.opt.step()
         return loss.detach()
+
+    def last_lr(self) -> float:
+        """Learning rate of the last optimizer step (host sync on the flat path: for logging)."""
+        if self.flat:
+            return self.opt.last_lr()
+        from ..ops.adamw import scheduled_lr
+
+        return scheduled_lr(self.lr, self.schedule, max(0, self._host_steps - 1))
+
+    def last_grad_norm(self) -> float | None:
+        """Global gradient norm before clipping at the last step; None without max_grad_norm (host sync)."""
+        if self.flat:
+            return self.opt.last_grad_norm()
+        return None if self._host_norm is None else float(self._host_norm)
 
     def _sdpa_ctx(self):
         if self.sdpa is None:
@@ -246,6 +304,12 @@ def main(argv=None):
                     help="at TP > 1: split the residual stream / LayerNorms / dropouts over the ranks by token")
     ap.add_argument("--sdpa", choices=["math", "efficient", "flash"], default=None,
                     help="pin the scaled-dot-product-attention backend (default: PyTorch's choice)")
+    ap.add_argument("--max-grad-norm", type=float, default=None, help="clip gradients by this global L2 norm")
+    ap.add_argument("--warmup-steps", type=int, default=0, help="linear learning-rate warmup (needs --total-steps)")
+    ap.add_argument("--total-steps", type=int, default=None,
+                    help="linear decay of the learning rate to zero at this step (default: constant)")
+    ap.add_argument("--no-decay-bias-norm", action="store_true",
+                    help="no weight decay on biases and LayerNorm parameters")
     a = ap.parse_args(argv)
     if a.seed is not None:
         torch.manual_seed(a.seed)
@@ -266,7 +330,8 @@ def main(argv=None):
     cfg = BertConfig(layers=a.layers, dropout=a.dropout, sequence_parallel=a.sequence_parallel)
     tr = BertTrainer(cfg, a.batch, a.seq, dev, tp,
                      graph=False if a.no_graph else (True if a.graph else None),
-                     flat_adamw=False if a.no_flat_adamw else None, sdpa=a.sdpa)
+                     flat_adamw=False if a.no_flat_adamw else None, sdpa=a.sdpa, max_grad_norm=a.max_grad_norm,
+                     warmup_steps=a.warmup_steps, total_steps=a.total_steps, no_decay_bias_norm=a.no_decay_bias_norm)
     from ..ops import native_stats
 
     per_step = None
@@ -304,6 +369,10 @@ def main(argv=None):
                           "seq_len": a.seq, "ms_per_step": 1e3 * dt / a.steps, "loss": float(loss),
                           "dtype": "bf16", "data": "synthetic", "layers": a.layers,
                           "hipgraph": tr.graph is not None,
+                          "lr_schedule": "constant" if tr.schedule is None else
+                          {"kind": "linear", "warmup_steps": tr.schedule[1], "total_steps": tr.schedule[2]},
+                          "max_grad_norm": a.max_grad_norm, "grad_norm": tr.last_grad_norm(),
+                          "no_decay_bias_norm": a.no_decay_bias_norm,
                           "calls_per_step_native_vs_fallback": per_step,
                           "optimizer": "flat bf16 AdamW (fp32 master)" if tr.flat else "torch fused AdamW"}),
               flush=True)

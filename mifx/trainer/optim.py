@@ -80,20 +80,53 @@ class FlatAdamW:
         chunked kernel (a per-step table of their addresses), `zero_grad()` sets them to None -- no zero-fill
         and no `grad += new` accumulate kernel per parameter per step;
       * "views": gradients are views of one flat gradient buffer that autograd accumulates into (one memset
-        per `zero_grad()`); the flat kernel is then hipGraph-capturable (device-side step counter)."""
+        per `zero_grad()`); the flat kernel is then hipGraph-capturable (device-side step counter).
+
+    Fine-tuning recipe (all off by default; with them off the step is the plain update, bit for bit):
+      * `max_grad_norm`: clip by the global L2 norm of all gradients (torch.nn.utils.clip_grad_norm_ semantics,
+        error_if_nonfinite=False). Two extra launches per step (per-chunk sums of squares, then one workgroup
+        that writes {coef, norm}); no atomics, bit-reproducible;
+      * `schedule=("linear", warmup_steps, total_steps)`: linear warmup from 0, then linear decay to 0 at
+        total_steps, stepped once per update (LambdaLR with the usual lambda). The kernel evaluates it from the
+        device-side step counter, so a captured step follows the schedule on every replay;
+      * `no_decay`: parameters for which it returns true get weight decay 0 (a per-parameter table).
+    On the GPU these need grads="own" without overlap (a bucket launched during the backward cannot know the
+    global norm; the "views" kernel has no parameter boundaries). On the CPU they run through the PyTorch
+    reference (mifx.ops.adamw.adamw_recipe_reference_), which reads each parameter's `.grad`.
+    `last_grad_norm()` / `last_lr()` report the last step's values (a host sync each: for logging).
+    `state_dict()` carries the step counter, so `load_state_dict()` resumes the schedule where it stopped."""
 
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
                  dtype: torch.dtype = torch.bfloat16, grads: str | None = None, overlap: bool | None = None,
-                 bucket_elems: int = 8 << 20):
+                 bucket_elems: int = 8 << 20, max_grad_norm: float | None = None, schedule: tuple | None = None,
+                 no_decay=None):
         self.params = [p for p in params if p.requires_grad]
         self.lr, self.betas, self.eps, self.wd = lr, betas, eps, weight_decay
         dev = self.params[0].device
+        if schedule is not None:
+            if len(schedule) != 3 or schedule[0] != "linear":
+                raise ValueError('schedule must be None or ("linear", warmup_steps, total_steps)')
+            warmup, total = int(schedule[1]), int(schedule[2])
+            if warmup < 0 or total < 0 or total <= warmup:
+                raise ValueError(f"schedule needs 0 <= warmup_steps < total_steps, got {warmup}, {total}")
+            schedule = ("linear", warmup, total)
+        if max_grad_norm is not None and not float(max_grad_norm) > 0:
+            raise ValueError(f"max_grad_norm must be positive, got {max_grad_norm}")
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.schedule = schedule
+        self.recipe = max_grad_norm is not None or schedule is not None or no_decay is not None
+        if self.recipe and overlap:
+            raise ValueError("FlatAdamW: max_grad_norm / schedule / no_decay cannot be combined with overlap=True "
+                             "(a bucket updated during the backward cannot know the global gradient norm)")
         if grads is None:
             grads = "own" if dev.type == "cuda" and dtype == torch.bfloat16 else "views"
         if grads not in ("own", "views"):
             raise ValueError("grads must be 'own' or 'views'")
         if grads == "own" and (dev.type != "cuda" or dtype != torch.bfloat16):
             raise ValueError("grads='own' needs bf16 parameters on the GPU")
+        if self.recipe and grads == "views" and dev.type == "cuda":
+            raise ValueError("FlatAdamW: max_grad_norm / schedule / no_decay on the GPU need grads='own' (the flat "
+                             "'views' kernel has no parameter boundaries)")
         self.mode = grads
         align = 8 if grads == "own" else 1  # 16-byte aligned bf16 / 32-byte fp32 vectors per parameter
         offs, off = [], 0
@@ -108,6 +141,10 @@ class FlatAdamW:
         self.m = torch.zeros(n, device=dev, dtype=torch.float32)
         self.v = torch.zeros(n, device=dev, dtype=torch.float32)
         self.step_count = torch.zeros((), device=dev, dtype=torch.int32)
+        self._offs = offs
+        self._pwd_host = None if no_decay is None else [0.0 if no_decay(p) else float(weight_decay)
+                                                        for p in self.params]
+        self._cpu_norm = None
         with torch.no_grad():
             for p, off in zip(self.params, offs):
                 k = p.numel()
@@ -142,6 +179,16 @@ class FlatAdamW:
             if overlap is None:
                 overlap = os.environ.get("MIFX_ADAMW_OVERLAP", "0") == "1"
             self.overlap = bool(overlap)
+            if self.overlap and self.recipe:
+                raise ValueError("FlatAdamW: max_grad_norm / schedule / no_decay cannot be combined with the "
+                                 "overlapped update (MIFX_ADAMW_OVERLAP=1)")
+            # recipe buffers, allocated here: nothing may allocate during a capture
+            self.pwd = None if self._pwd_host is None else torch.tensor(self._pwd_host, dtype=torch.float32,
+                                                                        device=dev)
+            self.clip = self._partial = None
+            if self.max_grad_norm is not None:
+                self._partial = torch.zeros(len(bp), dtype=torch.float32, device=dev)  # per-chunk sums of squares
+                self.clip = torch.zeros(2, dtype=torch.float32, device=dev)  # {coef, norm} of the last step
             if self.overlap:
                 self._buckets, cur, acc = [], [], 0
                 for i, p in enumerate(self.params):
@@ -224,6 +271,17 @@ class FlatAdamW:
     def step(self) -> None:
         from ..ops.adamw import adamw_chunks_, adamw_flat_
 
+        if self.mode == "views" and self.recipe:  # CPU: the PyTorch reference, parameter by parameter
+            from ..ops.adamw import adamw_recipe_reference_
+
+            with torch.no_grad():
+                sl = [slice(o, o + p.numel()) for o, p in zip(self._offs, self.params)]
+                self._cpu_norm, _ = adamw_recipe_reference_(
+                    [self.flat[s] for s in sl], [p.grad for p in self.params], [self.master[s] for s in sl],
+                    [self.m[s] for s in sl], [self.v[s] for s in sl], self.step_count, self.lr, self.betas[0],
+                    self.betas[1], self.eps, self.wd if self._pwd_host is None else self._pwd_host,
+                    max_grad_norm=self.max_grad_norm, schedule=self.schedule)
+            return
         if self.mode == "views":
             adamw_flat_(self.flat, self.flat_grad, self.master, self.m, self.v, self.step_count, self.lr,
                         self.betas[0], self.betas[1], self.eps, self.wd)
@@ -258,8 +316,37 @@ class FlatAdamW:
         elif addr != self._addr:  # eager: upload only when autograd handed out new gradient addresses
             self._gptr.copy_(torch.tensor(addr, dtype=torch.int64).pin_memory(), non_blocking=True)
             self._addr = addr
+        if self.recipe:
+            from ..ops.adamw import adamw_chunks_ex_, clip_coef_
+
+            if self.max_grad_norm is not None:
+                clip_coef_(self._gptr, self.bp, self.bo, self.bn, self._partial, self.max_grad_norm, self.clip)
+            adamw_chunks_ex_(self.flat, self._gptr, self.poff, self.bp, self.bo, self.bn, self.master, self.m, self.v,
+                             self.step_count, self.lr, self.betas[0], self.betas[1], self.eps, self.wd,
+                             clip=self.clip, pwd=self.pwd, schedule=self.schedule)
+            return
         adamw_chunks_(self.flat, self._gptr, self.poff, self.bp, self.bo, self.bn, self.master, self.m, self.v,
                       self.step_count, self.lr, self.betas[0], self.betas[1], self.eps, self.wd)
 
+    def last_grad_norm(self) -> float | None:
+        """Global gradient norm (before clipping) of the last step; None without max_grad_norm. Host sync."""
+        if self.max_grad_norm is None:
+            return None
+        return float(self.clip[1]) if self.mode == "own" else self._cpu_norm
+
+    def last_lr(self) -> float:
+        """Learning rate the last step used (the schedule at step_count - 1). Host sync."""
+        from ..ops.adamw import scheduled_lr
+
+        return scheduled_lr(self.lr, self.schedule, max(0, int(self.step_count) - 1))
+
     def state_dict(self) -> dict:
         return {"master": self.master, "m": self.m, "v": self.v, "step": self.step_count}
+
+    @torch.no_grad()
+    def load_state_dict(self, sd: dict) -> None:
+        """Resume from a state_dict() of an optimizer over the same parameters: master weights, moments and the step
+        counter (which also places the learning-rate schedule); the model weights are re-derived from the master."""
+        for k, dst in (("master", self.master), ("m", self.m), ("v", self.v), ("step", self.step_count)):
+            dst.copy_(sd[k])
+        self.flat.copy_(self.master.to(self.flat.dtype))
