@@ -31,11 +31,18 @@ __device__ __forceinline__ float opt_update(const OptHyper& hp, float w, float g
     a0 = an;
     return fabsf(a1) > hp.l1 ? (copysignf(hp.l1, a1) - a1) / quad : 0.f;
   }
-  a0 = hp.beta1 * a0 + (1.f - hp.beta1) * g;
-  a1 = hp.beta2 * a1 + (1.f - hp.beta2) * g * g;
-  const float bc1 = 1.f - powf(hp.beta1, (float)step);
-  const float bc2 = 1.f - powf(hp.beta2, (float)step);
-  return w - hp.lr * (a0 / bc1) / (sqrtf(a1 / bc2) + hp.eps);
+  {
+    // Adam: every operation rounded on its own. With FMA contraction the compiler fuses these sums of products
+    // differently from kernel to kernel ((1 - beta) * g became fma(-beta, g, g) in wd_res_opt_sc and a packed multiply
+    // in wd_opt1_sc), and the variants of one step then disagree in the last bits of the moments
+    // (tests/test_wd_optimizer.py asserts that they are bit-identical).
+#pragma clang fp contract(off)
+    a0 = hp.beta1 * a0 + (1.f - hp.beta1) * g;
+    a1 = hp.beta2 * a1 + (1.f - hp.beta2) * g * g;
+    const float bc1 = 1.f - powf(hp.beta1, (float)step);
+    const float bc2 = 1.f - powf(hp.beta2, (float)step);
+    return w - hp.lr * (a0 / bc1) / (sqrtf(a1 / bc2) + hp.eps);
+  }
 }
 
 // per-workgroup optimizer step slots (see csrc/wide_deep.hip)

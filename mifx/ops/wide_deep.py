@@ -147,6 +147,8 @@ class XcdReduce:
         self.xep = torch.zeros(STEP_SLOTS, dtype=torch.int64, device=device)
 
     def _call(self, slab, groups, out, wsc, param_sc, s0_sc, s1_sc, wt_out, step_ctr, hyper_dnn, hyper_wide):
+        if slab.shape[-1] != self.stride or slab.numel() < groups * self.stride or not slab.is_contiguous():
+            raise ValueError("slab must be contiguous [>= groups, stride]")
         rc = _fns()["reduce_xcd_opt"](ptr(slab), int(groups), self.stride, ptr(self.xcd_of), ptr(self.part),
                                       ptr(self.ok), ptr(self.xep), ptr(out), ptr(wsc), ptr(param_sc), ptr(s0_sc),
                                       ptr(s1_sc), ptr(wt_out), ptr(step_ctr), ptr(hyper_dnn), ptr(hyper_wide),
@@ -156,15 +158,6 @@ class XcdReduce:
     def apply_sc(self, slab: torch.Tensor, groups: int, wsc, param_sc, s0_sc, s1_sc, wt_out, step_ctr, hyper_dnn,
                  hyper_wide) -> None:
         _check_step_ctr(step_ctr)
-        if self.fused:
-            if slab.shape[-1] != self.stride or slab.numel() < groups * self.stride or not slab.is_contiguous():
-                raise ValueError("slab must be contiguous [>= groups, stride]")
-            rc = _fns()["reduce_res_opt_fused"](ptr(slab), int(groups), self.stride, ptr(self.part), ptr(self.ticket),
-                                                ptr(wsc), ptr(param_sc), ptr(s0_sc), ptr(s1_sc), ptr(wt_out),
-                                                ptr(step_ctr), ptr(hyper_dnn), ptr(hyper_wide),
-                                                stream_handle(slab.device))
-            check(rc, "mifx_wd_reduce_res_opt_fused")
-            return
         self._call(slab, groups, None, wsc, param_sc, s0_sc, s1_sc, wt_out, step_ctr, hyper_dnn, hyper_wide)
 
     def sum_into(self, slab: torch.Tensor, groups: int, out: torch.Tensor) -> None:

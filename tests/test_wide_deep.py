@@ -8,6 +8,10 @@ from mifx.models import wide_deep as wdm
 from mifx.trainer.fused_wide_deep import OptSpec
 from mifx.trainer.torch_wide_deep import TorchWideDeepTrainer
 
+# the "*_reg" cases of the variant tests: FTRL's L1 shrinkage, its 2 * l2 term and its general lr_power (powf) branch
+_REG_OPTS = {"dnn_opt": OptSpec("adagrad", lr=0.05),
+             "wide_opt": OptSpec("ftrl", lr=0.2, l1=0.5, l2=0.1, lr_power=-0.75)}
+
 
 def _canonical_forward(vec, dense, ids):
     """numpy emulation of the kernel's padded forward (fp32), biases via constant-1 column."""
@@ -402,6 +406,32 @@ def test_chain_trainer_xcd_reduce_matches_plain_reduce():
 
 
 @pytest.mark.gpu
+def test_chain_trainer_recorded_xcd_reduce_matches_default(monkeypatch):
+    """MIFX_WD_RES=0 selects the placement-recorded XCD reduction (XcdReduce: wd_reduce_xcd + wd_xcd_opt_sc<1> on
+    the xcd_of the chained kernel records) instead of the residue-class default; both train the same."""
+    from mifx.data.synthetic import synthetic_records
+    from mifx.ops import wide_deep as wdk
+    from mifx.trainer.fused_wide_deep import FusedWideDeepTrainer
+
+    recs = synthetic_records(1 << 16, device="cuda", seed=9)
+    out = []
+    for res, cls in (("0", wdk.XcdReduce), (None, wdk.ResReduce)):
+        if res is None:
+            monkeypatch.delenv("MIFX_WD_RES", raising=False)
+        else:
+            monkeypatch.setenv("MIFX_WD_RES", res)
+        tr = FusedWideDeepTrainer(wdm.WideDeepModel(seed=3), batch=16384, device="cuda", in_kernel_tail=False)
+        assert type(tr._xcd) is cls
+        tr.set_data(recs)
+        for _ in range(4):
+            tr.step()
+        torch.cuda.synchronize()
+        assert tr.steps_done == 4
+        out.append(tr.param.clone())
+    np.testing.assert_allclose(out[0].cpu().numpy(), out[1].cpu().numpy(), rtol=1e-4, atol=1e-6)
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("batch", [40, 16384])
 def test_chain_kernel_step_matches_tile_kernel(batch):
     """The register-chained kernel against the LDS-tile kernel: same data, same init, one fused step each
@@ -494,16 +524,20 @@ def test_multi_step_graph_matches_single_step_replays():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("batch,opt", [(65536, "adagrad_ftrl"), (16384, "adam"), (8192, "sgd")])
+@pytest.mark.parametrize("batch,opt", [(65536, "adagrad_ftrl"), (16384, "adam"), (8192, "sgd"),
+                                       (8192, "adagrad_ftrl_reg")])
 def test_in_kernel_tail_step_matches_three_launch_step(batch, opt):
     """The one-launch step (slab reduction + optimizer inside the fused kernel after two grid barriers) against the
     three-launch step (fused, XCD-local reduce, reduce + optimizer) over 12 steps with multi-step hipGraph replays:
-    same math, another fp32 association of the slab sum -> allclose; no barrier may time out."""
+    same math, another fp32 association of the slab sum -> allclose; no barrier may time out. adagrad_ftrl_reg: FTRL
+    with l1, l2 and the general lr_power branch (the three-launch side is anchored to an fp64 reference in
+    tests/test_wd_optimizer.py)."""
     from mifx.trainer.fused_wide_deep import FusedWideDeepTrainer
 
     recs = synthetic_records(1 << 18, device="cuda", seed=13)
     lr = 1e-3 if opt == "adam" else 1e-6  # (sum-reduced loss over the batch: plain SGD needs a tiny step)
-    kw = {} if opt == "adagrad_ftrl" else {"dnn_opt": OptSpec(opt, lr=lr), "wide_opt": OptSpec(opt, lr=lr)}
+    kw = {} if opt == "adagrad_ftrl" else _REG_OPTS if opt == "adagrad_ftrl_reg" else \
+        {"dnn_opt": OptSpec(opt, lr=lr), "wide_opt": OptSpec(opt, lr=lr)}
     out = []
     for tail in (True, False):
         # (the three-launch side on the same T = 128 build: large_tile=False)
@@ -544,7 +578,7 @@ def test_in_kernel_tail_is_run_to_run_deterministic_and_image_consistent():
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("batch,opt", [(40, "adagrad_ftrl"), (128, "adagrad_ftrl"), (1, "adagrad_ftrl"),
-                                       (40, "adam"), (77, "sgd"), (40, "ftrl")])
+                                       (40, "adam"), (77, "sgd"), (40, "ftrl"), (1, "adagrad_ftrl_reg")])
 def test_persistent_small_batch_matches_slab_path(batch, opt):
     """The persistent single-workgroup kernel (n whole steps in one launch, weight image resident in LDS, optimizer
     in the workgroup) against the grid-1 slab path (fused kernel + reduce/optimizer kernel per step): the same fp32
@@ -555,8 +589,9 @@ def test_persistent_small_batch_matches_slab_path(batch, opt):
 
     recs = synthetic_records(300, device="cuda", seed=21)
     lr = 1e-3 if opt == "adam" else 1e-4 if opt == "sgd" else None
-    kw = {} if opt == "adagrad_ftrl" else {"dnn_opt": OptSpec(opt, lr=lr) if lr else OptSpec(opt, lr=0.05),
-                                             "wide_opt": OptSpec(opt, lr=lr) if lr else OptSpec(opt, lr=0.2)}
+    kw = {} if opt == "adagrad_ftrl" else _REG_OPTS if opt == "adagrad_ftrl_reg" else \
+        {"dnn_opt": OptSpec(opt, lr=lr) if lr else OptSpec(opt, lr=0.05),
+         "wide_opt": OptSpec(opt, lr=lr) if lr else OptSpec(opt, lr=0.2)}
     out = []
     for persistent in (True, False):
         tr = FusedWideDeepTrainer(wdm.WideDeepModel(seed=5), batch=batch, device="cuda", persistent=persistent,
@@ -620,20 +655,24 @@ def test_large_tile_matches_t128(batch):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("batch", [40, 100])
-def test_one_launch_step_bit_identical(batch):
+@pytest.mark.parametrize("batch,opt", [pytest.param(40, "adagrad_ftrl", id="40"),
+                                       pytest.param(100, "adagrad_ftrl", id="100"),
+                                       pytest.param(40, "adagrad_ftrl_reg", id="40-adagrad_ftrl_reg")])
+def test_one_launch_step_bit_identical(batch, opt):
     """The one-launch step (csrc/wd_chain.hip help_update: the optimizer in extra workgroups of the fused launch,
     waiting for workgroup 0's gradient row) trains bit-identically to the fused kernel + wd_opt1_sc two-kernel step:
     eager steps, captured multi-step graphs, and a checkpoint rewind in between (which resets the published-step
-    flag). Batch 40: the T = 64 build; 100: the 8-wave T = 128 build."""
+    flag). Batch 40: the T = 64 build; 100: the 8-wave T = 128 build. adagrad_ftrl_reg: FTRL with l1, l2 and
+    lr_power = -0.75."""
     from mifx.trainer.fused_wide_deep import FusedWideDeepTrainer
 
     dev = torch.device("cuda")
     rec = synthetic_records(batch * 5 + 77, device=dev, seed=43)
+    kw = _REG_OPTS if opt == "adagrad_ftrl_reg" else {}
     out = {}
     for one in (False, True):
         tr = FusedWideDeepTrainer(wdm.WideDeepModel(seed=8), batch=batch, device=dev, one_launch=one,
-                                  shuffle_seed=0x5EED)
+                                  shuffle_seed=0x5EED, **kw)
         assert (tr._one is not None) == one
         tr.set_data(rec)
         for _ in range(3):
