@@ -11,15 +11,17 @@ from mifx.orchestration import LocalDagRunner, Pipeline  # noqa: E402
 
 
 def create_pipeline(root: str, num_images: int, image_size: int, crop: int, classes: int, steps: int, batch: int,
-                    num_gpus: int = 1, checkpoint_every: int = 0, accum_steps: int = 1, name: str = "resnet_image_pipeline"):
+                    num_gpus: int = 1, checkpoint_every: int = 0, accum_steps: int = 1, name: str = "resnet_image_pipeline",
+                    optimizer: dict | None = None):
     """num_gpus > 1: the Trainer component runs data-parallel, one rank per GPU (BASELINE config 5: DP=8);
-    batch is per replica."""
+    batch is per replica. optimizer: the Trainer's recipe keys (lr_schedule, end_lr, lars, lars_eta, lars_clip,
+    label_smoothing)."""
     gen = ImageExampleGen(num_synthetic=num_images, image_size=image_size, num_classes=classes)
     tfm = ImageTransform(input_data=gen.outputs["examples"], crop=crop)
     trainer = ImageTrainer(examples=gen.outputs["examples"], transform_output=tfm.outputs["transform_output"],
                            train_steps=steps, batch_size=batch, num_classes=classes,
                            custom_config={"num_gpus": num_gpus, "checkpoint_every": checkpoint_every,
-                                          "accum_steps": accum_steps})
+                                          "accum_steps": accum_steps, **(optimizer or {})})
     return Pipeline(name, os.path.join(root, "pipeline"), [gen, tfm, trainer], enable_cache=True,
                     metadata_db_root=os.path.join(root, "metadata.db"))
 

@@ -125,6 +125,24 @@ class ImageTrainerSpec(ComponentSpec):
                   "custom_config": ExecutionParameter(optional=True)}
 
 
+def resolve_optimizer_config(cc: dict, learning_rate: float, train_steps: int) -> dict:
+    """custom_config -> the ResNetTrainer optimizer arguments (what the result records under "optimizer"). With
+    lr_schedule unset the learning rate is the linear warmup over train_steps // 10 steps, then constant."""
+    kind = cc.get("lr_schedule") or "constant"
+    if kind not in ("constant", "cosine", "poly"):
+        raise ValueError(f'lr_schedule must be "constant", "cosine" or "poly", got {kind!r}')
+    decays = kind != "constant"
+    if not decays and cc.get("end_lr"):
+        raise ValueError('end_lr needs lr_schedule="cosine" or "poly"')
+    lars = bool(cc.get("lars", False))
+    if not lars and (cc.get("lars_eta") is not None or cc.get("lars_clip")):
+        raise ValueError("lars_eta / lars_clip need lars")
+    return {"learning_rate": float(learning_rate), "lr_schedule": kind, "warmup_steps": max(1, train_steps // 10),
+            "total_steps": int(train_steps) if decays else None, "end_lr": float(cc.get("end_lr", 0.0) or 0.0),
+            "lars": lars, "lars_eta": float(cc.get("lars_eta", 0.001) if lars else 0.001),
+            "lars_clip": bool(cc.get("lars_clip", False)), "label_smoothing": float(cc.get("label_smoothing", 0.0))}
+
+
 def run_image_rank(spec: dict) -> dict:
     """One rank (or the only process) of the image Trainer: ResNet-50 v2 on the examples of `spec`, resuming
     from the latest checkpoint in <out>/serving_model_dir, checkpointing every `checkpoint_every` steps (rank 0
@@ -149,10 +167,13 @@ def run_image_rank(spec: dict) -> dict:
     if dev == "cuda" and world > 1:
         dev = f"cuda:{0 if os.environ.get('MIFX_SHARED_GPU') == '1' else int(os.environ.get('LOCAL_RANK', 0))}"
     steps = int(spec["train_steps"])
+    oc = resolve_optimizer_config(cc, float(spec["learning_rate"]), steps)
     tr = ResNetTrainer(int(spec["batch_size"]), dev, imgs, labels, num_classes=int(spec["num_classes"]),
-                       lr=float(spec["learning_rate"]), warmup_steps=max(1, steps // 10), mean=tuple(tf["mean"]),
+                       lr=oc["learning_rate"], warmup_steps=oc["warmup_steps"], mean=tuple(tf["mean"]),
                        std=tuple(tf["std"]), crop=int(tf["crop"]), process_group=pg, seed=int(cc.get("seed", 0)),
-                       accum_steps=int(cc.get("accum_steps", 1)))
+                       accum_steps=int(cc.get("accum_steps", 1)), lr_schedule=oc["lr_schedule"],
+                       total_steps=oc["total_steps"], end_lr=oc["end_lr"], lars=oc["lars"], lars_eta=oc["lars_eta"],
+                       lars_clip=oc["lars_clip"], label_smoothing=oc["label_smoothing"])
     model_dir = os.path.join(spec["out_dir"], "serving_model_dir")
     ck = ResNetTrainer.latest_checkpoint(model_dir)
     if ck:
@@ -174,7 +195,8 @@ def run_image_rank(spec: dict) -> dict:
     tr.check()
     secs = time.time() - t0
     res = {"final_loss": float(loss), "world": world, "steps": tr.step_idx, "resumed_from": ck,
-           "train_images_per_sec": (tr.step_idx - s0) * tr.batch * tr.accum * world / max(secs, 1e-9)}
+           "train_images_per_sec": (tr.step_idx - s0) * tr.batch * tr.accum * world / max(secs, 1e-9),
+           "optimizer": dict(oc, final_lr=tr.last_lr())}
     if rank == 0:
         tr.save_checkpoint(model_dir)
         ev_imgs = torch.from_numpy(np.load(os.path.join(spec["eval_uri"], "images.npy"), allow_pickle=False))
@@ -191,7 +213,10 @@ class ImageTrainerExecutor(BaseExecutor):
     """custom_config: num_gpus (> 1: one rank per GPU launched by the component itself, mifx.trainer.distributed;
     the reference runs its ResNet-50 workers as a hand-written TFJob, `tf-job-simple-v1beta2.jsonnet:22-40`),
     checkpoint_every (steps; resume from the latest checkpoint like the reference's Saver,
-    `research/pate_2017/deep_cnn.py:489,541-542`), accum_steps, seed, timeout_s."""
+    `research/pate_2017/deep_cnn.py:489,541-542`), accum_steps, seed, timeout_s. Optimizer recipe
+    (`resolve_optimizer_config`; recorded in metrics.json under "optimizer" and in the output's custom properties):
+    lr_schedule ("constant" | "cosine" | "poly", decaying to end_lr at train_steps), lars, lars_eta, lars_clip,
+    label_smoothing."""
 
     def Do(self, input_dict, output_dict, exec_properties):  # noqa: N802
         ex = {a.split: a.uri for a in input_dict["examples"]}
@@ -218,6 +243,9 @@ class ImageTrainerExecutor(BaseExecutor):
         out.custom_properties.update({"eval_accuracy": float(res["eval_accuracy"]),
                                       "final_loss": float(res["final_loss"]), "num_replicas": int(res["world"]),
                                       "train_images_per_sec": float(res["train_images_per_sec"])})
+        # the resolved optimizer recipe (bools as 0 / 1, unset values left out: MLMD properties are int / float / str)
+        out.custom_properties.update({k: int(v) if isinstance(v, bool) else v
+                                      for k, v in (res.get("optimizer") or {}).items() if v is not None})
         self.context.logger.info("ImageTrainer: %d replica(s), loss %.4f eval accuracy %.4f", res["world"],
                                  res["final_loss"], res["eval_accuracy"])
 

@@ -1,22 +1,64 @@
 """Multi-tensor fused SGD (csrc/sgd.hip): weight decay, momentum, dampening and Nesterov for a list of fp32
 parameters in ONE launch, learning rate read from a device tensor (graph-capturable). `FusedSGDTables` builds the
 per-tensor address / chunk tables once, outside any capture; `sgd_reference_` is the torch.optim.SGD foreach
-update it replaces (the parity check of tests/test_sgd_fused.py)."""
+update it replaces (the parity check of tests/test_sgd_fused.py).
+
+Large-batch recipe (tests/test_sgd_lars.py): `FusedSGDTables(..., lars=...)` + `step_ex` evaluate LARS trust ratios
+and the learning-rate schedule on the device from an int64 step counter, so a captured step follows both with no
+host write between replays; `scheduled_lr` is the schedule's Python twin and `lars_reference_` the same update from
+stock torch ops (CPU runs, eager steps, the parity checks)."""
 from __future__ import annotations
 
+import ctypes
 import functools
+import math
 
 import torch
 
 from . import _lib
-from ._lib import F32, I32, VP, check, ptr, sig, stream_handle
+from ._lib import F32, I32, I64, VP, check, ptr, sig, stream_handle
+
+F64 = ctypes.c_double
+SCHEDULES = ("constant", "cosine", "poly")
 
 
 @functools.lru_cache(maxsize=None)
 def _fns():
     lib = _lib.load("sgd")
     return {"chunk": sig(lib, "mifx_sgd_chunk_size", []),
-            "run": sig(lib, "mifx_sgd_chunks", [VP, VP, VP, VP, VP, VP, VP, I32, VP, F32, F32, I32, VP])}
+            "run": sig(lib, "mifx_sgd_chunks", [VP, VP, VP, VP, VP, VP, VP, I32, VP, F32, F32, I32, VP]),
+            "run_ex": sig(lib, "mifx_sgd_step_ex", [VP, VP, VP, VP, VP, VP, VP, I32, VP, VP, I32, VP, VP, VP, VP, VP,
+                                                    VP, I32, I64, I64, F64, F64, F64, F64, I32, F32, F32, I32, VP])}
+
+
+def scheduled_lr(kind: str, base: float, warmup: int, total: int | None, end: float, t: int) -> float:
+    """Learning rate of the update that follows `t` completed ones, in double (the twin of lr_at in csrc/sgd.hip,
+    operation for operation). Every kind starts with the linear warmup base * min(1, (t + 1) / max(1, warmup));
+    "constant" keeps that rule forever, "cosine" and "poly" (power 2) decay from base at t = warmup to `end` at
+    t = total and stay there."""
+    if kind not in SCHEDULES:
+        raise ValueError(f"lr schedule must be one of {SCHEDULES}, got {kind!r}")
+    base, end, warmup, t = float(base), float(end), int(warmup), int(t)
+    if base < 0 or end < 0 or warmup < 0 or t < 0 or (total is not None and int(total) < 0):
+        raise ValueError("lr schedule: base, end, warmup, total and t must be non-negative")
+    if kind != "constant" and (total is None or int(total) <= warmup):
+        raise ValueError(f'lr schedule "{kind}" needs total > warmup, got total={total} warmup={warmup}')
+    if kind == "constant" or t < warmup:
+        return base * min(1.0, (t + 1) / max(1, warmup))
+    total = int(total)
+    if t >= total:
+        return end
+    x = (t - warmup) / (total - warmup)
+    if kind == "cosine":
+        return end + (base - end) * 0.5 * (1.0 + math.cos(math.pi * x))
+    q = 1.0 - x
+    return end + (base - end) * (q * q)
+
+
+def _check_schedule(schedule) -> tuple:
+    kind, base, warmup, total, end = schedule
+    scheduled_lr(kind, base, warmup, total, end, 0)  # raises on an invalid combination
+    return SCHEDULES.index(kind), float(base), int(warmup), int(total or 0), float(end)
 
 
 def _dense(t: torch.Tensor) -> bool:
@@ -32,12 +74,30 @@ def _dense(t: torch.Tensor) -> bool:
 class FusedSGDTables:
     """Device tables for one fused update of `params` (fp32, CUDA) with their momentum `bufs` and a per-tensor
     weight decay; the gradients' addresses are set per step (`set_grads`). The tables hold raw addresses: rebuild
-    them (`matches`) when a parameter or momentum buffer is reallocated."""
+    them (`matches`) when a parameter or momentum buffer is reallocated.
+
+    lars = dict(eta=0.001, eps=1e-8, clip=False, adapt=[bool per tensor]) adds the per-tensor tables of `step_ex`:
+    tensor i's gradient is scaled by the trust ratio eta ||w|| / (||g|| + wd_i ||w|| + eps) when adapt[i] (default:
+    tensors with more than one dimension) and both norms are non-zero, else by exactly 1; clip=True is LARC
+    clipping, min(ratio / lr_t, 1)."""
 
     CAPTURES = 4  # graph captures one table set can serve (each keeps its own pinned address buffer)
 
-    def __init__(self, params, bufs, wds, grads=None):
+    def __init__(self, params, bufs, wds, grads=None, lars=None):
         dev = params[0].device
+        if lars is not None:
+            unknown = set(lars) - {"eta", "eps", "clip", "adapt"}
+            if unknown:
+                raise ValueError(f"fused SGD: unknown lars option(s) {sorted(unknown)}")
+            eta, eps = float(lars.get("eta", 0.001)), float(lars.get("eps", 1e-8))
+            if not (eta > 0 and math.isfinite(eta)) or not (eps >= 0 and math.isfinite(eps)):
+                raise ValueError("fused SGD: lars needs eta > 0 and eps >= 0")
+            adapt = lars.get("adapt")
+            adapt = [p.ndim > 1 for p in params] if adapt is None else [bool(a) for a in adapt]
+            if len(adapt) != len(params):
+                raise ValueError("fused SGD: lars adapt needs one flag per tensor")
+            if any(float(w) < 0 for w in wds):
+                raise ValueError("fused SGD: lars needs non-negative weight decays")
         # the update is elementwise, so any dense layout works (channels_last convolution weights) as long as a
         # parameter, its gradient and its momentum buffer share it: element i of one is element i of the others
         for t in (*params, *bufs):
@@ -62,6 +122,22 @@ class FusedSGDTables:
         self.wd = torch.tensor([float(w) for w in wds], dtype=torch.float32, device=dev)
         self.tp, self.to, self.tn = (torch.tensor(x, dtype=torch.int32, device=dev) for x in (tp, to, tn))
         self.nblocks = len(tp)
+        # step_ex: {-lr_t, lr_t} written by the finalize kernel (read by the update, kept for last_lr)
+        self.lr_out = torch.zeros(2, dtype=torch.float32, device=dev)
+        self.lars = None
+        if lars is not None:
+            # a tensor's chunks are consecutive in the tables: tensor i owns partials [first[i], first[i + 1])
+            first = [0]
+            for p in params:
+                first.append(first[-1] + (p.numel() + ch - 1) // ch)
+            self.lars = {"eta": eta, "eps": eps, "clip": bool(lars.get("clip", False)), "adapt": adapt}
+            self.first = torch.tensor(first, dtype=torch.int32, device=dev)
+            self.adapt = torch.tensor([int(a) for a in adapt], dtype=torch.int32, device=dev)
+            self.pw = torch.zeros(self.nblocks, dtype=torch.float32, device=dev)
+            self.pg = torch.zeros(self.nblocks, dtype=torch.float32, device=dev)
+            self.ratio = torch.ones(len(params), dtype=torch.float32, device=dev)
+            self.norms = torch.zeros(len(params), 2, dtype=torch.float32, device=dev)
+        self._stepped_ex = False
         self.grads = None
         self._captured_hosts: list = []
         self._spare_hosts = [torch.zeros(len(params), dtype=torch.int64).pin_memory() for _ in range(self.CAPTURES)]
@@ -109,6 +185,67 @@ class FusedSGDTables:
                             ptr(self.tn), self.nblocks, ptr(neg_lr), float(momentum), float(dampening),
                             int(bool(nesterov)), stream_handle(neg_lr.device)), "mifx_sgd_chunks")
         torch.autograd.graph.increment_version(self.params)
+
+    def step_ex(self, step_dev: torch.Tensor, schedule, momentum: float, dampening: float, nesterov: bool) -> None:
+        """One update with the recipe evaluated on the device, so a captured step replays it: the learning rate is
+        `scheduled_lr(*schedule, t)` with schedule = (kind, base, warmup, total, end) and t = step_dev[0] (int64
+        device tensor: updates completed so far; read, not advanced), and with `lars` the gradients are scaled by
+        their tensors' trust ratios. Launches the norm pass, the finalize and the extended update on the current
+        stream; bumps the parameters' versions as `step` does."""
+        if self.grads is None:
+            raise RuntimeError("fused SGD: set_grads() before step_ex()")
+        if step_dev.dtype != torch.int64 or step_dev.device != self.pp.device or step_dev.numel() < 1:
+            raise ValueError("fused SGD: step_dev must be an int64 tensor on the parameters' device")
+        kind, base, warmup, total, end = _check_schedule(schedule)
+        L = self.lars
+        tabs = (self.first, self.adapt, self.pw, self.pg, self.ratio, self.norms) if L else (None,) * 6
+        check(_fns()["run_ex"](ptr(self.pp), ptr(self.gp), ptr(self.bp), ptr(self.wd), ptr(self.tp), ptr(self.to),
+                               ptr(self.tn), self.nblocks, ptr(tabs[0]), ptr(tabs[1]), len(self.params),
+                               ptr(tabs[2]), ptr(tabs[3]), ptr(tabs[4]), ptr(tabs[5]), ptr(step_dev),
+                               ptr(self.lr_out), kind, warmup, total, base, end, L["eta"] if L else 0.0,
+                               L["eps"] if L else 0.0, int(L["clip"]) if L else 0, float(momentum), float(dampening),
+                               int(bool(nesterov)), stream_handle(step_dev.device)), "mifx_sgd_step_ex")
+        torch.autograd.graph.increment_version(self.params)
+        self._stepped_ex = True
+
+    def last_lr(self) -> float | None:
+        """The learning rate the last `step_ex` (or replay of a graph that holds one) used; None before any."""
+        return float(self.lr_out[1]) if self._stepped_ex else None
+
+    def last_trust_ratios(self) -> torch.Tensor | None:
+        """[P] fp32 (CPU) trust ratios of the last `step_ex`; None without `lars` or before any."""
+        return self.ratio.cpu() if self.lars and self._stepped_ex else None
+
+    def last_norms(self) -> torch.Tensor | None:
+        """[P, 2] fp32 (CPU) {||w||, ||g||} of the last `step_ex`; None without `lars` or before any."""
+        return self.norms.cpu() if self.lars and self._stepped_ex else None
+
+
+@torch.no_grad()
+def lars_reference_(params, grads, bufs, wds, adapt, eta: float, eps: float, clip: bool, momentum: float,
+                    dampening: float, nesterov: bool, lr) -> list:
+    """The update of `FusedSGDTables.step_ex` from stock torch ops, in the tensors' own device and dtype:
+    g' = (g + wd w) * r with r = eta ||w|| / (||g|| + wd ||w|| + eps) for an adapted tensor with non-zero norms
+    (clip: min(r / lr, 1)), else 1; then `sgd_reference_` with wd = 0 on g'. `lr` is a float or a 0-dim tensor
+    (no host synchronisation, so it captures). Returns the ratios, one 0-dim tensor per parameter."""
+    scaled, ratios = [], []
+    p0 = params[0]  # (one dtype and device for the whole list)
+    lr_t = lr.to(p0.dtype) if isinstance(lr, torch.Tensor) else torch.tensor(float(lr), dtype=p0.dtype,
+                                                                              device=p0.device)
+    for p, g, wd, a in zip(params, grads, wds, adapt):
+        gg = g.add(p, alpha=wd) if wd else g
+        r = torch.ones((), dtype=p.dtype, device=p.device)
+        if a:
+            wn, gn = torch.linalg.vector_norm(p), torch.linalg.vector_norm(g)
+            q = eta * wn / (gn + wd * wn + eps)
+            if clip:
+                q = torch.clamp(q / lr_t, max=1.0)
+            r = torch.where((wn != 0) & (gn != 0), q, r)
+            gg = gg * r
+        scaled.append(gg)
+        ratios.append(r)
+    sgd_reference_(list(params), scaled, list(bufs), 0.0, momentum, dampening, nesterov, -lr_t)
+    return ratios
 
 
 @torch.no_grad()

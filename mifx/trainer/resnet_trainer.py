@@ -3,7 +3,9 @@ GPU), HBM-resident uint8 dataset with the fused crop/flip/normalize HIP kernel, 
 run on the hand-written implicit-GEMM kernel (csrc/gemm8.hip, mifx.ops.conv1x1 / conv3x3) with BatchNorm statistics,
 BatchNorm-backward sums and residual adds in its epilogues; weight gradients are deferred to grouped launches
 (mifx.ops.gemm.deferred_weight_grads); SGD + Nesterov momentum with linear warmup is one fused multi-tensor kernel
-(csrc/sgd.hip). What MIOpen still runs is listed in README.md.
+(csrc/sgd.hip). Optional large-batch recipe: LARS trust ratios, cosine / polynomial decay and label smoothing
+(lars=, lr_schedule=, label_smoothing=); in the captured step the ratios and the learning rate are computed on the
+device from the step counter, nothing is written by the host. What MIOpen still runs is listed in README.md.
 
 On the GPU the step is captured into hipGraphs after `graph_warmup` eager steps (graph=True, the default there):
 graph A = gradient zeroing + every micro-batch's input kernel, forward and backward (the step counter, learning rate
@@ -48,12 +50,40 @@ class ResNetTrainer:
     def __init__(self, batch: int, device, images: torch.Tensor, labels: torch.Tensor, num_classes: int = 1000,
                  lr: float = 0.1, momentum: float = 0.9, weight_decay: float = 5e-5, warmup_steps: int = 100,
                  process_group=None, mean=IMAGENET_MEAN, std=IMAGENET_STD, seed: int = 0, crop: int = 224,
-                 accum_steps: int = 1, graph: bool | None = None, graph_warmup: int = 2, force_dp: bool = False):
+                 accum_steps: int = 1, graph: bool | None = None, graph_warmup: int = 2, force_dp: bool = False,
+                 lr_schedule: str = "constant", total_steps: int | None = None, end_lr: float = 0.0,
+                 lars: bool = False, lars_eta: float = 0.001, lars_eps: float = 1e-8, lars_clip: bool = False,
+                 label_smoothing: float = 0.0):
         """batch: examples per micro-batch per replica; accum_steps micro-batches (each with its own BatchNorm
         statistics) are summed into one update. A data-parallel step over W ranks trains on W x accum_steps x batch
         examples: the global sample of the step is drawn from (seed, step) and rank r takes micro-batches
         r accum_steps .. (r + 1) accum_steps - 1 of it, so W ranks at accum 1 compute the same update as one
-        process at accum W (up to fp32 summation order)."""
+        process at accum W (up to fp32 summation order).
+
+        Large-batch recipe (all off by default): lr_schedule "cosine" / "poly" decays from lr after warmup_steps to
+        end_lr at total_steps (mifx.ops.sgd.scheduled_lr); lars scales every tensor with more than one dimension by
+        its trust ratio lars_eta ||w|| / (||g|| + wd ||w|| + lars_eps) in front of the SGD update (lars_clip: LARC
+        clipping), on the averaged gradients under data parallelism; label_smoothing goes to the cross entropy.
+        In the captured step the schedule and the ratios are evaluated on the device (csrc/sgd.hip)."""
+        from ..ops.sgd import scheduled_lr
+
+        scheduled_lr(lr_schedule, lr, warmup_steps, total_steps, end_lr, 0)  # ValueError on an invalid combination
+        if not 0.0 <= float(label_smoothing) < 1.0:
+            raise ValueError(f"label_smoothing must be in [0, 1), got {label_smoothing}")
+        if lars and not (float(lars_eta) > 0 and float(lars_eps) >= 0):
+            raise ValueError("lars needs lars_eta > 0 and lars_eps >= 0")
+        if (lars_clip or lars_eta != 0.001 or lars_eps != 1e-8) and not lars:
+            raise ValueError("lars_eta / lars_eps / lars_clip need lars=True")
+        if lr_schedule == "constant" and (total_steps is not None or end_lr):
+            raise ValueError('total_steps / end_lr need lr_schedule="cosine" or "poly"')
+        self.lr_schedule, self.total_steps, self.end_lr = lr_schedule, total_steps, float(end_lr)
+        self.lars = {"eta": float(lars_eta), "eps": float(lars_eps), "clip": bool(lars_clip)} if lars else None
+        self.label_smoothing = float(label_smoothing)
+        # the captured step takes the learning rate (and the trust ratios) from the device: FusedSGDTables.step_ex
+        self._recipe = bool(lars) or lr_schedule != "constant"
+        self._last_lr = self._last_ratios = None
+        self._lr_on_device = False
+        self._sgd_tab, self._sgd_pos = None, []
         self.device = torch.device(device)
         self.batch, self.crop, self.seed = batch, crop, seed
         self.accum = max(1, int(accum_steps))
@@ -103,8 +133,71 @@ class ResNetTrainer:
         if self._bn_count is not None and self.model.training:
             self._bn_count.add_(1)
 
+    def _schedule(self) -> tuple:
+        return (self.lr_schedule, self.base_lr, self.warmup, self.total_steps, self.end_lr)
+
     def _lr(self) -> float:
-        return self.base_lr * min(1.0, (self.step_idx + 1) / max(1, self.warmup))
+        from ..ops.sgd import scheduled_lr
+
+        return scheduled_lr(*self._schedule(), self.step_idx)
+
+    def _sgd_lists(self):
+        """The optimizer's tensors in param-group order (the order of the fused tables): parameters, their weight
+        decays and LARS adapt flags (more than one dimension), and each one's index in model.parameters()."""
+        pos = {id(p): i for i, p in enumerate(self.model.parameters())}
+        params, wds = [], []
+        for g in self.opt.param_groups:
+            for p in g["params"]:
+                if p.requires_grad:
+                    params.append(p)
+                    wds.append(g["weight_decay"])
+        return params, wds, [p.ndim > 1 for p in params], [pos[id(p)] for p in params]
+
+    def _momentum_buffer(self, p: torch.Tensor) -> torch.Tensor:
+        st = self.opt.state[p]
+        if st.get("momentum_buffer") is None:  # (zero: with dampening 0 the first update equals torch.optim.SGD's)
+            st["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        return st["momentum_buffer"]
+
+    @torch.no_grad()
+    def _lars_update(self, lr) -> None:
+        """The LARS update from torch ops (mifx.ops.sgd.lars_reference_) on the optimizer's own momentum buffers:
+        the eager and CPU steps, and the captured step without the fused tables (`lr` a device tensor there)."""
+        from ..ops.sgd import lars_reference_
+
+        params, wds, adapt, pos = self._sgd_lists()
+        keep = [i for i, p in enumerate(params) if p.grad is not None]
+        g0 = self.opt.param_groups[0]
+        ratios = lars_reference_([params[i] for i in keep], [params[i].grad for i in keep],
+                                 [self._momentum_buffer(params[i]) for i in keep], [wds[i] for i in keep],
+                                 [adapt[i] for i in keep], self.lars["eta"], self.lars["eps"], self.lars["clip"],
+                                 g0["momentum"], g0["dampening"], g0["nesterov"], lr)
+        by_pos = dict(zip((pos[i] for i in keep), ratios))
+        one = torch.ones((), dtype=torch.float32, device=self.device)
+        n = sum(1 for _ in self.model.parameters())
+        self._last_ratios = torch.stack([by_pos.get(i, one).float() for i in range(n)])
+
+    def last_lr(self) -> float | None:
+        """The learning rate of the last step (read back from the device after a captured step that evaluates the
+        schedule there); None before the first step."""
+        if self._lr_on_device and self._sgd_tab is not None and self._last_lr is None:
+            return self._sgd_tab.last_lr()
+        return self._last_lr
+
+    def last_trust_ratios(self) -> torch.Tensor | None:
+        """fp32 trust ratios of the last step, one per tensor of model.parameters() (1 for the tensors LARS leaves
+        alone); None without lars or before the first step."""
+        if self.lars is None:
+            return None
+        if self._last_ratios is not None:
+            return self._last_ratios.detach().cpu()
+        if self._lr_on_device and self._sgd_tab is not None:
+            r = self._sgd_tab.last_trust_ratios()
+            if r is not None:
+                out = torch.ones(sum(1 for _ in self.model.parameters()), dtype=torch.float32)
+                out[torch.tensor(self._sgd_pos)] = r
+                return out
+        return None
 
     def _step_indices(self) -> torch.Tensor:
         """The global sample of this step ([world * accum * batch], from (seed, step) on a host generator: the same
@@ -140,14 +233,18 @@ class ResNetTrainer:
                                     self.mean, self.std, torch.bfloat16 if self.amp else torch.float32)
             y = self.labels[idx]
             with torch.autocast(self.device.type, dtype=torch.bfloat16, enabled=self.amp):
-                loss = F.cross_entropy(self.model(x).float(), y) / self.accum
+                loss = F.cross_entropy(self.model(x).float(), y, label_smoothing=self.label_smoothing) / self.accum
             self._count_forward()
             last = m == self.accum - 1
             self._backward(loss, last)
             total = total + loss.detach()
         if self.dp is not None:
             self.dp.finish()
-        self.opt.step()
+        if self.lars is not None:
+            self._lars_update(self._lr())
+        else:
+            self.opt.step()
+        self._last_lr = self._lr()
         self.step_idx += 1
         return total
 
@@ -184,7 +281,11 @@ class ResNetTrainer:
             self._capture()
         self._idx_dev.copy_(glob)
         self._step_dev.fill_(self.step_idx)
-        self._neg_lr.fill_(-self._lr())
+        if self._lr_on_device:  # the graph evaluates the schedule from _step_dev: no host write of the learning rate
+            self._last_lr = self._last_ratios = None  # (read back from the tables on demand)
+        else:
+            self._neg_lr.fill_(-self._lr())
+            self._last_lr = self._lr()
         for pg in self.opt.param_groups:
             pg["lr"] = self._lr()  # (kept current for checkpoints / eager fallbacks)
         self._gA.replay()
@@ -224,7 +325,8 @@ class ResNetTrainer:
                                         step_dev=self._step_dev)
                 y = self.labels[idx]
                 with torch.autocast(self.device.type, dtype=torch.bfloat16, enabled=self.amp):
-                    loss = F.cross_entropy(self.model(x).float(), y) / self.accum
+                    loss = F.cross_entropy(self.model(x).float(), y,
+                                           label_smoothing=self.label_smoothing) / self.accum
                 self._count_forward()
                 # the same backward as the eager steps; the exchange captures with it only on the ipc path (RCCL:
                 # the whole graph runs under no_sync and the bucket all-reduces run eagerly between the graphs)
@@ -249,16 +351,11 @@ class ResNetTrainer:
 
         if not _lib.available("sgd"):
             return
-        params, bufs, wds = [], [], []
-        for g in groups:
-            for p in g["params"]:
-                if not p.requires_grad:
-                    continue
-                params.append(p)
-                bufs.append(self.opt.state[p]["momentum_buffer"])
-                wds.append(g["weight_decay"])
+        params, wds, adapt, self._sgd_pos = self._sgd_lists()
+        bufs = [self.opt.state[p]["momentum_buffer"] for p in params]
+        lars = dict(self.lars, adapt=adapt) if self.lars is not None else None
         try:
-            self._sgd_tab = FusedSGDTables(params, bufs, wds)
+            self._sgd_tab = FusedSGDTables(params, bufs, wds, lars=lars)
         except ValueError:
             self._sgd_tab = None
 
@@ -272,9 +369,16 @@ class ResNetTrainer:
             if tab.grads_ok(grads):
                 tab.set_grads(grads)
                 g0 = self.opt.param_groups[0]
-                tab.step(self._neg_lr, g0["momentum"], g0["dampening"], g0["nesterov"])
+                if self._recipe:  # schedule (and trust ratios) evaluated on the device from the step counter
+                    tab.step_ex(self._step_dev, self._schedule(), g0["momentum"], g0["dampening"], g0["nesterov"])
+                    self._lr_on_device = True
+                else:
+                    tab.step(self._neg_lr, g0["momentum"], g0["dampening"], g0["nesterov"])
                 return
             self._sgd_tab = None  # a gradient missing or laid out unlike its parameter: the foreach update
+        if self.lars is not None:  # the same update from torch ops, learning rate filled in by the host
+            self._lars_update(-self._neg_lr)
+            return
         for group in self.opt.param_groups:
             params = [p for p in group["params"] if p.grad is not None]
             if not params:
@@ -298,6 +402,7 @@ class ResNetTrainer:
                if p.requires_grad):
             raise RuntimeError("capture needs the SGD momentum buffers of an eager step first")
         self._sgd_prepare()
+        self._lr_on_device = False  # (set by _sgd_captured when the fused tables take the recipe)
         torch.cuda.synchronize(self.device)
         self._gA = torch.cuda.CUDAGraph()
         one = self.dp is None or self.dp.exchange == "ipc"
@@ -338,6 +443,7 @@ class ResNetTrainer:
         self.step_idx = int(sd["step"][0])
         self._gA = self._gB = None  # the graphs captured the old momentum buffers: re-capture after warm steps
         self._eager_done = 0
+        self._lr_on_device = False  # (the schedule depends on the step alone: a resumed run continues it)
 
     def save_checkpoint(self, model_dir: str, keep: int = 1) -> str:
         import glob as _glob
@@ -394,6 +500,14 @@ def main(argv=None):
                          "are not run-to-run reproducible, measured in round 2, profiles/archive/resnet_determinism_r2s3.txt). Diagnostic only: "
                          "measured 13.7 s/step at B=256 on one MI355X vs 26.5 ms with the default solvers")
     ap.add_argument("--no-graph", action="store_true", help="eager steps instead of the captured hipGraph step")
+    ap.add_argument("--lr", type=float, default=0.1, help="base learning rate (after 10 warmup steps)")
+    ap.add_argument("--lr-schedule", choices=("constant", "cosine", "poly"), default="constant")
+    ap.add_argument("--total-steps", type=int, default=None, help="cosine / poly: the step at which --end-lr is reached")
+    ap.add_argument("--end-lr", type=float, default=0.0)
+    ap.add_argument("--lars", action="store_true", help="layer-wise trust ratios (tensors with more than one dimension)")
+    ap.add_argument("--lars-eta", type=float, default=0.001)
+    ap.add_argument("--lars-clip", action="store_true", help="LARC clipping: min(ratio / lr, 1)")
+    ap.add_argument("--label-smoothing", type=float, default=0.0)
     a = ap.parse_args(argv)
     if a.deterministic:
         torch.backends.cudnn.deterministic = True
@@ -412,8 +526,9 @@ def main(argv=None):
         torch.distributed.init_process_group("nccl" if dev.type == "cuda" else "gloo",
                                              init_method=f"tcp://127.0.0.1:{port}", rank=0, world_size=1)
     pg = torch.distributed.group.WORLD if env.world_size > 1 or force else None
-    tr = ResNetTrainer(a.batch, dev, imgs, labels, process_group=pg, warmup_steps=10, graph=not a.no_graph,
-                       force_dp=force)
+    tr = ResNetTrainer(a.batch, dev, imgs, labels, process_group=pg, lr=a.lr, warmup_steps=10, graph=not a.no_graph,
+                       force_dp=force, lr_schedule=a.lr_schedule, total_steps=a.total_steps, end_lr=a.end_lr,
+                       lars=a.lars, lars_eta=a.lars_eta, lars_clip=a.lars_clip, label_smoothing=a.label_smoothing)
     for i in range(a.warmup):  # first steps include MIOpen solver search/compile: report progress
         t1 = time.perf_counter()
         with heartbeat("resnet warmup"):
@@ -444,6 +559,9 @@ def main(argv=None):
                           "dp_exchange": tr.dp.exchange if tr.dp is not None else "none",
                           "graphs_per_step": 0 if not tr.use_graph else (2 if tr._gB is not None else 1),
                           "sgd": "fused" if getattr(tr, "_sgd_tab", None) is not None else "foreach",
+                          "lr_schedule": tr.lr_schedule, "lars": tr.lars is not None,
+                          "label_smoothing": tr.label_smoothing, "last_lr": tr.last_lr(),
+                          "lr_on_device": tr._lr_on_device,
                           "deterministic": bool(torch.backends.cudnn.deterministic)}), flush=True)
     mdist.shutdown()
 
