@@ -104,16 +104,22 @@ __device__ __forceinline__ void scores(const bf16* Ks, const v8bf (&qf)[2], v4f 
   }
 }
 
-// P^T (probabilities, before dropout) from the scores, the key bias and the per-query logsumexp
+// the backward's probability from the saved statistics of its row (the note at mifx_attn_fwd): sm = biased score minus
+// the row maximum, l2 = log2 of the row sum. exp(sm) / l as one fma and one v_exp_f32 (__expf is a multiply and the
+// same instruction)
+constexpr float kLog2e = 1.4426950408889634f;
+__device__ __forceinline__ float prob(float sm, float l2) { return __builtin_amdgcn_exp2f(fmaf(sm, kLog2e, -l2)); }
+
+// P^T (probabilities, before dropout) from the scores, the key bias and the per-query softmax statistics
 template <int S>
-__device__ __forceinline__ void probs(v4f (&p)[S / 16], float scale, const float* kb, float lse, int h) {
+__device__ __forceinline__ void probs(v4f (&p)[S / 16], float scale, const float* kb, float m, float l2, int h) {
 #pragma unroll
   for (int kt = 0; kt < S / 16; ++kt) {
     const float4 b = kb ? *(const float4*)(kb + 16 * kt + 4 * h) : make_float4(0.f, 0.f, 0.f, 0.f);
-    p[kt][0] = __expf(p[kt][0] * scale + b.x - lse);
-    p[kt][1] = __expf(p[kt][1] * scale + b.y - lse);
-    p[kt][2] = __expf(p[kt][2] * scale + b.z - lse);
-    p[kt][3] = __expf(p[kt][3] * scale + b.w - lse);
+    p[kt][0] = prob(p[kt][0] * scale + b.x - m, l2);
+    p[kt][1] = prob(p[kt][1] * scale + b.y - m, l2);
+    p[kt][2] = prob(p[kt][2] * scale + b.z - m, l2);
+    p[kt][3] = prob(p[kt][3] * scale + b.w - m, l2);
   }
 }
 
@@ -198,7 +204,11 @@ __global__ __launch_bounds__(64 * (S / 16) / QS) void attn_fwd(const bf16* __res
     }
     *(v4bf*)(out + ((size_t)b * S + qi) * H * D + (size_t)hh * D + 16 * dt + 4 * h) = pack4(o);
   }
-  if (h == 0) lse_out[((size_t)b * H + hh) * S + qi] = m + __logf(l);
+  if (h == 0) {
+    float* st = lse_out + ((size_t)b * H + hh) * S + qi;
+    st[0] = m;
+    st[(size_t)(gridDim.x / QS) * S] = __log2f(l);
+  }
 }
 
 template <int S>
@@ -236,7 +246,7 @@ __global__ __launch_bounds__(64 * (S / 16)) void attn_bwd(const bf16* __restrict
     di += __shfl_xor(di, 16);
     di += __shfl_xor(di, 32);
   }
-  const float lq = lse[((size_t)b * H + hh) * S + qi];
+  const float mq = lse[((size_t)b * H + hh) * S + qi], lq = lse[((size_t)gridDim.x + (size_t)b * H + hh) * S + qi];
   __syncthreads();
 
   v8bf qf[2], dof[2];
@@ -247,7 +257,7 @@ __global__ __launch_bounds__(64 * (S / 16)) void attn_bwd(const bf16* __restrict
   }
   v4f pp[KT];
   scores<S>(Ks, qf, pp, r, h);
-  probs<S>(pp, scale, kbias ? kbias + (size_t)b * S : nullptr, lq, h);
+  probs<S>(pp, scale, kbias ? kbias + (size_t)b * S : nullptr, mq, lq, h);
   // dP_d^T = V dO^T
   v4f dp_[KT];
 #pragma unroll
@@ -436,7 +446,10 @@ __global__ __launch_bounds__(LNT) void attn_fwd_long(const bf16* __restrict__ qk
 #pragma unroll
   for (int dt = 0; dt < D / 16; ++dt)
     *(v4bf*)(out + ((size_t)b * S + qi) * H * D + (size_t)hh * D + 16 * dt + 4 * h) = pack4(o[dt] * inv);
-  if (h == 0) lse_out[(size_t)bh * S + qi] = m + __logf(l);
+  if (h == 0) {
+    lse_out[(size_t)bh * S + qi] = m;
+    lse_out[((size_t)(gridDim.x / nqb) + bh) * S + qi] = __log2f(l);
+  }
 }
 
 __global__ __launch_bounds__(LNT) void attn_bwd_dq_long(const bf16* __restrict__ qkv, const float* __restrict__ kbias,
@@ -457,7 +470,7 @@ __global__ __launch_bounds__(LNT) void attn_bwd_dq_long(const bf16* __restrict__
   const bool live = qb * LQB + 16 * w < S;
   const int qi = qb * LQB + 16 * w + r;
   v8bf qf[2], dof[2];
-  float di = 0.f, lq = 0.f;
+  float di = 0.f, mq = 0.f, lq = 0.f;
   if (live) {
     const bf16* pdo = dout + ((size_t)b * S + qi) * otok + (size_t)hh * D;
 #pragma unroll
@@ -472,7 +485,8 @@ __global__ __launch_bounds__(LNT) void attn_bwd_dq_long(const bf16* __restrict__
     di += __shfl_xor(di, 16);
     di += __shfl_xor(di, 32);
     if (h == 0) dsum[(size_t)bh * S + qi] = di;
-    lq = lse[(size_t)bh * S + qi];
+    mq = lse[(size_t)bh * S + qi];
+    lq = lse[((size_t)(gridDim.x / nqb) + bh) * S + qi];
   }
   __syncthreads();
   if (!live) return;
@@ -499,7 +513,7 @@ __global__ __launch_bounds__(LNT) void attn_bwd_dq_long(const bf16* __restrict__
       const uint32_t kbits = dp.thr ? mifx_rng::keep4(key, (row_base + c + 16 * kt + 4 * h) >> 2, dp.thr) : 0xf;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const float pe = __expf(sc[e] * scale + bv[e] - lq);
+        const float pe = prob(sc[e] * scale + bv[e] - mq, lq);
         const float dpv = (kbits >> e) & 1 ? dpd[e] * dsc : 0.f;
         ds[kt][e] = pe * (dpv - di) * scale;
       }
@@ -547,7 +561,8 @@ __global__ __launch_bounds__(LNT) void attn_bwd_dkv_long(const bf16* __restrict_
   __syncthreads();
   if (!live) return;
 
-  const float* lq = lse + (size_t)bh * S;
+  const float* mq = lse + (size_t)bh * S;
+  const float* lq = mq + (size_t)(gridDim.x / nkb) * S;
   const float* dd = dsum + (size_t)bh * S;
   const uint64_t key = dp.thr ? mifx_rng::drop_key(dp.rng, dp.site) : 0;
   const uint64_t mrow = ((uint64_t)b * Htot + h0 + hh) * S;
@@ -567,15 +582,16 @@ __global__ __launch_bounds__(LNT) void attn_bwd_dkv_long(const bf16* __restrict_
         dpd = mfma(ld8(dOs + (c + 16 * it + r) * LD + 32 * ks + 8 * h), vf[ks], dpd);
       }
       const int i0 = c + 16 * it + 4 * h;
+      const float4 M = *(const float4*)(mq + i0);
       const float4 L = *(const float4*)(lq + i0);
       const float4 Dq = *(const float4*)(dd + i0);
-      const float lv[4] = {L.x, L.y, L.z, L.w}, dv4[4] = {Dq.x, Dq.y, Dq.z, Dq.w};
+      const float mv[4] = {M.x, M.y, M.z, M.w}, lv[4] = {L.x, L.y, L.z, L.w}, dv4[4] = {Dq.x, Dq.y, Dq.z, Dq.w};
       uint32_t nib = 0xf;
       if (dp.thr) nib = mifx_rng::keep4(key, ((mrow + i0 + p) * S + (kj & ~3)) >> 2, dp.thr);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const bool kept = dp.thr ? ((__shfl(nib, (lane & ~3) | e) >> p) & 1) : true;
-        const float pe = __expf(sc[e] * scale + bj - lv[e]);
+        const float pe = prob(sc[e] * scale + bj - mv[e], lv[e]);
         pd[it][e] = kept ? pe * dsc : 0.f;
         ds[it][e] = pe * ((kept ? dpd[e] * dsc : 0.f) - dv4[e]) * scale;
       }
@@ -619,7 +635,11 @@ constexpr int bwd_lds() {
 extern "C" {
 
 // qkv [B, S, 3, H, 64] bf16 (contiguous), kbias [B, S] fp32 additive key bias or null, out [B, S, H, 64] bf16,
-// lse [B, H, S] fp32. p: attention-probability dropout (rng: device int64 [seed, counter]; site per layer).
+// lse [2, B, H, S] fp32: the softmax statistics of each query row, its maximum m of the biased scores and log2(l) of
+// its sum l of exp(s - m), kept apart. The backward recomputes P = exp2((s - m) log2(e) - log2 l). In one float,
+// m + log l, a row whose keys are all masked (m = -1e30) loses log l to rounding and its P comes back as 1 instead
+// of 1 / S. The bias may be any finite value down to the -1e30 of a padding key (the running maximum starts at
+// -3.0e38). p: attention-probability dropout (rng: device int64 [seed, counter]; site per layer).
 // h0 / Htot: this rank's first global head and the model's head count (dropout indexing only).
 int mifx_attn_fwd(const void* qkv, const float* kbias, int B, int S, int H, int h0, int Htot, float scale, float p,
                   const int64_t* rng, int site, void* out, float* lse, hipStream_t st) {
@@ -661,7 +681,8 @@ int mifx_attn_fwd(const void* qkv, const float* kbias, int B, int S, int H, int 
   return (int)hipGetLastError();
 }
 
-// dqkv [B, S, 3, H, 64] bf16 (every element written); dsum: fp32 [B, H, S] workspace for S > 128 (else unused)
+// lse: the forward's statistics [2, B, H, S]. dqkv [B, S, 3, H, 64] bf16 (every element written); dsum: fp32
+// [B, H, S] workspace for S > 128 (else unused)
 int mifx_attn_bwd(const void* qkv, const float* kbias, const void* out, const void* dout, const float* lse, int B,
                   int S, int H, int h0, int Htot, float scale, float p, const int64_t* rng, int site, void* dqkv,
                   float* dsum, hipStream_t st) {

@@ -421,7 +421,8 @@ class _Attention(torch.autograd.Function):
         B, S, _, H, Dh = qkv.shape
         qkv = qkv.contiguous()
         out = torch.empty(B, S, H, Dh, device=qkv.device, dtype=torch.bfloat16)
-        lse = torch.empty(B, H, S, device=qkv.device, dtype=torch.float32)
+        # softmax statistics per query row, kept apart: [0] the maximum of the biased scores, [1] log2 of the row sum
+        lse = torch.empty(2, B, H, S, device=qkv.device, dtype=torch.float32)
         kb = None if kbias is None else kbias.float().contiguous()
         check(_attn_fns()["fwd"](ptr(qkv), ptr(kb), B, S, H, int(h0), int(htot), float(scale), float(p),
                                  ptr(rng if p > 0 else None), int(site), ptr(out), ptr(lse), stream_handle(qkv.device)),
@@ -466,7 +467,9 @@ def attention(qkv: torch.Tensor, kbias, scale: float, p: float = 0.0, rng=None, 
               htot: int | None = None) -> torch.Tensor:
     """Multi-head self-attention over the fused projection output qkv [B, S, 3, H, Dh] -> [B, S, H, Dh].
     GPU (bf16, Dh 64, S 64 / 128, or a multiple of 64 up to 512): csrc/attention.hip fwd/bwd; elsewhere the
-    reference composition (same mask)."""
+    reference composition (same mask).
+    kbias: finite additive values, down to the -1e30 of a padding key (a sequence may be masked entirely); -inf and
+    finfo.min are outside the contract (the kernels start the running maximum at -3.0e38)."""
     if p > 0 and rng is None:
         raise ValueError("attention dropout p > 0 needs an rng state tensor [seed, counter]")
     htot = qkv.shape[3] if htot is None else htot
