@@ -18,7 +18,7 @@
 //    ds_read_b64_tr_b16 at the permuted rows that match (rows 32s + 16(h%2) + 4(h/2) + {0..3, 8..11}).
 //    Layer 5 (one logit row) is a rank-1 product done on the VALU.
 //  * Weight gradients dW_l^T = dZ_l^T A_{l-1} reduce over examples, so they need the transpose: per layer the
-//    128 x N_l gradient (natural order) and the 128 x K_l activation (C order) are staged in LDS once and read
+//    T x N_l gradient (natural order) and the T x K_l activation (C order) are staged in LDS once and read
 //    back with ds_read_b64_tr_b16; every wave owns a fixed set of 16x16 dW tiles and keeps their fp32
 //    accumulators in registers across ALL iterations (MFMA K-accumulation == batch reduction), so the
 //    workgroup writes one gradient slab at the end, in the same tile-native layout as wd_fused.
@@ -69,7 +69,7 @@ constexpr int K3 = 96, N3 = 64;
 constexpr int K4 = 64, N4 = 64;
 constexpr int K5 = 64, N5 = 16;
 
-// weight image (bf16, LDS layout == global image layout): W_l^T [N_l][K_l + WPAD], columns in C order
+// weight image (bf16, global layout; the LDS placement below): W_l^T [N_l][K_l + WPAD], columns in C order
 constexpr int LW1 = 0;
 constexpr int LW2 = LW1 + N1 * (K1 + WPAD);
 constexpr int LW3 = LW2 + N2 * (K2 + WPAD);
@@ -79,27 +79,48 @@ constexpr int LWEND = LW5 + N5 * (K5 + WPAD);  // 33536
 // dW staging: dZ_l [T][N_l + PAD] (natural order) followed by A_{l-1} [T][K_l + PAD] (C order)
 constexpr int stage_len(int K, int N) { return T * (N + PAD) + T * (K + PAD); }
 constexpr int cmax(int a, int b) { return a > b ? a : b; }
-// LDS left for staging next to the weight image and the wide histogram. A layer whose full staging (T rows of dZ
-// and A) does not fit is staged and reduced in two passes of T / 2 rows -- column block 0 of every wave, then
-// block 1 (T = 256: layers 1-3; never at T <= 128)
 constexpr int WIDE_PAD = 2176;  // the wide (linear) weights / histogram, padded
-constexpr int LDS_FIXED_B = LWEND * 2 + WIDE_PAD * 4 + 64 * 4;
-constexpr int STAGE_MAX = ((163840 - LDS_FIXED_B) / 2) & ~7;
-constexpr bool split_stage(int K, int N) { return stage_len(K, N) > STAGE_MAX; }
-constexpr int stage_eff(int K, int N) { return split_stage(K, N) ? stage_len(K, N) / 2 : stage_len(K, N); }
-constexpr int LSLEN = cmax(cmax(cmax(stage_eff(K1, N1), stage_eff(K2, N2)), cmax(stage_eff(K3, N3), stage_eff(K4, N4))),
-                           stage_eff(K5, N5));
-static_assert(T == 256 || !(split_stage(K1, N1) || split_stage(K2, N2) || split_stage(K3, N3) ||
-                            split_stage(K4, N4) || split_stage(K5, N5)), "split staging is the T = 256 shape's");
-static_assert(!split_stage(K4, N4) && !split_stage(K5, N5), "layers 4-5 stage whole");
-constexpr int LS = LWEND;
-constexpr int LSEND = LS + LSLEN;
+// ---- LDS placement. T <= 128: the weight image sits in LDS as in global memory (W1..W5 from 0) and every layer
+// stages at LS, right after it. T = 256 (one iteration per workgroup: a layer's weights are dead once the backward
+// has passed it, W1 after the forward) places the image ROTATED, W2 | W3 | W4 | W5 | gap | W1, and starts each
+// layer's staging where the dead weights begin, so that every layer's full T-row staging fits and is written once:
+//   layers 5, 4: SB5 = SB4 = PWEND -- past the whole image: W5 and W4 are read beside these stagings, and other
+//            waves may still be in the forward (W1..W5) when layer 5's begins;
+//   layer 3: SB3 = PW4 -- overwrites W4, W5, W1: every wave read them last before layer 4's first barrier;
+//            must not touch W3 (read by the activation gradient that runs beside this staging);
+//   layer 2: SB2 = PW3 -- overwrites W3 (last read before layer 3's first barrier); must not touch W2;
+//   layer 1: SB1 = PW3 -- no weights are read any more (W2 stays untouched anyway).
+// A stage also overwrites the previous layer's stage: its dW reads end before that layer's second barrier.
+// The global image layout (LW1..LWEND: models.wide_deep.chain_image, the optimizer's image offsets) is the same
+// for every T; only the prologue's LDS destinations differ (img_lds).
+constexpr bool ROT = T == 256;
+constexpr int DMA_GAP = 256;  // the last LDS-DMA wave-chunk runs this far past the image end (see the prologue)
+constexpr int PW2 = ROT ? 0 : LW2;
+constexpr int PW3 = PW2 + (LW3 - LW2);
+constexpr int PW4 = PW3 + (LW4 - LW3);
+constexpr int PW5 = PW4 + (LW5 - LW4);
+constexpr int PW1 = ROT ? PW5 + (LWEND - LW5) + DMA_GAP : LW1;
+constexpr int PWEND = ROT ? PW1 + (LW2 - LW1) : LWEND;
+constexpr int LS = PWEND;
+constexpr int SB4 = LS, SB3 = ROT ? PW4 : LS, SB2 = ROT ? PW3 : LS, SB1 = ROT ? PW3 : LS, SB5 = LS;
+constexpr int LSEND = cmax(cmax(cmax(SB1 + stage_len(K1, N1), SB2 + stage_len(K2, N2)),
+                                cmax(SB3 + stage_len(K3, N3), SB4 + stage_len(K4, N4))),
+                           SB5 + stage_len(K5, N5));
+static_assert(!ROT || (LW1 == 0 && LW2 % 512 == 0 && (512 - LWEND % 512) % 512 <= DMA_GAP),
+              "rotated placement: W1 is whole LDS-DMA wave-chunks, the last chunk's overrun ends in the gap");
+static_assert(SB5 >= PWEND && SB4 >= PWEND, "layers 5 and 4 stage beside live weights of later layers");
+static_assert(SB3 >= PW3 + (LW4 - LW3) && SB2 >= PW2 + (LW3 - LW2), "a layer's stage keeps off its own weights");
+static_assert(SB1 + stage_len(K1, N1) <= LSEND && SB2 + stage_len(K2, N2) <= LSEND &&
+              SB3 + stage_len(K3, N3) <= LSEND && SB4 + stage_len(K4, N4) <= LSEND &&
+              SB5 + stage_len(K5, N5) <= LSEND, "every stage ends below the wide histogram");
 constexpr int NWIDE = 2128;
 constexpr int WIDE_BIAS = 2127;
 constexpr int NTILE = 108;
+// the wide histogram and `red` follow at LSEND, the end of LDS
 constexpr int LDS_BYTES = LSEND * 2 + WIDE_PAD * 4 + 64 * 4;
 static_assert(LDS_BYTES <= 163840, "LDS budget");
-static_assert((LSEND * 2) % 16 == 0 && (LS * 2) % 16 == 0, "16-B aligned regions");
+static_assert((LSEND * 2) % 16 == 0 && (LS * 2) % 16 == 0 && (SB1 * 2) % 16 == 0 && (SB2 * 2) % 16 == 0 &&
+              (SB3 * 2) % 16 == 0, "16-B aligned regions");
 
 constexpr int TB1 = 0, TB2 = TB1 + (N1 / 16) * (K1 / 16), TB3 = TB2 + (N2 / 16) * (K2 / 16),
               TB4 = TB3 + (N3 / 16) * (K3 / 16), TB5 = TB4 + (N4 / 16) * (K4 / 16);
@@ -308,63 +329,19 @@ __device__ __forceinline__ void stage(uint16_t* S, const v4bf (&dz)[TBN][N / 16]
   }
 }
 
-// ---- split staging (T = 256, layers 1-3): pass `tb` stages column block tb of every wave (rows 16 w + sperm16(r) of
-// a T / 2-row image), the activation gradient waits as unmasked bf16 tiles until its pass's A rows give the mask
-template <int K, int N, int TBN>
-__device__ __forceinline__ void stage_half(uint16_t* S, const v4bf (&dz)[TBN][N / 16], const v8bf (&a)[TBN][K / 32],
-                                           int w, int r, int h, int tb) {
-  constexpr int R = T / 2;
-  uint16_t* SZ = S;
-  uint16_t* SA = S + R * (N + PAD);
-  const int row = 16 * w + sperm16(r);
-#pragma unroll
-  for (int t = 0; t < TBN; ++t) {
-    if (t != tb) continue;
-#pragma unroll
-    for (int m = 0; m < N / 32; ++m) *(v8bf*)(SZ + row * (N + PAD) + 32 * m + 8 * h) = cat_bf(dz[t][2 * m], dz[t][2 * m + 1]);
-#pragma unroll
-    for (int s2 = 0; s2 < K / 32; ++s2) *(v8bf*)(SA + row * (K + PAD) + 32 * s2 + 8 * h) = a[t][s2];
-  }
-}
-template <int K, int TBN>
-__device__ __forceinline__ void to_bf_tiles(const v4f (&g)[TBN][K / 16], unsigned int (&gb)[TBN][K / 16][2]) {
-#pragma unroll
-  for (int tb = 0; tb < TBN; ++tb)
-#pragma unroll
-    for (int kt = 0; kt < K / 16; ++kt) {
-      gb[tb][kt][0] = cvt_pk(g[tb][kt][0], g[tb][kt][1]);
-      gb[tb][kt][1] = cvt_pk(g[tb][kt][2], g[tb][kt][3]);
-    }
-}
-template <int K, int TBN>
-__device__ __forceinline__ void mask_half(const unsigned int (&gb)[TBN][K / 16][2], const uint16_t* SA, int w, int r,
-                                          int h, v4bf (&dz)[TBN][K / 16], int tb) {
-  const int row = 16 * w + sperm16(r);
-#pragma unroll
-  for (int t = 0; t < TBN; ++t) {
-    if (t != tb) continue;
-#pragma unroll
-    for (int kt = 0; kt < K / 16; ++kt) {
-      const uint2 m = *(const uint2*)(SA + row * (K + PAD) + 16 * kt + 4 * h);
-      const unsigned int u[2] = {mask_pk(gb[t][kt][0], m.x), mask_pk(gb[t][kt][1], m.y)};
-      dz[t][kt] = __builtin_bit_cast(v4bf, u);
-    }
-  }
-}
-
 // ---- weight gradient: the wave's NTW x KTW tiles (nt = nt0 + i ntS, kt = kt0 + j ktS) accumulate
-// dW^T[n][k] += sum_t dZ[t][n] A[t][k] over the T staged rows (4 k-steps of 32 examples)
-template <int K, int N, int NTW, int KTW, int ROWS = T>
+// dW^T[n][k] += sum_t dZ[t][n] A[t][k] over the T staged rows (k-steps of 32 examples)
+template <int K, int N, int NTW, int KTW>
 __device__ __forceinline__ void dw_phase(v4f (&acc)[NTW * KTW], const uint16_t* S, int nt0, int ntS, int kt0, int ktS,
                                          int r, int h) {
   const uint16_t* SZ = S;
-  const uint16_t* SA = S + ROWS * (N + PAD);
+  const uint16_t* SA = S + T * (N + PAD);
   const int q = r >> 2, p = r & 3;
   // example rows 32 ts + 8 h + q (first read) and + 4 (second): inside the 16-row block 16 (h >> 1) they are
   // rows 8 (h & 1) + q and + 4, physical sperm16() = 8 (h & 1) + 2 q and + 1
   const int rl = 16 * (h >> 1) + 8 * (h & 1) + 2 * q;
 #pragma unroll
-  for (int ts = 0; ts < ROWS / 32; ++ts) {
+  for (int ts = 0; ts < T / 32; ++ts) {
     v8bf fa[NTW], fb[KTW];
 #pragma unroll
     for (int i = 0; i < NTW; ++i) {
@@ -534,7 +511,7 @@ __device__ void help_update(const TailArgs& ta, const float* __restrict__ slab, 
 // launch -- the ~750 KB of per-step optimizer traffic (slab, master weights, accumulators, column map) through one
 // CU's memory path outweighs the staging and launch it saves -- so the trainer keeps it opt-in.
 constexpr int LDS_BYTES_P = LDS_BYTES + WIDE_PAD * 4;
-static_assert(LDS_BYTES_P <= 163840, "LDS budget (persistent)");
+static_assert(ROT || LDS_BYTES_P <= 163840, "LDS budget (persistent: the T = 128 build)");
 
 // The optimizer over the lane's own dW columns (column ct[i] * 256 + 64 e + lane of the compact layout, which
 // this lane stored to the slab row earlier in the step -- same lane, same addresses, so program order suffices):
@@ -628,9 +605,14 @@ __global__ __launch_bounds__(64 * (T / (16 * TBN)), 1) void wdc_fused(const uint
   constexpr int NCH_STAGE = LWEND / 8, PER_STAGE = (NCH_STAGE + NTHR - 1) / NTHR;
   uint4 wst[REG_STAGE ? PER_STAGE : 1];
   (void)wst;
+  // LDS element of global image element e (a multiple of 8 here). Rotated placement (T = 256): W1 is whole
+  // wave-chunks of 512 elements, so the destination of a wave-chunk is wave-uniform
+  auto img_lds = [](int e) { return ROT ? (e < LW2 ? PW1 + e : PW2 + (e - LW2)) : e; };
+  static_assert(!(ROT && (PERSIST || TAIL)), "the persistent kernel and the in-kernel tail address the global layout");
   {  // stage the bf16 weight image (already in LDS layout) with direct-to-LDS loads: no VGPR round trip, no
      // ds_write transfer cycles. Wave w's lanes fill 16-byte chunks i * NTHR + 64 w + lane; the last wave's
-     // lanes past the image end re-read its last chunk and land in the staging area, written before any read.
+     // lanes past the image end re-read its last chunk and land in the staging area, written before any read
+     // (rotated placement: in the DMA_GAP elements between W5 and W1, which nothing reads).
 #ifndef WDC_DIAG_NOIMG
 #define WDC_DIAG_NOIMG 0
 #endif
@@ -642,7 +624,7 @@ __global__ __launch_bounds__(64 * (T / (16 * TBN)), 1) void wdc_fused(const uint
         const int c0 = i * NTHR + 64 * w;  // wave-uniform
         if (c0 < NCH_STAGE)
           __builtin_amdgcn_global_load_lds((const void*)(wimg + min(c0 + lane, NCH_STAGE - 1)),
-                                           (__attribute__((address_space(3))) void*)(lds + c0 * 8), 16, 0, 0);
+                                           (__attribute__((address_space(3))) void*)(lds + img_lds(c0 * 8)), 16, 0, 0);
       }
     } else if constexpr (REG_STAGE) {  // register staging: loads now, ds_write_b128 after the first record fetch
 #pragma unroll
@@ -734,7 +716,7 @@ __global__ __launch_bounds__(64 * (T / (16 * TBN)), 1) void wdc_fused(const uint
   if constexpr (REG_STAGE) {
 #pragma unroll
     for (int i = 0; i < PER_STAGE; ++i)
-      if (i * NTHR + tid < NCH_STAGE) *(uint4*)(lds + (i * NTHR + tid) * 8) = wst[i];
+      if (i * NTHR + tid < NCH_STAGE) *(uint4*)(lds + img_lds((i * NTHR + tid) * 8)) = wst[i];
   }
   if constexpr (!PERSIST) {  // weight image (LDS-DMA) and the first records landed; wgrad zeroed
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -797,25 +779,25 @@ __global__ __launch_bounds__(64 * (T / (16 * TBN)), 1) void wdc_fused(const uint
     v4f z5[TBN][1];
     {
       v4f acc[TBN][N1 / 16];
-      fwd<K1, N1, TBN>(lds + LW1, a0, acc, r, h);
+      fwd<K1, N1, TBN>(lds + PW1, a0, acc, r, h);
       relu_pack<N1, TBN>(acc, a1);
     }
     {
       v4f acc[TBN][N2 / 16];
-      fwd<K2, N2, TBN>(lds + LW2, a1, acc, r, h);
+      fwd<K2, N2, TBN>(lds + PW2, a1, acc, r, h);
       relu_pack<N2, TBN>(acc, a2);
     }
     {
       v4f acc[TBN][N3 / 16];
-      fwd<K3, N3, TBN>(lds + LW3, a2, acc, r, h);
+      fwd<K3, N3, TBN>(lds + PW3, a2, acc, r, h);
       relu_pack<N3, TBN>(acc, a3);
     }
     {
       v4f acc[TBN][N4 / 16];
-      fwd<K4, N4, TBN>(lds + LW4, a3, acc, r, h);
+      fwd<K4, N4, TBN>(lds + PW4, a3, acc, r, h);
       relu_pack<N4, TBN>(acc, a4);
     }
-    fwd<K5, N5, TBN>(lds + LW5, a4, z5, r, h);
+    fwd<K5, N5, TBN>(lds + PW5, a4, z5, r, h);
 
     STAMP(3);
     // ---- logit = deep (row 0 of the layer-5 tile: lane (r, h = 0)) + wide; loss and dlogit
@@ -847,8 +829,14 @@ __global__ __launch_bounds__(64 * (T / (16 * TBN)), 1) void wdc_fused(const uint
 
     // ---- layer 5: stage (dZ5, A4); dW5; dA4 = w5 (x) dl on the VALU, masked
     STAMP(4);
-    uint16_t* S = lds + LS;
-    block_sync_lds();  // previous iteration's dW1 reads of the staging area are done
+    uint16_t* const S5 = lds + SB5;
+    uint16_t* const S4 = lds + SB4;
+    uint16_t* const S3 = lds + SB3;
+    uint16_t* const S2 = lds + SB2;
+    uint16_t* const S1 = lds + SB1;
+    // previous iteration's dW1 reads of the staging area are done (rotated placement: every wave's forward reads of
+    // the weights are done -- layers 3 to 1 stage over them with only the layer barriers in between)
+    block_sync_lds();
     STAMP(5);
     if (own) {
       const int q = __float2int_rn(fminf(fmaxf(dl * qscale, -qmax), qmax));
@@ -867,10 +855,10 @@ __global__ __launch_bounds__(64 * (T / (16 * TBN)), 1) void wdc_fused(const uint
 #pragma unroll
       for (int tb = 0; tb < TBN; ++tb) {
         const int row = EPW * w + 16 * tb + sperm16(r);
-        *(v4bf*)(S + row * (N5 + PAD) + 4 * h) = d5[tb][0];
+        *(v4bf*)(S5 + row * (N5 + PAD) + 4 * h) = d5[tb][0];
 #pragma unroll
         for (int s = 0; s < K5 / 32; ++s)
-          *(v8bf*)(S + T * (N5 + PAD) + row * (K5 + PAD) + 32 * s + 8 * h) = a4[tb][s];
+          *(v8bf*)(S5 + T * (N5 + PAD) + row * (K5 + PAD) + 32 * s + 8 * h) = a4[tb][s];
       }
     }
     v4bf dz4[TBN][K5 / 16];
@@ -878,7 +866,7 @@ __global__ __launch_bounds__(64 * (T / (16 * TBN)), 1) void wdc_fused(const uint
       v4f g[TBN][K5 / 16];
 #pragma unroll
       for (int kt = 0; kt < K5 / 16; ++kt) {
-        const uint2 wv2 = *(const uint2*)(lds + LW5 + 16 * kt + 4 * h);  // W5 row 0 (the logit row; X(0) = 0)
+        const uint2 wv2 = *(const uint2*)(lds + PW5 + 16 * kt + 4 * h);  // W5 row 0 (the logit row; X(0) = 0)
         const float w5[4] = {__uint_as_float(wv2.x << 16), __uint_as_float(wv2.x & 0xffff0000u),
                              __uint_as_float(wv2.y << 16), __uint_as_float(wv2.y & 0xffff0000u)};
 #pragma unroll
@@ -886,120 +874,67 @@ __global__ __launch_bounds__(64 * (T / (16 * TBN)), 1) void wdc_fused(const uint
 #pragma unroll
           for (int e = 0; e < 4; ++e) g[tb][kt][e] = w5[e] * dlb[tb];
       }
-      mask_grad<K5, TBN>(g, S + T * (N5 + PAD), w, r, h, dz4);
+      mask_grad<K5, TBN>(g, S5 + T * (N5 + PAD), w, r, h, dz4);
     }
     block_sync_lds();
     STAMP(6);
-    if (l5) dw_phase<K5, N5, 1, 1>(acc5, S, 0, 0, w & 3, 0, r, h);
+    if (l5) dw_phase<K5, N5, 1, 1>(acc5, S5, 0, 0, w & 3, 0, r, h);
     WDC_EMIT(1, acc5, ct5);
     block_sync_lds();
 
     // ---- layer 4
     STAMP(7);
-    stage<K4, N4, TBN>(S, dz4, a3, w, r, h);
+    stage<K4, N4, TBN>(S4, dz4, a3, w, r, h);
     // the activation gradient needs only the weights, this wave's dZ and its own staged rows (the relu mask):
     // issued before the barrier so its MFMAs and weight reads overlap the other waves' staging
     v4bf dz3[TBN][K4 / 16];
     {
       v4f g[TBN][K4 / 16];
-      bwd_dA<K4, N4, TBN>(lds + LW4, dz4, g, r, h);
-      mask_grad<K4, TBN>(g, S + T * (N4 + PAD), w, r, h, dz3);
+      bwd_dA<K4, N4, TBN>(lds + PW4, dz4, g, r, h);
+      mask_grad<K4, TBN>(g, S4 + T * (N4 + PAD), w, r, h, dz3);
     }
     block_sync_lds();
     STAMP(8);
-    dw_phase<K4, N4, 1, O4K>(acc4, S, n4, 0, k4, 1, r, h);
+    dw_phase<K4, N4, 1, O4K>(acc4, S4, n4, 0, k4, 1, r, h);
     WDC_EMIT(O4K, acc4, ct4);
-    block_sync_lds();
+    block_sync_lds();  // (T = 256: W4, W5, W1 and layer 4's stage are dead from here)
 
     // ---- layer 3
     STAMP(9);
+    stage<K3, N3, TBN>(S3, dz3, a2, w, r, h);
     v4bf dz2[TBN][K3 / 16];
-    if constexpr (split_stage(K3, N3)) {  // two passes of T / 2 staged rows (column block 0, then 1)
-      unsigned int gb[TBN][K3 / 16][2];
-      {
-        stage_half<K3, N3, TBN>(S, dz3, a2, w, r, h, 0);
-        v4f g[TBN][K3 / 16];
-        bwd_dA<K3, N3, TBN>(lds + LW3, dz3, g, r, h);
-        to_bf_tiles<K3, TBN>(g, gb);
-      }
-      mask_half<K3, TBN>(gb, S + (T / 2) * (N3 + PAD), w, r, h, dz2, 0);
-      block_sync_lds();
-      dw_phase<K3, N3, 1, O3K, T / 2>(acc3, S, n3, 0, k3, 1, r, h);
-      block_sync_lds();
-      stage_half<K3, N3, TBN>(S, dz3, a2, w, r, h, 1);
-      mask_half<K3, TBN>(gb, S + (T / 2) * (N3 + PAD), w, r, h, dz2, 1);
-      block_sync_lds();
-      STAMP(10);
-      dw_phase<K3, N3, 1, O3K, T / 2>(acc3, S, n3, 0, k3, 1, r, h);
-    } else {
-      stage<K3, N3, TBN>(S, dz3, a2, w, r, h);
-      // the activation gradient needs only the weights, this wave's dZ and its own staged rows (the relu mask):
-      // issued before the barrier so its MFMAs and weight reads overlap the other waves' staging
-      {
-        v4f g[TBN][K3 / 16];
-        bwd_dA<K3, N3, TBN>(lds + LW3, dz3, g, r, h);
-        mask_grad<K3, TBN>(g, S + T * (N3 + PAD), w, r, h, dz2);
-      }
-      block_sync_lds();
-      STAMP(10);
-      dw_phase<K3, N3, 1, O3K>(acc3, S, n3, 0, k3, 1, r, h);
+    {  // (before the barrier, as in layer 4)
+      v4f g[TBN][K3 / 16];
+      bwd_dA<K3, N3, TBN>(lds + PW3, dz3, g, r, h);
+      mask_grad<K3, TBN>(g, S3 + T * (N3 + PAD), w, r, h, dz2);
     }
-    WDC_EMIT(O3K, acc3, ct3);
     block_sync_lds();
+    STAMP(10);
+    dw_phase<K3, N3, 1, O3K>(acc3, S3, n3, 0, k3, 1, r, h);
+    WDC_EMIT(O3K, acc3, ct3);
+    block_sync_lds();  // (T = 256: W3 and layer 3's stage are dead from here)
 
     // ---- layer 2
     STAMP(11);
+    stage<K2, N2, TBN>(S2, dz2, a1, w, r, h);
     v4bf dz1[TBN][K2 / 16];
-    if constexpr (split_stage(K2, N2)) {  // two passes of T / 2 staged rows (column block 0, then 1)
-      unsigned int gb[TBN][K2 / 16][2];
-      {
-        stage_half<K2, N2, TBN>(S, dz2, a1, w, r, h, 0);
-        v4f g[TBN][K2 / 16];
-        bwd_dA<K2, N2, TBN>(lds + LW2, dz2, g, r, h);
-        to_bf_tiles<K2, TBN>(g, gb);
-      }
-      mask_half<K2, TBN>(gb, S + (T / 2) * (N2 + PAD), w, r, h, dz1, 0);
-      block_sync_lds();
-      dw_phase<K2, N2, O2N, O2K, T / 2>(acc2, S, n2, 1, k2, 1, r, h);
-      block_sync_lds();
-      stage_half<K2, N2, TBN>(S, dz2, a1, w, r, h, 1);
-      mask_half<K2, TBN>(gb, S + (T / 2) * (N2 + PAD), w, r, h, dz1, 1);
-      block_sync_lds();
-      STAMP(12);
-      dw_phase<K2, N2, O2N, O2K, T / 2>(acc2, S, n2, 1, k2, 1, r, h);
-    } else {
-      stage<K2, N2, TBN>(S, dz2, a1, w, r, h);
-      // the activation gradient needs only the weights, this wave's dZ and its own staged rows (the relu mask):
-      // issued before the barrier so its MFMAs and weight reads overlap the other waves' staging
-      {
-        v4f g[TBN][K2 / 16];
-        bwd_dA<K2, N2, TBN>(lds + LW2, dz2, g, r, h);
-        mask_grad<K2, TBN>(g, S + T * (N2 + PAD), w, r, h, dz1);
-      }
-      block_sync_lds();
-      STAMP(12);
-      dw_phase<K2, N2, O2N, O2K>(acc2, S, n2, 1, k2, 1, r, h);
+    {  // (before the barrier, as in layer 4)
+      v4f g[TBN][K2 / 16];
+      bwd_dA<K2, N2, TBN>(lds + PW2, dz2, g, r, h);
+      mask_grad<K2, TBN>(g, S2 + T * (N2 + PAD), w, r, h, dz1);
     }
+    block_sync_lds();
+    STAMP(12);
+    dw_phase<K2, N2, O2N, O2K>(acc2, S2, n2, 1, k2, 1, r, h);
     WDC_EMIT(O2N * O2K, acc2, ct2);
     block_sync_lds();
 
-    // ---- layer 1
+    // ---- layer 1 (no activation gradient: the records are the input)
     STAMP(13);
-    if constexpr (split_stage(K1, N1)) {  // two passes of T / 2 staged rows
-      stage_half<K1, N1, TBN>(S, dz1, a0, w, r, h, 0);
-      block_sync_lds();
-      dw_phase<K1, N1, O1N, 1, T / 2>(acc1, S, n1, 1, 0, 0, r, h);
-      block_sync_lds();
-      stage_half<K1, N1, TBN>(S, dz1, a0, w, r, h, 1);
-      block_sync_lds();
-      STAMP(14);
-      dw_phase<K1, N1, O1N, 1, T / 2>(acc1, S, n1, 1, 0, 0, r, h);
-    } else {
-      stage<K1, N1, TBN>(S, dz1, a0, w, r, h);
-      block_sync_lds();
-      STAMP(14);
-      dw_phase<K1, N1, O1N, 1>(acc1, S, n1, 1, 0, 0, r, h);
-    }
+    stage<K1, N1, TBN>(S1, dz1, a0, w, r, h);
+    block_sync_lds();
+    STAMP(14);
+    dw_phase<K1, N1, O1N, 1>(acc1, S1, n1, 1, 0, 0, r, h);
     WDC_EMIT(O1N, acc1, ct1);
     if constexpr (PERSIST) {  // the whole DNN update of this lane's columns (see opt_tiles)
       constexpr int NA = O1N + O2N * O2K + O3K + O4K + 1;

@@ -53,7 +53,7 @@ def _fns64():
 @functools.lru_cache(maxsize=None)
 def _fns256():
     """csrc/wd_chain256.hip: 256 examples per iteration (8 waves x 32), ONE iteration per workgroup (grid * 256 >=
-    batch), layers 1-3 staged in two passes: the large-batch shape."""
+    batch), every layer's dW operands staged once over the LDS of dead weight layers: the large-batch shape."""
     lib = _lib.load("wd_chain256")
     return {
         "constants": sig(lib, "mifx_wdc_constants_t256", [VP, I32]),

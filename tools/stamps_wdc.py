@@ -32,6 +32,10 @@ from mifx.trainer.fused_wide_deep import FusedWideDeepTrainer  # noqa: E402
 NAMES = {1: "prologue", 2: "loop->iter", 3: "gather+fwd", 4: "loss", 5: "B0", 6: "stage5+B", 7: "dW5+dA4",
          8: "B+stage4+B", 9: "dW4+dA3", 10: "B+stage3+B", 11: "dW3+dA2", 12: "B+stage2+B", 13: "dW2+dA1",
          14: "B+stage1+B", 15: "dW1", 16: "->epi", 17: "epilogue"}
+# T = 256: every layer stages its T rows once (csrc/wd_chain.hip, the rotated LDS placement): a layer is stage +
+# activation gradient + barrier, then dW phase + barrier
+NAMES256 = {**NAMES, 8: "stg4+dA3+B", 9: "dW4+B", 10: "stg3+dA2+B", 11: "dW3+B", 12: "stg2+dA1+B", 13: "dW2+B",
+            14: "stage1+B"}
 CFGS = [(4, 40, False), (8, 65536, False), (8, 65536, True)] if "--quick" in sys.argv else \
     [(4, 40, False), (8, 40, False), (4, 65536, False), (8, 128, False), (8, 65536, False), (8, 65536, True)]
 for NW, batch, big in CFGS:
@@ -50,7 +54,8 @@ for NW, batch, big in CFGS:
     print(f"== batch {batch} grid {tr.grid} T {tr.tile}: cycles per phase (block 0; the 2nd iteration when there is one)")
     for i in range(1, 18):
         d = [st[w][i] - st[w][i - 1] for w in range(NW)]
-        print(f"  {NAMES[i]:>11}: " + " ".join(f"{x:8d}" for x in d))
+        nm = (NAMES256 if big else NAMES)[i]
+        print(f"  {nm:>12}: " + " ".join(f"{x:8d}" for x in d))
     print(f"  iteration (stamp 2 -> 15), wave 0: {st[0][15] - st[0][2]}; kernel (0 -> 17): {st[0][17] - st[0][0]}")
 
 # per-block global clock (100 MHz) of the last launch (the 8-wave B=65536 trainer above): dispatch stagger and
