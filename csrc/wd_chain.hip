@@ -1279,10 +1279,8 @@ int WDC_SYM(mifx_wdc_fused_help)(const void* data, long long n_data, long long b
   ta.wt_out = (uint16_t*)wimg;
   ta.step_slots = step_ctr;
   ta.helpers = helpers;
-  ta.hd = OptHyper{(int)hyper_dnn[0], hyper_dnn[1], hyper_dnn[2], hyper_dnn[3], hyper_dnn[4], hyper_dnn[5],
-                   hyper_dnn[6], hyper_dnn[7]};
-  ta.hw = OptHyper{(int)hyper_wide[0], hyper_wide[1], hyper_wide[2], hyper_wide[3], hyper_wide[4], hyper_wide[5],
-                   hyper_wide[6], hyper_wide[7]};
+  ta.hd = opt_hyper(hyper_dnn);
+  ta.hw = opt_hyper(hyper_wide);
   launch<true, 1, true>(dim3(1 + helpers), stream, data, n_data, batch, 0, step_ctr, wimg, wide, slab, slab_loss,
                         nullptr, grad_scale, tmap, stride, nullptr, MifxFeed{feed_stride, feed_offset, shuffle_key},
                         ta);
@@ -1326,10 +1324,8 @@ int mifx_wdc_fused_tail(const void* data, long long n_data, long long batch, lon
   ta.wt_out = (uint16_t*)wimg;
   ta.step_slots = step_ctr;
   ta.dbg = dbg;
-  ta.hd = OptHyper{(int)hyper_dnn[0], hyper_dnn[1], hyper_dnn[2], hyper_dnn[3], hyper_dnn[4], hyper_dnn[5],
-                   hyper_dnn[6], hyper_dnn[7]};
-  ta.hw = OptHyper{(int)hyper_wide[0], hyper_wide[1], hyper_wide[2], hyper_wide[3], hyper_wide[4], hyper_wide[5],
-                   hyper_wide[6], hyper_wide[7]};
+  ta.hd = opt_hyper(hyper_dnn);
+  ta.hw = opt_hyper(hyper_wide);
   launch<true, 1, true>(dim3(grid), stream, data, n_data, batch, 0, step_ctr, wimg, wide, slab, slab_loss, nullptr,
                         grad_scale, tmap, stride, xcd_of, MifxFeed{feed_stride, feed_offset, shuffle_key}, ta);
   return (int)hipGetLastError();
@@ -1357,10 +1353,8 @@ int mifx_wdc_persist(const void* data, long long n_data, long long batch, long l
   ta.wt_out = (uint16_t*)wimg;
   ta.step_slots = step_ctr;
   ta.nsteps = nsteps;
-  ta.hd = OptHyper{(int)hyper_dnn[0], hyper_dnn[1], hyper_dnn[2], hyper_dnn[3], hyper_dnn[4], hyper_dnn[5],
-                   hyper_dnn[6], hyper_dnn[7]};
-  ta.hw = OptHyper{(int)hyper_wide[0], hyper_wide[1], hyper_wide[2], hyper_wide[3], hyper_wide[4], hyper_wide[5],
-                   hyper_wide[6], hyper_wide[7]};
+  ta.hd = opt_hyper(hyper_dnn);
+  ta.hw = opt_hyper(hyper_wide);
   launch<true, 1, false, true>(dim3(1), stream, data, n_data, batch, 0, step_ctr, wimg, wide, slab, slab_loss,
                                nullptr, grad_scale, tmap, stride, nullptr, MifxFeed{feed_stride, feed_offset, shuffle_key},
                                ta);

@@ -1,4 +1,4 @@
-// Optimizer math shared by the W&D kernels (csrc/wide_deep.hip reductions + optimizers, csrc/wd_chain.hip's
+// Optimizer math shared by the W&D kernels (csrc/wd_tail.h reductions + optimizers, csrc/wd_chain.hip's
 // in-kernel tail): TF ApplyAdagrad / ApplyFtrl / Adam / SGD on one fp32 parameter (no epsilon in Adagrad, as TF),
 // and the slab-column-order state (param / s0 / s1 indexed by gradient column; wsc[col]: -1 padding, -2 wide weight,
 // >= 0 DNN weight with its bf16 weight-image offset). Included inside each translation unit's anonymous namespace.
@@ -8,6 +8,8 @@ struct OptHyper {
   int kind;        // 0 sgd, 1 adagrad, 2 ftrl, 3 adam
   float lr, beta1, beta2, eps, l1, l2, lr_power;
 };
+// the launchers' hyper_dnn / hyper_wide arguments: 8 host floats in the order of the fields
+inline OptHyper opt_hyper(const float* h) { return OptHyper{(int)h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7]}; }
 
 __device__ __forceinline__ float opt_update(const OptHyper& hp, float w, float g, float& a0, float& a1,
                                             long long step) {
@@ -45,7 +47,7 @@ __device__ __forceinline__ float opt_update(const OptHyper& hp, float w, float g
   }
 }
 
-// per-workgroup optimizer step slots (see csrc/wide_deep.hip)
+// per-workgroup optimizer step slots (see csrc/wd_tail.h)
 constexpr int STEP_SLOTS = 512;
 
 struct ScState {

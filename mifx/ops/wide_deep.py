@@ -1,4 +1,4 @@
-"""ctypes bindings for csrc/wide_deep.hip (fused Wide&Deep train/eval step on gfx950)."""
+"""ctypes bindings for csrc/wide_deep.hip (fused Wide&Deep train/eval step on gfx950; step tail: csrc/wd_tail.h)."""
 from __future__ import annotations
 
 import ctypes
@@ -25,8 +25,7 @@ def _fns():
         "xcd_chunks": sig(lib, "mifx_wd_xcd_chunks", [I32]),
         "reduce_xcd_opt": sig(lib, "mifx_wd_reduce_xcd_opt", [VP, I32, I32, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP,
                                                               VP, VP, VP, VP]),
-        "reduce_res_opt": sig(lib, "mifx_wd_reduce_res_opt", [VP, I32, I32, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP,
-                                                              VP]),
+        "reduce_res_opt": sig(lib, "mifx_wd_reduce_res_opt", [VP, I32, I32, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP]),
         "reduce_res_opt_fused": sig(lib, "mifx_wd_reduce_res_opt_fused", [VP, I32, I32, VP, VP, VP, VP, VP, VP, VP,
                                                                           VP, VP, VP, VP]),
         "xgmi_chunks": sig(lib, "mifx_wd_xgmi_chunks", [I32]),
@@ -79,7 +78,7 @@ def reduce(slab: torch.Tensor, groups: int, nsplit: int, partial: torch.Tensor) 
           "mifx_wd_reduce")
 
 
-STEP_SLOTS = 512  # csrc/wide_deep.hip: one step slot per optimizer workgroup, slot 0 = canonical step
+STEP_SLOTS = 512  # csrc/wd_opt.h: one step slot per optimizer workgroup, slot 0 = canonical step
 
 
 def _check_step_ctr(step_ctr: torch.Tensor) -> None:
@@ -87,11 +86,17 @@ def _check_step_ctr(step_ctr: torch.Tensor) -> None:
         raise ValueError(f"step_ctr must be a contiguous int64 tensor of {STEP_SLOTS} per-workgroup step slots")
 
 
+def _check_slab(slab: torch.Tensor, groups: int, stride: int) -> None:
+    if slab.shape[-1] != stride or slab.numel() < groups * stride or not slab.is_contiguous():
+        raise ValueError("slab must be contiguous [>= groups, stride]")
+
+
 def reduce_full(slab: torch.Tensor, groups: int, out: torch.Tensor) -> None:
     """out[stride] = sum of the first `groups` slab rows (one launch, fixed summation order)."""
     stride = int(slab.shape[-1])
-    if out.numel() < stride or slab.numel() < groups * stride or not slab.is_contiguous():
-        raise ValueError("slab must be contiguous [>= groups, stride] and out hold >= stride floats")
+    _check_slab(slab, groups, stride)
+    if out.numel() < stride:
+        raise ValueError("out must hold >= stride floats")
     rc = _fns()["reduce_opt"](ptr(slab), int(groups), stride, ptr(out), None, None, None, None, None, None, None,
                               None, None, stream_handle(slab.device))
     check(rc, "mifx_wd_reduce_opt")
@@ -109,8 +114,7 @@ def reduce_apply(slab: torch.Tensor, groups: int, inv: torch.Tensor, param: torc
     stride = int(slab.shape[-1])
     if inv.dtype != torch.int32 or inv.numel() != stride:
         raise ValueError("inv must be int32 [stride]")
-    if slab.numel() < groups * stride or not slab.is_contiguous():
-        raise ValueError("slab must be contiguous [>= groups, stride]")
+    _check_slab(slab, groups, stride)
     _check_step_ctr(step_ctr)
     rc = _fns()["reduce_opt"](ptr(slab), int(groups), stride, None, ptr(inv), ptr(param), ptr(s0), ptr(s1),
                               ptr(wt_out), ptr(wmap), ptr(step_ctr), ptr(hyper_dnn), ptr(hyper_wide),
@@ -121,7 +125,7 @@ def reduce_apply(slab: torch.Tensor, groups: int, inv: torch.Tensor, param: torc
 def reduce_apply_sc(slab: torch.Tensor, groups: int, wsc: torch.Tensor, param_sc: torch.Tensor, s0_sc: torch.Tensor,
                     s1_sc: torch.Tensor, wt_out: torch.Tensor, step_ctr: torch.Tensor, hyper_dnn: torch.Tensor,
                     hyper_wide: torch.Tensor) -> None:
-    """Slab [groups, stride] -> sum -> optimizer on slab-column-order state (csrc/wide_deep.hip wd_reduce_opt_sc)."""
+    """Slab [groups, stride] -> sum -> optimizer on slab-column-order state (csrc/wd_tail.h wd_reduce_opt_sc)."""
     stride = slab.shape[-1]
     for t in (wsc, param_sc, s0_sc, s1_sc):
         if t.numel() != stride or not t.is_contiguous():
@@ -133,8 +137,15 @@ def reduce_apply_sc(slab: torch.Tensor, groups: int, wsc: torch.Tensor, param_sc
     check(rc, "mifx_wd_reduce_opt_sc")
 
 
+def _reduce_launch(name: str, slab: torch.Tensor, groups: int, stride: int, *tensors) -> None:
+    """A two-level reduction launcher: (slab, groups, stride, the tensors in the C argument order, stream)."""
+    _check_slab(slab, groups, stride)
+    rc = _fns()[name](ptr(slab), int(groups), stride, *[ptr(t) for t in tensors], stream_handle(slab.device))
+    check(rc, "mifx_wd_" + name)
+
+
 class XcdReduce:
-    """Scratch for the XCD-local two-level slab reduction + optimizer (csrc/wide_deep.hip wd_reduce_xcd /
+    """Scratch for the XCD-local two-level slab reduction + optimizer (csrc/wd_tail.h wd_reduce_xcd /
     wd_xcd_opt_sc): xcd_of [256] (filled by the chained kernel), per-XCD partials [16, stride], epoch stamps and
     epoch slots."""
 
@@ -146,14 +157,9 @@ class XcdReduce:
         self.ok = torch.zeros(16 * nc1, dtype=torch.int32, device=device)
         self.xep = torch.zeros(STEP_SLOTS, dtype=torch.int64, device=device)
 
-    def _call(self, slab, groups, out, wsc, param_sc, s0_sc, s1_sc, wt_out, step_ctr, hyper_dnn, hyper_wide):
-        if slab.shape[-1] != self.stride or slab.numel() < groups * self.stride or not slab.is_contiguous():
-            raise ValueError("slab must be contiguous [>= groups, stride]")
-        rc = _fns()["reduce_xcd_opt"](ptr(slab), int(groups), self.stride, ptr(self.xcd_of), ptr(self.part),
-                                      ptr(self.ok), ptr(self.xep), ptr(out), ptr(wsc), ptr(param_sc), ptr(s0_sc),
-                                      ptr(s1_sc), ptr(wt_out), ptr(step_ctr), ptr(hyper_dnn), ptr(hyper_wide),
-                                      stream_handle(slab.device))
-        check(rc, "mifx_wd_reduce_xcd_opt")
+    def _call(self, slab, groups, out, *opt):
+        _reduce_launch("reduce_xcd_opt", slab, groups, self.stride, self.xcd_of, self.part, self.ok, self.xep, out,
+                       *opt)
 
     def apply_sc(self, slab: torch.Tensor, groups: int, wsc, param_sc, s0_sc, s1_sc, wt_out, step_ctr, hyper_dnn,
                  hyper_wide) -> None:
@@ -161,48 +167,32 @@ class XcdReduce:
         self._call(slab, groups, None, wsc, param_sc, s0_sc, s1_sc, wt_out, step_ctr, hyper_dnn, hyper_wide)
 
     def sum_into(self, slab: torch.Tensor, groups: int, out: torch.Tensor) -> None:
-        self._call(slab, groups, out, None, None, None, None, None, None, None, None)
+        self._call(slab, groups, out, *[None] * 8)
 
 
 class ResReduce:
-    """Scratch of the residue-class two-level slab reduction + optimizer (csrc/wide_deep.hip wd_reduce_res /
-    wd_res_opt_sc): per-residue partials [8, stride]. Same interface as XcdReduce."""
+    """Scratch of the residue-class two-level slab reduction + optimizer (csrc/wd_tail.h wd_reduce_res /
+    wd_res_opt_sc): per-residue partials [8, stride]. XcdReduce's apply_sc interface."""
 
     def __init__(self, stride: int, device, fused: bool | None = None):
         self.stride = int(stride)
         self.part = torch.zeros(8 * stride, device=device)
         self.xcd_of = None  # (no placement record needed)
         # fused (MIFX_WD_RES_FUSED=1): both levels in one launch, the optimizer run by the last of a chunk's residue
-        # workgroups (csrc/wide_deep.hip wd_reduce_res_fused); per-chunk tickets, zero between calls. Bit-identical
+        # workgroups (csrc/wd_tail.h wd_reduce_res_fused); per-chunk tickets, zero between calls. Bit-identical
         # to the two launches but measured slower on the headline step: 29.7-29.9 vs 28.3-28.5 us (release-fenced
         # ticket: 33.4-33.6), profiles/wd_res_fused_ab_r6.jsonl -- opt-in
         self.fused = os.environ.get("MIFX_WD_RES_FUSED", "0") == "1" if fused is None else bool(fused)
         self.ticket = torch.zeros((self.stride + 255) // 256, dtype=torch.int32, device=device)
 
-    def _call(self, slab, groups, out, wsc, param_sc, s0_sc, s1_sc, wt_out, step_ctr, hyper_dnn, hyper_wide):
-        if slab.shape[-1] != self.stride or slab.numel() < groups * self.stride or not slab.is_contiguous():
-            raise ValueError("slab must be contiguous [>= groups, stride]")
-        rc = _fns()["reduce_res_opt"](ptr(slab), int(groups), self.stride, ptr(self.part), ptr(out), ptr(wsc),
-                                      ptr(param_sc), ptr(s0_sc), ptr(s1_sc), ptr(wt_out), ptr(step_ctr),
-                                      ptr(hyper_dnn), ptr(hyper_wide), stream_handle(slab.device))
-        check(rc, "mifx_wd_reduce_res_opt")
-
     def apply_sc(self, slab: torch.Tensor, groups: int, wsc, param_sc, s0_sc, s1_sc, wt_out, step_ctr, hyper_dnn,
                  hyper_wide) -> None:
         _check_step_ctr(step_ctr)
+        opt = (wsc, param_sc, s0_sc, s1_sc, wt_out, step_ctr, hyper_dnn, hyper_wide)
         if self.fused:
-            if slab.shape[-1] != self.stride or slab.numel() < groups * self.stride or not slab.is_contiguous():
-                raise ValueError("slab must be contiguous [>= groups, stride]")
-            rc = _fns()["reduce_res_opt_fused"](ptr(slab), int(groups), self.stride, ptr(self.part), ptr(self.ticket),
-                                                ptr(wsc), ptr(param_sc), ptr(s0_sc), ptr(s1_sc), ptr(wt_out),
-                                                ptr(step_ctr), ptr(hyper_dnn), ptr(hyper_wide),
-                                                stream_handle(slab.device))
-            check(rc, "mifx_wd_reduce_res_opt_fused")
-            return
-        self._call(slab, groups, None, wsc, param_sc, s0_sc, s1_sc, wt_out, step_ctr, hyper_dnn, hyper_wide)
-
-    def sum_into(self, slab: torch.Tensor, groups: int, out: torch.Tensor) -> None:
-        self._call(slab, groups, out, None, None, None, None, None, None, None, None)
+            _reduce_launch("reduce_res_opt_fused", slab, groups, self.stride, self.part, self.ticket, *opt)
+        else:
+            _reduce_launch("reduce_res_opt", slab, groups, self.stride, self.part, *opt)
 
 
 def optimizer(partial: torch.Tensor, nparts: int, gidx: torch.Tensor, mask: torch.Tensor, param: torch.Tensor,

@@ -1,10 +1,15 @@
 """Device-resident, hipGraph-captured Wide&Deep trainer on the fused gfx950 kernels.
 
-One training step = ``wdc_fused`` (csrc/wd_chain.hip; or ``wd_fused`` with kernel="tile") (forward + loss +
-backward, per-workgroup gradient slabs) -> ``wd_reduce_opt`` (full slab sum + Adagrad/FTRL/Adam/SGD + bf16 weight image in ONE launch). When
-data-parallel the local sum is written to ONE flat 82 KB gradient bucket, RCCL all-reduced over xGMI,
-and the optimizer launch reads that bucket. (The older two-launch ``wd_reduce`` -> ``wd_optimizer``
-path stays selectable with ``fused_update=False`` for A/B.) The input
+One training step = ``wdc_fused`` (csrc/wd_chain.hip and its T = 64 / T = 256 builds; or ``wd_fused`` with
+kernel="tile") (forward + loss + backward, per-workgroup gradient slabs) -> the step tail (csrc/wd_tail.h): slab
+sum + Adagrad/FTRL/Adam/SGD + bf16 weight image. The tail the chained trainer runs on one GPU depends on the slab
+height: ``wd_opt1_sc`` for one slab row (the reference batch), ``wd_reduce_opt_sc`` below 64 rows, and from 64 to
+256 rows the two-level residue-class reduction ``wd_reduce_res`` -> ``wd_res_opt_sc`` (MIFX_WD_RES=0: the
+placement-recorded ``wd_reduce_xcd`` -> ``wd_xcd_opt_sc``; MIFX_WD_RES_FUSED=1: both levels in one launch). The
+tile kernel uses the canonical-order ``wd_reduce_opt``. Data-parallel, the local sum goes into ONE flat 82 KB
+gradient bucket that is RCCL all-reduced and read by the optimizer launch, or, with the xGMI exchange
+(mifx.parallel.xgmi), is exchanged by the tail kernels themselves with no host collective. (The older two-launch
+``wd_reduce`` -> ``wd_optimizer`` path stays selectable with ``fused_update=False`` for A/B.) The input
 shard lives in HBM; the data offset advances through a device-side step counter, so the whole
 step (collective included) can be captured once and replayed as a hipGraph.
 
@@ -53,9 +58,11 @@ def default_wide_opt(num_linear_columns: int = 9) -> OptSpec:
 
 
 class FusedWideDeepTrainer:
-    """kernel="chain" (default): csrc/wd_chain.hip, register-chained MFMA forward/backward, 128 examples per
-    workgroup iteration; kernel="tile": csrc/wide_deep.hip (wd_fused), LDS-staged activations, 64 per tile.
-    Both write the same kind of per-workgroup gradient slab, reduced + applied by wd_reduce_opt."""
+    """kernel="chain" (default): csrc/wd_chain.hip, register-chained MFMA forward/backward, T examples per workgroup
+    iteration: T = 128, or 64 for a batch of at most 64 (csrc/wd_chain64.hip), or 256 once a batch needs more than
+    max_grid iterations of 128 (csrc/wd_chain256.hip); kernel="tile": csrc/wide_deep.hip (wd_fused), LDS-staged
+    activations, 64 per tile. Both write the same kind of per-workgroup gradient slab, reduced + applied by the
+    step tail (csrc/wd_tail.h; see the module docstring for which kernels)."""
 
     def __init__(self, model: wdm.WideDeepModel | None = None, batch: int = 40, device="cuda",
                  dnn_opt: OptSpec | None = None, wide_opt: OptSpec | None = None, loss_reduction: str = "sum",
@@ -139,7 +146,7 @@ class FusedWideDeepTrainer:
         self.inv = torch.from_numpy(inv).to(dev)
         # Chained kernel: the master weights and optimizer state live in SLAB-COLUMN order (param_sc / s0_sc /
         # s1_sc [stride]) so the optimizer kernels index them by the gradient's own column (no inv[] -> state ->
-        # wmap chain of dependent loads; csrc/wide_deep.hip wd_reduce_opt_sc). wsc[col]: -1 padding, -2 wide
+        # wmap chain of dependent loads; csrc/wd_tail.h wd_reduce_opt_sc). wsc[col]: -1 padding, -2 wide
         # weight, >= 0 DNN weight with its bf16 weight-image offset. `param` / `s0` / `s1` are canonical views.
         self._sc = kernel == "chain"
         self._gidx_l = self.gidx.long()
@@ -156,14 +163,14 @@ class FusedWideDeepTrainer:
             self._param, self._s0, self._s1 = param, s0, s1
         self.wt = self._weight_image()
         self.fused_update = bool(fused_update)
-        # per-optimizer-workgroup step slots (slot 0 = the step; see csrc/wide_deep.hip STEP_SLOTS)
+        # per-optimizer-workgroup step slots (slot 0 = the step; see csrc/wd_opt.h STEP_SLOTS)
         self.step_ctr = torch.zeros(wdk.STEP_SLOTS, dtype=torch.int64, device=dev)
         self.slab = torch.empty(self.grid, self.stride, device=dev)
         # chained kernel, one rank: XCD-local two-level slab reduction (each XCD's slab rows summed where its L2
-        # holds them; csrc/wide_deep.hip wd_reduce_xcd)
+        # holds them; csrc/wd_tail.h wd_reduce_xcd)
         # (small grids keep the one-pass reduce: below ~64 workgroups there is little slab to keep local)
         # default: the residue-class variant (rows b == k mod 8 per partial; no placement record, no XCD ordering:
-        # csrc/wide_deep.hip wd_reduce_res) -- 29.9 vs 32.4 us per headline step on MI355X
+        # csrc/wd_tail.h wd_reduce_res) -- 29.9 vs 32.4 us per headline step on MI355X
         # (profiles/wd_res_ab_r6.jsonl); MIFX_WD_RES=0: the placement-recorded XCD reduction
         use_xcd = os.environ.get("MIFX_WD_XCD", "1") != "0"
         # (data parallelism keeps the XCD-recorded scratch: the xGMI exchange kernel sums the per-XCD partials itself,
@@ -463,7 +470,7 @@ class FusedWideDeepTrainer:
 
     def _check_exchange(self) -> None:
         """Raise if the xGMI exchange timed out on this rank (the kernels then stopped updating: see
-        csrc/wide_deep.hip xg_wait). Called at every host synchronisation point."""
+        csrc/wd_tail.h xg_wait). Called at every host synchronisation point."""
         if self._xg is not None:
             self._xg.check()
         if self._ktail is not None:
