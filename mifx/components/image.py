@@ -5,7 +5,10 @@
   set; deterministic hash split train:eval = 2:1; writes `images.npy` / `labels.npy` per split.
 * `ImageTransform`: full-pass per-channel mean / std analyzer over the training split (fp64 on the
   GPU via the HIP column-moments kernel when available) -> transform artifact (JSON), applied by the
-  trainer's fused crop/flip/normalize kernel.
+  trainer's fused crop/flip/normalize kernel. It owns the preprocessing recipe: optional `augment`
+  ("random_resized_crop": a random box of `rrc_scale` of the image at an aspect ratio in `rrc_ratio`,
+  resized to the crop size), and `eval_resize` (evaluate on resize-then-centre-crop); all off by default
+  and written as extra keys of `image_transform.json`.
 * `ImageTrainer`: ResNet-50 v2 on the fused input kernel, bf16 channels_last, optional
   data-parallel (RCCL) inside the component; exports a servable model (`save_module`)."""
 from __future__ import annotations
@@ -74,7 +77,9 @@ class ImageExampleGen(_KwComponent):
 class ImageTransformSpec(ComponentSpec):
     INPUTS = {"input_data": ChannelParameter(A.EXAMPLES)}
     OUTPUTS = {"transform_output": ChannelParameter(A.TRANSFORM)}
-    PARAMETERS = {"crop": ExecutionParameter(optional=True, default=224)}
+    PARAMETERS = {"crop": ExecutionParameter(optional=True, default=224),
+                  "augment": ExecutionParameter(optional=True), "rrc_scale": ExecutionParameter(optional=True),
+                  "rrc_ratio": ExecutionParameter(optional=True), "eval_resize": ExecutionParameter(optional=True)}
 
 
 class ImageTransformExecutor(BaseExecutor):
@@ -85,7 +90,8 @@ class ImageTransformExecutor(BaseExecutor):
         out = output_dict["transform_output"][0]
         os.makedirs(out.uri, exist_ok=True)
         with open(os.path.join(out.uri, "image_transform.json"), "w") as f:
-            json.dump({"mean": mean, "std": std, "crop": int(exec_properties.get("crop") or 224)}, f)
+            json.dump({"mean": mean, "std": std, "crop": int(exec_properties.get("crop") or 224),
+                       **resolve_input_config(exec_properties, given_only=True)}, f)
 
 
 def _channel_stats(imgs: np.ndarray):
@@ -143,6 +149,30 @@ def resolve_optimizer_config(cc: dict, learning_rate: float, train_steps: int) -
             "lars_clip": bool(cc.get("lars_clip", False)), "label_smoothing": float(cc.get("label_smoothing", 0.0))}
 
 
+def resolve_input_config(tf: dict, given_only: bool = False) -> dict:
+    """The input recipe keys of ImageTransform's parameters / image_transform.json -> the ResNetTrainer arguments
+    (what the result records under "input"). given_only: just the keys that are set (what the Transform writes: a
+    JSON without them behaves as before)."""
+    from ..ops.image_ops import RRC_RATIO, RRC_SCALE, check_rrc_ranges
+
+    aug = tf.get("augment") or None
+    if aug == "none":
+        aug = None
+    if aug not in (None, "random_resized_crop"):
+        raise ValueError(f'augment must be "random_resized_crop" or unset, got {aug!r}')
+    if aug is None and (tf.get("rrc_scale") is not None or tf.get("rrc_ratio") is not None):
+        raise ValueError("rrc_scale / rrc_ratio need augment")
+    scale = tuple(float(v) for v in (tf.get("rrc_scale") or RRC_SCALE))
+    ratio = tuple(float(v) for v in (tf.get("rrc_ratio") or RRC_RATIO))
+    check_rrc_ranges(scale, ratio)
+    ev = tf.get("eval_resize")
+    out = {"augment": aug, "rrc_scale": list(scale), "rrc_ratio": list(ratio),
+           "eval_resize": None if ev is None else int(ev)}
+    if given_only:
+        out = {k: v for k, v in out.items() if tf.get(k) is not None and (k != "augment" or aug is not None)}
+    return out
+
+
 def run_image_rank(spec: dict) -> dict:
     """One rank (or the only process) of the image Trainer: ResNet-50 v2 on the examples of `spec`, resuming
     from the latest checkpoint in <out>/serving_model_dir, checkpointing every `checkpoint_every` steps (rank 0
@@ -168,12 +198,15 @@ def run_image_rank(spec: dict) -> dict:
         dev = f"cuda:{0 if os.environ.get('MIFX_SHARED_GPU') == '1' else int(os.environ.get('LOCAL_RANK', 0))}"
     steps = int(spec["train_steps"])
     oc = resolve_optimizer_config(cc, float(spec["learning_rate"]), steps)
+    ic = resolve_input_config(tf)
     tr = ResNetTrainer(int(spec["batch_size"]), dev, imgs, labels, num_classes=int(spec["num_classes"]),
                        lr=oc["learning_rate"], warmup_steps=oc["warmup_steps"], mean=tuple(tf["mean"]),
                        std=tuple(tf["std"]), crop=int(tf["crop"]), process_group=pg, seed=int(cc.get("seed", 0)),
                        accum_steps=int(cc.get("accum_steps", 1)), lr_schedule=oc["lr_schedule"],
                        total_steps=oc["total_steps"], end_lr=oc["end_lr"], lars=oc["lars"], lars_eta=oc["lars_eta"],
-                       lars_clip=oc["lars_clip"], label_smoothing=oc["label_smoothing"])
+                       lars_clip=oc["lars_clip"], label_smoothing=oc["label_smoothing"], augment=ic["augment"],
+                       rrc_scale=tuple(ic["rrc_scale"]), rrc_ratio=tuple(ic["rrc_ratio"]),
+                       eval_resize=ic["eval_resize"])
     model_dir = os.path.join(spec["out_dir"], "serving_model_dir")
     ck = ResNetTrainer.latest_checkpoint(model_dir)
     if ck:
@@ -196,7 +229,7 @@ def run_image_rank(spec: dict) -> dict:
     secs = time.time() - t0
     res = {"final_loss": float(loss), "world": world, "steps": tr.step_idx, "resumed_from": ck,
            "train_images_per_sec": (tr.step_idx - s0) * tr.batch * tr.accum * world / max(secs, 1e-9),
-           "optimizer": dict(oc, final_lr=tr.last_lr())}
+           "optimizer": dict(oc, final_lr=tr.last_lr()), "input": tr.input_recipe()}
     if rank == 0:
         tr.save_checkpoint(model_dir)
         ev_imgs = torch.from_numpy(np.load(os.path.join(spec["eval_uri"], "images.npy"), allow_pickle=False))
@@ -216,7 +249,9 @@ class ImageTrainerExecutor(BaseExecutor):
     `research/pate_2017/deep_cnn.py:489,541-542`), accum_steps, seed, timeout_s. Optimizer recipe
     (`resolve_optimizer_config`; recorded in metrics.json under "optimizer" and in the output's custom properties):
     lr_schedule ("constant" | "cosine" | "poly", decaying to end_lr at train_steps), lars, lars_eta, lars_clip,
-    label_smoothing."""
+    label_smoothing. The input recipe (augment, rrc_scale, rrc_ratio, eval_resize) comes from the Transform's
+    image_transform.json; the resolved settings are recorded in metrics.json under "input" and in the output's custom
+    properties (input_augment, input_rrc_scale_lo / _hi, input_rrc_ratio_lo / _hi, input_eval_resize)."""
 
     def Do(self, input_dict, output_dict, exec_properties):  # noqa: N802
         ex = {a.split: a.uri for a in input_dict["examples"]}
@@ -246,6 +281,13 @@ class ImageTrainerExecutor(BaseExecutor):
         # the resolved optimizer recipe (bools as 0 / 1, unset values left out: MLMD properties are int / float / str)
         out.custom_properties.update({k: int(v) if isinstance(v, bool) else v
                                       for k, v in (res.get("optimizer") or {}).items() if v is not None})
+        inp = res.get("input") or {}
+        if inp:
+            out.custom_properties["input_augment"] = str(inp["augment"])
+            for k in ("rrc_scale", "rrc_ratio"):
+                out.custom_properties[f"input_{k}_lo"], out.custom_properties[f"input_{k}_hi"] = map(float, inp[k])
+            if inp.get("eval_resize") is not None:
+                out.custom_properties["input_eval_resize"] = int(inp["eval_resize"])
         self.context.logger.info("ImageTrainer: %d replica(s), loss %.4f eval accuracy %.4f", res["world"],
                                  res["final_loss"], res["eval_accuracy"])
 

@@ -5,7 +5,11 @@ BatchNorm-backward sums and residual adds in its epilogues; weight gradients are
 (mifx.ops.gemm.deferred_weight_grads); SGD + Nesterov momentum with linear warmup is one fused multi-tensor kernel
 (csrc/sgd.hip). Optional large-batch recipe: LARS trust ratios, cosine / polynomial decay and label smoothing
 (lars=, lr_schedule=, label_smoothing=); in the captured step the ratios and the learning rate are computed on the
-device from the step counter, nothing is written by the host. What MIOpen still runs is listed in README.md.
+device from the step counter, nothing is written by the host. Optional input recipe (off by default):
+augment="random_resized_crop" replaces the fixed-size random crop by scale + aspect-ratio augmentation (a random box
+of rrc_scale of the image at an aspect ratio in rrc_ratio, resized bilinearly to the crop size by the box + resample
+kernels of csrc/image_ops.hip), and eval_resize=N evaluates on resize-to-N-then-centre-crop. What MIOpen still runs
+is listed in README.md.
 
 On the GPU the step is captured into hipGraphs after `graph_warmup` eager steps (graph=True, the default there):
 graph A = gradient zeroing + every micro-batch's input kernel, forward and backward (the step counter, learning rate
@@ -30,7 +34,8 @@ import torch.nn.functional as F
 
 from ..models.resnet import resnet50_v2
 from ..ops.bn_relu import defer_batch_counts
-from ..ops.image_ops import IMAGENET_MEAN, IMAGENET_STD, crop_flip_normalize
+from ..ops.image_ops import (IMAGENET_MEAN, IMAGENET_STD, RRC_RATIO, RRC_SCALE, check_rrc_ranges, crop_flip_normalize,
+                             random_resized_crop_normalize)
 from ..parallel import dist as mdist
 from ..parallel.ddp import DataParallel
 from ..utils.meter import heartbeat
@@ -53,7 +58,8 @@ class ResNetTrainer:
                  accum_steps: int = 1, graph: bool | None = None, graph_warmup: int = 2, force_dp: bool = False,
                  lr_schedule: str = "constant", total_steps: int | None = None, end_lr: float = 0.0,
                  lars: bool = False, lars_eta: float = 0.001, lars_eps: float = 1e-8, lars_clip: bool = False,
-                 label_smoothing: float = 0.0):
+                 label_smoothing: float = 0.0, augment: str | None = None, rrc_scale=RRC_SCALE, rrc_ratio=RRC_RATIO,
+                 eval_resize: int | None = None):
         """batch: examples per micro-batch per replica; accum_steps micro-batches (each with its own BatchNorm
         statistics) are summed into one update. A data-parallel step over W ranks trains on W x accum_steps x batch
         examples: the global sample of the step is drawn from (seed, step) and rank r takes micro-batches
@@ -64,7 +70,13 @@ class ResNetTrainer:
         end_lr at total_steps (mifx.ops.sgd.scheduled_lr); lars scales every tensor with more than one dimension by
         its trust ratio lars_eta ||w|| / (||g|| + wd ||w|| + lars_eps) in front of the SGD update (lars_clip: LARC
         clipping), on the averaged gradients under data parallelism; label_smoothing goes to the cross entropy.
-        In the captured step the schedule and the ratios are evaluated on the device (csrc/sgd.hip)."""
+        In the captured step the schedule and the ratios are evaluated on the device (csrc/sgd.hip).
+
+        Input recipe (off by default): augment="random_resized_crop" trains on a random box per image, covering a
+        fraction in rrc_scale of it at an aspect ratio in rrc_ratio (ratio_lo <= 1 <= ratio_hi), resized to
+        crop x crop (mifx.ops.image_ops.random_resized_crop_normalize); the boxes are a pure function of
+        (seed, step, slot), so checkpoints carry nothing new. eval_resize=N (>= crop) evaluates on the central
+        round(min(H, W) crop / N) square resized to crop x crop: resize the shorter side to N, then centre-crop."""
         from ..ops.sgd import scheduled_lr
 
         scheduled_lr(lr_schedule, lr, warmup_steps, total_steps, end_lr, 0)  # ValueError on an invalid combination
@@ -76,6 +88,16 @@ class ResNetTrainer:
             raise ValueError("lars_eta / lars_eps / lars_clip need lars=True")
         if lr_schedule == "constant" and (total_steps is not None or end_lr):
             raise ValueError('total_steps / end_lr need lr_schedule="cosine" or "poly"')
+        if augment not in (None, "random_resized_crop"):
+            raise ValueError(f'augment must be None or "random_resized_crop", got {augment!r}')
+        if augment is None and (tuple(rrc_scale) != tuple(RRC_SCALE) or tuple(rrc_ratio) != tuple(RRC_RATIO)):
+            raise ValueError('rrc_scale / rrc_ratio need augment="random_resized_crop"')
+        check_rrc_ranges(rrc_scale, rrc_ratio)
+        if eval_resize is not None and int(eval_resize) < crop:
+            raise ValueError(f"eval_resize must be at least the crop size {crop}, got {eval_resize}")
+        self.augment = augment
+        self.rrc_scale, self.rrc_ratio = tuple(float(v) for v in rrc_scale), tuple(float(v) for v in rrc_ratio)
+        self.eval_resize = None if eval_resize is None else int(eval_resize)
         self.lr_schedule, self.total_steps, self.end_lr = lr_schedule, total_steps, float(end_lr)
         self.lars = {"eta": float(lars_eta), "eps": float(lars_eps), "clip": bool(lars_clip)} if lars else None
         self.label_smoothing = float(label_smoothing)
@@ -199,6 +221,21 @@ class ResNetTrainer:
                 return out
         return None
 
+    def _train_input(self, idx: torch.Tensor, step: int, step_dev: torch.Tensor | None = None) -> torch.Tensor:
+        """One micro-batch's input: the fixed-size random crop, or the random-resized crop with augment set."""
+        dtype = torch.bfloat16 if self.amp else torch.float32
+        if self.augment is None:
+            return crop_flip_normalize(self.images, idx, (self.crop, self.crop), True, self.seed, step, self.mean,
+                                       self.std, dtype, step_dev=step_dev)
+        return random_resized_crop_normalize(self.images, idx, (self.crop, self.crop), True, self.seed, step,
+                                             self.mean, self.std, dtype, step_dev=step_dev, scale=self.rrc_scale,
+                                             ratio=self.rrc_ratio)
+
+    def input_recipe(self) -> dict:
+        """The resolved input settings (what results record under "input")."""
+        return {"augment": self.augment or "none", "rrc_scale": list(self.rrc_scale),
+                "rrc_ratio": list(self.rrc_ratio), "eval_resize": self.eval_resize}
+
     def _step_indices(self) -> torch.Tensor:
         """The global sample of this step ([world * accum * batch], from (seed, step) on a host generator: the same
         on every rank and device)."""
@@ -229,8 +266,7 @@ class ResNetTrainer:
         for m in range(self.accum):
             mb = self.rank * self.accum + m
             idx = glob[mb * self.batch:(mb + 1) * self.batch].to(self.device)
-            x = crop_flip_normalize(self.images, idx, (self.crop, self.crop), True, self.seed, self.step_idx,
-                                    self.mean, self.std, torch.bfloat16 if self.amp else torch.float32)
+            x = self._train_input(idx, self.step_idx)
             y = self.labels[idx]
             with torch.autocast(self.device.type, dtype=torch.bfloat16, enabled=self.amp):
                 loss = F.cross_entropy(self.model(x).float(), y, label_smoothing=self.label_smoothing) / self.accum
@@ -320,9 +356,7 @@ class ResNetTrainer:
             for m in range(self.accum):
                 mb = self.rank * self.accum + m
                 idx = self._idx_dev[mb * self.batch:(mb + 1) * self.batch]
-                x = crop_flip_normalize(self.images, idx, (self.crop, self.crop), True, self.seed, 0, self.mean,
-                                        self.std, torch.bfloat16 if self.amp else torch.float32,
-                                        step_dev=self._step_dev)
+                x = self._train_input(idx, 0, step_dev=self._step_dev)
                 y = self.labels[idx]
                 with torch.autocast(self.device.type, dtype=torch.bfloat16, enabled=self.amp):
                     loss = F.cross_entropy(self.model(x).float(), y,
@@ -481,8 +515,13 @@ class ResNetTrainer:
         correct = 0
         for s in range(0, len(labels), batch):
             idx = torch.arange(s, min(s + batch, len(labels)), device=self.device)
-            x = crop_flip_normalize(images.to(self.device), idx, (self.crop, self.crop), False, 0, 0, self.mean,
-                                    self.std, torch.bfloat16 if self.amp else torch.float32)
+            dtype = torch.bfloat16 if self.amp else torch.float32
+            if self.augment is None and self.eval_resize is None:
+                x = crop_flip_normalize(images.to(self.device), idx, (self.crop, self.crop), False, 0, 0, self.mean,
+                                        self.std, dtype)
+            else:  # the central box of eval_resize (None: the central crop itself) through the resample kernel
+                x = random_resized_crop_normalize(images.to(self.device), idx, (self.crop, self.crop), False, 0, 0,
+                                                  self.mean, self.std, dtype, eval_resize=self.eval_resize)
             with torch.autocast(self.device.type, dtype=torch.bfloat16, enabled=self.amp):
                 correct += int((self.model(x).argmax(1) == labels[s:s + batch].to(self.device)).sum())
         self.model.train()
@@ -508,6 +547,13 @@ def main(argv=None):
     ap.add_argument("--lars-eta", type=float, default=0.001)
     ap.add_argument("--lars-clip", action="store_true", help="LARC clipping: min(ratio / lr, 1)")
     ap.add_argument("--label-smoothing", type=float, default=0.0)
+    ap.add_argument("--augment", choices=("none", "random_resized_crop"), default="none",
+                    help="random_resized_crop: a random box (area --rrc-scale of the image, aspect ratio --rrc-ratio) "
+                         "resized to the crop size, instead of the fixed-size random crop")
+    ap.add_argument("--rrc-scale", type=float, nargs=2, metavar=("LO", "HI"), default=None, help="default 0.08 1.0")
+    ap.add_argument("--rrc-ratio", type=float, nargs=2, metavar=("LO", "HI"), default=None, help="default 3/4 4/3")
+    ap.add_argument("--eval-resize", type=int, default=None,
+                    help="evaluate on resize-the-shorter-side-to-N, then centre-crop (default: centre-crop alone)")
     a = ap.parse_args(argv)
     if a.deterministic:
         torch.backends.cudnn.deterministic = True
@@ -528,7 +574,10 @@ def main(argv=None):
     pg = torch.distributed.group.WORLD if env.world_size > 1 or force else None
     tr = ResNetTrainer(a.batch, dev, imgs, labels, process_group=pg, lr=a.lr, warmup_steps=10, graph=not a.no_graph,
                        force_dp=force, lr_schedule=a.lr_schedule, total_steps=a.total_steps, end_lr=a.end_lr,
-                       lars=a.lars, lars_eta=a.lars_eta, lars_clip=a.lars_clip, label_smoothing=a.label_smoothing)
+                       lars=a.lars, lars_eta=a.lars_eta, lars_clip=a.lars_clip, label_smoothing=a.label_smoothing,
+                       augment=None if a.augment == "none" else a.augment, eval_resize=a.eval_resize,
+                       **({"rrc_scale": tuple(a.rrc_scale)} if a.rrc_scale else {}),
+                       **({"rrc_ratio": tuple(a.rrc_ratio)} if a.rrc_ratio else {}))
     for i in range(a.warmup):  # first steps include MIOpen solver search/compile: report progress
         t1 = time.perf_counter()
         with heartbeat("resnet warmup"):
@@ -561,7 +610,7 @@ def main(argv=None):
                           "sgd": "fused" if getattr(tr, "_sgd_tab", None) is not None else "foreach",
                           "lr_schedule": tr.lr_schedule, "lars": tr.lars is not None,
                           "label_smoothing": tr.label_smoothing, "last_lr": tr.last_lr(),
-                          "lr_on_device": tr._lr_on_device,
+                          "lr_on_device": tr._lr_on_device, "augment": a.augment,
                           "deterministic": bool(torch.backends.cudnn.deterministic)}), flush=True)
     mdist.shutdown()
 
