@@ -23,6 +23,13 @@
 //    accumulators in registers across ALL iterations (MFMA K-accumulation == batch reduction), so the
 //    workgroup writes one gradient slab at the end, in the same tile-native layout as wd_fused.
 //    The ReLU masks of the backward come from the staged activations (C order, 8-byte reads).
+//  * Only live tiles are computed. The model 3 -> 100 -> 70 -> 48 -> 34 -> 1 is padded to 32 -> 128 -> 96 -> 64 -> 64
+//    -> 16, and the padding fills whole trailing 16x16 tiles on every axis the kernel walks: natural n tiles in the
+//    forward (7, 5, 4, 3, 1 of 8, 6, 4, 4, 1), C-order k tiles in the activation gradient, the mask reads and the dW
+//    columns (1, 7, 5, 4, 3 of 2, 8, 6, 4, 4), and -- because stage() places the dZ fragments so that the staged
+//    16-column tiles are natural feature tiles -- natural n tiles in the dW rows (7, 5, 3, 3, 1). 72 dW tiles of 108
+//    are computed and stored (1952 MFMAs per 256 examples instead of 2368); the counts are compile-time constants
+//    (FN / DN / KT below), exported through mifx_wdc_constants and checked by the host against the model.
 //  * Wide part: embedding-bag gather of 9 fp32 weights per example (issued before the forward), fixed-point
 //    LDS histogram for its gradient (order-independent -> deterministic), as in wd_fused.
 //
@@ -68,6 +75,30 @@ constexpr int K2 = 128, N2 = 96;
 constexpr int K3 = 96, N3 = 64;
 constexpr int K4 = 64, N4 = 64;
 constexpr int K5 = 64, N5 = 16;
+// The real widths inside that padding: 3 dense inputs -> 100 -> 70 -> 48 -> 34 -> 1 logit. Row R_l of layers 1-4 is the
+// constant-1 row (models.wide_deep.pack_canonical), which carries the next layer's bias, so rows 0..R_l are live in
+// the forward and columns 0..R_{l-1} on every k axis. Padding fills WHOLE trailing 16x16 tiles on both axes, and the
+// kernel skips those at compile time: no MFMA, no weight / mask / dW fragment read for them (their results were
+// exact zeros). The host refuses a model whose live tiles differ (ops.wd_chain.check_live_tiles against the counts
+// mifx_wdc_constants exports): zero padding alone no longer makes another width correct.
+constexpr int R0 = 3, R1 = 100, R2 = 70, R3 = 48, R4 = 34, R5 = 1;
+constexpr int cdiv16(int n) { return (n + 15) / 16; }
+// live C-order k tiles of an axis with `live` leading features: tile 2 s + b holds the features
+// 32 s + 8 b + {0..7, 16..23}, so its smallest feature 32 s + 8 b grows with the tile index: a prefix
+constexpr int live_ctiles(int live, int K) {
+  int n = 0;
+  for (int t = 0; t < K / 16; ++t) n += 32 * (t / 2) + 8 * (t % 2) < live ? 1 : 0;
+  return n;
+}
+// forward n tiles (rows incl. the constant-1 row), dW n tiles (trainable rows; natural order, see stage()) and
+// C-order k tiles per layer
+constexpr int FN1 = cdiv16(R1 + 1), FN2 = cdiv16(R2 + 1), FN3 = cdiv16(R3 + 1), FN4 = cdiv16(R4 + 1), FN5 = cdiv16(R5);
+constexpr int DN1 = cdiv16(R1), DN2 = cdiv16(R2), DN3 = cdiv16(R3), DN4 = cdiv16(R4), DN5 = cdiv16(R5);
+constexpr int KT1 = live_ctiles(R0 + 1, K1), KT2 = live_ctiles(R1 + 1, K2), KT3 = live_ctiles(R2 + 1, K3),
+              KT4 = live_ctiles(R3 + 1, K4), KT5 = live_ctiles(R4 + 1, K5);
+static_assert(FN1 == 7 && FN2 == 5 && FN3 == 4 && FN4 == 3 && FN5 == 1, "forward n tiles");
+static_assert(KT1 == 1 && KT2 == 7 && KT3 == 5 && KT4 == 4 && KT5 == 3, "C-order k tiles");
+static_assert(DN1 * KT1 + DN2 * KT2 + DN3 * KT3 + DN4 * KT4 + DN5 * KT5 == 72, "live dW tiles");
 
 // weight image (bf16, global layout; the LDS placement below): W_l^T [N_l][K_l + WPAD], columns in C order
 constexpr int LW1 = 0;
@@ -227,10 +258,11 @@ __device__ unsigned long long g_wdc_blk[4096][3];
 
 // ---- forward layer for the wave's two column blocks: acc[tb][nt] = W^T[16 nt ..][.] . B[tb][.]
 // W image rows natural, columns C order; B[tb][s] is the k-step-s fragment (C order) of the layer input.
-template <int K, int N, int TBN>
-__device__ __forceinline__ void fwd(const uint16_t* W, const v8bf (&B)[TBN][K / 32], v4f (&acc)[TBN][N / 16], int r,
+// Only the NT live n tiles are computed (the rest of the N / 16 hold padding rows: relu_pack gives zeros for them).
+template <int K, int NT, int TBN>
+__device__ __forceinline__ void fwd(const uint16_t* W, const v8bf (&B)[TBN][K / 32], v4f (&acc)[TBN][NT], int r,
                                     int h) {
-  constexpr int KS = K / 32, NT = N / 16;
+  constexpr int KS = K / 32;
 #pragma unroll
   for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
@@ -252,21 +284,33 @@ __device__ __forceinline__ void fwd(const uint16_t* W, const v8bf (&B)[TBN][K / 
   }
 }
 
-template <int N, int TBN>
-__device__ __forceinline__ void relu_pack(const v4f (&acc)[TBN][N / 16], v8bf (&out)[TBN][N / 32]) {
+// (NT live tiles of N / 16: a dead tile's half of the fragment, or the whole fragment, is zero)
+template <int N, int NT, int TBN>
+__device__ __forceinline__ void relu_pack(const v4f (&acc)[TBN][NT], v8bf (&out)[TBN][N / 32]) {
 #pragma unroll
   for (int tb = 0; tb < TBN; ++tb)
 #pragma unroll
-    for (int s = 0; s < N / 32; ++s) out[tb][s] = pack_relu(acc[tb][2 * s], acc[tb][2 * s + 1]);
+    for (int s = 0; s < N / 32; ++s) {
+      if (2 * s + 1 < NT) {
+        out[tb][s] = pack_relu(acc[tb][2 * s], acc[tb][2 * s + 1]);
+      } else if (2 * s < NT) {
+        const unsigned int u[4] = {relu_pk(cvt_pk(acc[tb][2 * s][0], acc[tb][2 * s][1])),
+                                   relu_pk(cvt_pk(acc[tb][2 * s][2], acc[tb][2 * s][3])), 0u, 0u};
+        out[tb][s] = __builtin_bit_cast(v8bf, u);
+      } else {
+        out[tb][s] = (v8bf){};
+      }
+    }
 }
 
 // ---- activation gradient: dA^T[k][t] = sum_n W[n][k] dZ[n][t] for the W image of a layer (K x N), its
 // rows (n, natural) read transposed at the rows that match the chained dZ fragments (C order of the layer
-// above). dz[tb][kt'] are the previous gradient tiles (N/16 of them); out[tb][kt] the K/16 output tiles.
-template <int K, int N, int TBN>
+// above). dz[tb][kt'] are the previous gradient tiles (N/16 of them, the first NTL live, the rest zero);
+// out[tb][kt] the K/16 output tiles, of which the KTL live ones are computed (the rest: zero, no weight read).
+template <int K, int N, int KTL, int NTL, int TBN>
 __device__ __forceinline__ void bwd_dA(const uint16_t* W, const v4bf (&dz)[TBN][N / 16], v4f (&out)[TBN][K / 16], int r,
                                        int h) {
-  constexpr int NS = N / 32, KT = K / 16;
+  constexpr int NS = (NTL + 1) / 2, KT = K / 16;  // k-steps that hold a live dz tile
   const int q = r >> 2, p = r & 3;
   const int rb = wperm(16 * (h & 1) + 4 * (h >> 1) + q);  // + 32 s (+8): bits 3, 5, 6 untouched by wperm
   v8bf b[TBN][NS];
@@ -279,7 +323,7 @@ __device__ __forceinline__ void bwd_dA(const uint16_t* W, const v4bf (&dz)[TBN][
 #pragma unroll
     for (int tb = 0; tb < TBN; ++tb) out[tb][kt] = kZero4;
 #pragma unroll
-  for (int kt = 0; kt < KT; ++kt) {
+  for (int kt = 0; kt < KTL; ++kt) {
     v8bf a[NS];
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
@@ -294,7 +338,8 @@ __device__ __forceinline__ void bwd_dA(const uint16_t* W, const v4bf (&dz)[TBN][
 }
 
 // ReLU mask of the layer input from the staged activation (C order) and bf16 pack of the gradient
-template <int K, int TBN>
+// (KTL live k tiles; the gradient of a dead tile is zero without reading its mask)
+template <int K, int KTL, int TBN>
 __device__ __forceinline__ void mask_grad(const v4f (&g)[TBN][K / 16], const uint16_t* SA, int w, int r, int h,
                                           v4bf (&dz)[TBN][K / 16]) {
   const int rp = sperm16(r);
@@ -302,6 +347,10 @@ __device__ __forceinline__ void mask_grad(const v4f (&g)[TBN][K / 16], const uin
   for (int tb = 0; tb < TBN; ++tb)
 #pragma unroll
     for (int kt = 0; kt < K / 16; ++kt) {
+      if (kt >= KTL) {
+        dz[tb][kt] = (v4bf){(bf16)0.f, (bf16)0.f, (bf16)0.f, (bf16)0.f};
+        continue;
+      }
       const int row = 16 * TBN * w + 16 * tb + rp;
       const uint2 m = *(const uint2*)(SA + row * (K + PAD) + 16 * kt + 4 * h);
       const unsigned int u[2] = {mask_pk(cvt_pk(g[tb][kt][0], g[tb][kt][1]), m.x),
@@ -312,28 +361,37 @@ __device__ __forceinline__ void mask_grad(const v4f (&g)[TBN][K / 16], const uin
 
 // stage dZ (gradient tiles, C order of the layer above: tiles 2m, 2m+1 = the 16-byte fragment of C positions
 // 32 m + 8 h, as bwd_dA consumes them) and the layer's input activation fragments (C order) for the dW product
-// of a layer with dims K x N; rows permuted by sperm16 inside each 16-row block
+// of a layer with dims K x N; rows permuted by sperm16 inside each 16-row block.
+// The dZ fragment of lane group h holds the features 32 m + 16 (h & 1) + 4 (h >> 1) + {0..3, 8..11}; stored at
+// column 32 m + 8 (2 (h & 1) + (h >> 1)) -- h with its two bits swapped, still one 16-byte store -- staged 16-column
+// tile j holds exactly the features 16 j .. 16 j + 15 (inner order 0-3, 8-11, 4-7, 12-15: the host's
+// models.wide_deep.chain_dw_rows). The dW n tiles are then natural tiles, and the padding rows fill whole tiles.
+// Full rows are written, zeros included (narrower or divergent variants measured slower: profiles/wd_t256_onepass.md)
 template <int K, int N, int TBN>
 __device__ __forceinline__ void stage(uint16_t* S, const v4bf (&dz)[TBN][N / 16], const v8bf (&a)[TBN][K / 32], int w,
                                       int r, int h) {
   uint16_t* SZ = S;
   uint16_t* SA = S + T * (N + PAD);
   const int rp = sperm16(r);
+  const int hz = 2 * (h & 1) + (h >> 1);
 #pragma unroll
   for (int tb = 0; tb < TBN; ++tb) {
     const int row = 16 * TBN * w + 16 * tb + rp;
 #pragma unroll
-    for (int m = 0; m < N / 32; ++m) *(v8bf*)(SZ + row * (N + PAD) + 32 * m + 8 * h) = cat_bf(dz[tb][2 * m], dz[tb][2 * m + 1]);
+    for (int m = 0; m < N / 32; ++m) *(v8bf*)(SZ + row * (N + PAD) + 32 * m + 8 * hz) = cat_bf(dz[tb][2 * m], dz[tb][2 * m + 1]);
 #pragma unroll
     for (int s = 0; s < K / 32; ++s) *(v8bf*)(SA + row * (K + PAD) + 32 * s + 8 * h) = a[tb][s];
   }
 }
 
 // ---- weight gradient: the wave's NTW x KTW tiles (nt = nt0 + i ntS, kt = kt0 + j ktS) accumulate
-// dW^T[n][k] += sum_t dZ[t][n] A[t][k] over the T staged rows (k-steps of 32 examples)
-template <int K, int N, int NTW, int KTW>
+// dW^T[n][k] += sum_t dZ[t][n] A[t][k] over the T staged rows (k-steps of 32 examples).
+// NA x KA (<= NTW x KTW) of the block are live for this call: the others' fragments are not read and their
+// accumulators (slot i KTW + j all the same) stay untouched.
+template <int K, int N, int NTW, int KTW, int NA = NTW, int KA = KTW>
 __device__ __forceinline__ void dw_phase(v4f (&acc)[NTW * KTW], const uint16_t* S, int nt0, int ntS, int kt0, int ktS,
                                          int r, int h) {
+  static_assert(NA >= 1 && NA <= NTW && KA >= 1 && KA <= KTW, "live part of the block");
   const uint16_t* SZ = S;
   const uint16_t* SA = S + T * (N + PAD);
   const int q = r >> 2, p = r & 3;
@@ -342,31 +400,52 @@ __device__ __forceinline__ void dw_phase(v4f (&acc)[NTW * KTW], const uint16_t* 
   const int rl = 16 * (h >> 1) + 8 * (h & 1) + 2 * q;
 #pragma unroll
   for (int ts = 0; ts < T / 32; ++ts) {
-    v8bf fa[NTW], fb[KTW];
+    v8bf fa[NA], fb[KA];
 #pragma unroll
-    for (int i = 0; i < NTW; ++i) {
+    for (int i = 0; i < NA; ++i) {
       const uint16_t* pa = SZ + (32 * ts + rl) * (N + PAD) + 16 * (nt0 + i * ntS) + 4 * p;
       fa[i] = cat8(tr_read(pa), tr_read(pa + (N + PAD)));
     }
 #pragma unroll
-    for (int j = 0; j < KTW; ++j) {
+    for (int j = 0; j < KA; ++j) {
       const uint16_t* pb = SA + (32 * ts + rl) * (K + PAD) + 16 * (kt0 + j * ktS) + 4 * p;
       fb[j] = cat8(tr_read(pb), tr_read(pb + (K + PAD)));
     }
 #pragma unroll
-    for (int i = 0; i < NTW; ++i)
+    for (int i = 0; i < NA; ++i)
 #pragma unroll
-      for (int j = 0; j < KTW; ++j) acc[i * KTW + j] = mfma(fa[i], fb[j], acc[i * KTW + j]);
+      for (int j = 0; j < KA; ++j) acc[i * KTW + j] = mfma(fa[i], fb[j], acc[i * KTW + j]);
   }
 }
 
+// The same for a wave whose live part of the block is one of two sizes per axis (wave-uniform selectors: the
+// ragged edge of a layer's live tiles): NA0 / KA0 where the selector is false, NA1 / KA1 where it is true.
+template <int K, int N, int NTW, int KTW, int NA0, int NA1, int KA0, int KA1>
+__device__ __forceinline__ void dw_phase_sel(v4f (&acc)[NTW * KTW], const uint16_t* S, int nt0, int kt0, bool nsel,
+                                             bool ksel, int r, int h) {
+  const bool n1 = NA0 != NA1 && nsel, k1 = KA0 != KA1 && ksel;
+  if (!n1) {
+    if (!k1) dw_phase<K, N, NTW, KTW, NA0, KA0>(acc, S, nt0, 1, kt0, 1, r, h);
+    else dw_phase<K, N, NTW, KTW, NA0, KA1>(acc, S, nt0, 1, kt0, 1, r, h);
+  } else {
+    if (!k1) dw_phase<K, N, NTW, KTW, NA1, KA0>(acc, S, nt0, 1, kt0, 1, r, h);
+    else dw_phase<K, N, NTW, KTW, NA1, KA1>(acc, S, nt0, 1, kt0, 1, r, h);
+  }
+}
+
+// slab positions of the wave's block: tiles (nt0 + i, kt0 + j), i < na, j < ka; -1 (never stored) for the slots
+// of the block the wave does not own
 template <int K, int NTW, int KTW>
-__device__ __forceinline__ void load_ct(int (&ct)[NTW * KTW], int tbase, int nt0, int ntS, int kt0, int ktS,
+__device__ __forceinline__ void load_ct(int (&ct)[NTW * KTW], int tbase, int nt0, int na, int kt0, int ka,
                                         const int* __restrict__ tmap) {
 #pragma unroll
   for (int i = 0; i < NTW; ++i)
 #pragma unroll
-    for (int j = 0; j < KTW; ++j) ct[i * KTW + j] = tmap[tbase + (nt0 + i * ntS) * (K / 16) + kt0 + j * ktS];
+    for (int j = 0; j < KTW; ++j) {
+      const bool own = i < na && j < ka;
+      const int v = tmap[own ? tbase + (nt0 + i) * (K / 16) + kt0 + j : 0];
+      ct[i * KTW + j] = own ? v : -1;
+    }
 }
 
 
@@ -669,16 +748,27 @@ __global__ __launch_bounds__(64 * (T / (16 * TBN)), 1) void wdc_fused(const uint
   const float qinv = 1.f / qscale;
   const float qmax = 1073741824.f / (float)(max(my_iters, 1) * T);
 
-  // dW tile ownership (wave w); 4 waves: L1 nt {2w, 2w+1} x kt 0 (kt 1 holds only padding columns);
-  // L2 nt 0..5 x kt {2w, 2w+1}; L3 nt w x kt 0..5; L4 nt w x kt 0..3; L5 nt 0 x kt w.
-  // 8 waves: L1 nt w x kt 0; L2 nt 3(w%2)..+2 x kt 2(w/2)..+1 (3 x 2 blocks: 5 operand fragments per k-step
-  // instead of 7 for 6 x 1); L3 nt w%4 x kt 3(w/4)..+2; L4 nt w%4 x kt 2(w/4)..+1; L5 nt 0 x kt w (waves 0..3)
+  // dW tile ownership (wave w). Only the live tiles (DN_l natural n tiles x KT_l C-order k tiles: 7x1, 5x7, 3x5,
+  // 3x4, 1x3 = 72) are owned at all. 4 waves: L1 nt {2w, 2w+1} < 7 x kt 0; L2 nt 0..4 x kt {2w, 2w+1} < 7; L3 nt w
+  // x kt 0..4, L4 nt w x kt 0..3 and L5 nt 0 x kt w on waves 0..2.
+  // 8 waves, rebalanced over the live tiles (all waves share one LDS pipe: fewer operand fragments per k-step,
+  // 93 instead of 120 over the five layers): L1 nt w, waves 0..6; L2 {3, 2} n x {2, 2, 2, 1} k blocks: nt 3(w%2)..,
+  // kt 2(w/2)..; L3 nt w%3 x kt {0..2 | 3, 4} and L4 nt w%3 x kt 2(w/3)..+1 on waves 0..5; L5 kt w on waves 0..2.
+  // Every tile has one fixed owner and accumulates its k-steps in order, so the sums do not depend on the split.
   constexpr bool W4 = NWAVE == 4;  // 4-wave shapes (TBN 2 at T 128, TBN 1 at T 64) share one tile ownership
   static_assert(NWAVE == 4 || NWAVE == 8, "waves");
-  constexpr int O1N = W4 ? 2 : 1, O2N = W4 ? 6 : 3, O2K = 2, O3K = W4 ? 6 : 3, O4K = W4 ? 4 : 2;
+  static_assert(DN1 == 7 && DN2 == 5 && KT2 == 7 && DN3 == 3 && KT3 == 5 && DN4 == 3 && KT4 == 4 && DN5 == 1 &&
+                KT5 == 3 && KT1 == 1, "the ownership below is written for these live tiles");
+  constexpr int O1N = W4 ? 2 : 1, O2N = W4 ? DN2 : 3, O2K = 2, O3K = W4 ? KT3 : 3, O4K = W4 ? KT4 : 2;
+  const int wu = __builtin_amdgcn_readfirstlane(w);  // the ownership branches are wave-uniform: scalar
   const int n1 = W4 ? 2 * w : w, n2 = W4 ? 0 : 3 * (w & 1), k2 = W4 ? 2 * w : 2 * (w >> 1),
-            n3 = w & 3, k3 = W4 ? 0 : 3 * (w >> 2), n4 = w & 3, k4 = W4 ? 0 : 2 * (w >> 2);
-  const bool l5 = w < 4;
+            n3 = W4 ? w : w % 3, k3 = W4 ? 0 : 3 * (w / 3), n4 = W4 ? w : w % 3, k4 = W4 ? 0 : 2 * (w / 3);
+  // live part of the wave's block per layer (0: the wave owns nothing of that layer)
+  const int na1 = W4 ? (wu < 3 ? 2 : 1) : (wu < DN1 ? 1 : 0);
+  const int na2 = W4 ? DN2 : ((wu & 1) ? 2 : 3), ka2 = (W4 ? wu : wu >> 1) < 3 ? 2 : 1;
+  const int na3 = W4 ? (wu < DN3 ? 1 : 0) : (wu < 6 ? 1 : 0), ka3 = W4 ? KT3 : (wu < 3 ? 3 : 2);
+  const int na4 = W4 ? (wu < DN4 ? 1 : 0) : (wu < 6 ? 1 : 0), ka4 = W4 ? KT4 : 2;
+  const bool l5 = wu < KT5;
   v4f acc1[O1N], acc2[O2N * O2K], acc3[O3K], acc4[O4K], acc5[1];
   int ct1[O1N], ct2[O2N * O2K], ct3[O3K], ct4[O4K], ct5[1];
   if (TRAIN) {
@@ -691,12 +781,11 @@ __global__ __launch_bounds__(64 * (T / (16 * TBN)), 1) void wdc_fused(const uint
 #pragma unroll
     for (int i = 0; i < O4K; ++i) acc4[i] = kZero4;
     acc5[0] = kZero4;
-    load_ct<K1, O1N, 1>(ct1, TB1, n1, 1, 0, 0, tmap);
-    load_ct<K2, O2N, O2K>(ct2, TB2, n2, 1, k2, 1, tmap);
-    load_ct<K3, 1, O3K>(ct3, TB3, n3, 0, k3, 1, tmap);
-    load_ct<K4, 1, O4K>(ct4, TB4, n4, 0, k4, 1, tmap);
-    load_ct<K5, 1, 1>(ct5, TB5, 0, 0, w & 3, 0, tmap);
-    if (!l5) ct5[0] = -1;
+    load_ct<K1, O1N, 1>(ct1, TB1, n1, na1, 0, 1, tmap);
+    load_ct<K2, O2N, O2K>(ct2, TB2, n2, na2, k2, ka2, tmap);
+    load_ct<K3, 1, O3K>(ct3, TB3, n3, na3, k3, ka3, tmap);
+    load_ct<K4, 1, O4K>(ct4, TB4, n4, na4, k4, ka4, tmap);
+    load_ct<K5, 1, 1>(ct5, TB5, 0, 1, w & 3, l5 ? 1 : 0, tmap);
   }
   float loss_sum = 0.f, dl_sum = 0.f;
   // the column block whose wide part / loss this lane computes (lanes h < TBN own one each)
@@ -777,27 +866,27 @@ __global__ __launch_bounds__(64 * (T / (16 * TBN)), 1) void wdc_fused(const uint
     }
     v8bf a1[TBN][N1 / 32], a2[TBN][N2 / 32], a3[TBN][N3 / 32], a4[TBN][N4 / 32];
     v4f z5[TBN][1];
-    {
-      v4f acc[TBN][N1 / 16];
-      fwd<K1, N1, TBN>(lds + PW1, a0, acc, r, h);
-      relu_pack<N1, TBN>(acc, a1);
+    {  // (live n tiles only: FN_l of N_l / 16)
+      v4f acc[TBN][FN1];
+      fwd<K1, FN1, TBN>(lds + PW1, a0, acc, r, h);
+      relu_pack<N1, FN1, TBN>(acc, a1);
     }
     {
-      v4f acc[TBN][N2 / 16];
-      fwd<K2, N2, TBN>(lds + PW2, a1, acc, r, h);
-      relu_pack<N2, TBN>(acc, a2);
+      v4f acc[TBN][FN2];
+      fwd<K2, FN2, TBN>(lds + PW2, a1, acc, r, h);
+      relu_pack<N2, FN2, TBN>(acc, a2);
     }
     {
-      v4f acc[TBN][N3 / 16];
-      fwd<K3, N3, TBN>(lds + PW3, a2, acc, r, h);
-      relu_pack<N3, TBN>(acc, a3);
+      v4f acc[TBN][FN3];
+      fwd<K3, FN3, TBN>(lds + PW3, a2, acc, r, h);
+      relu_pack<N3, FN3, TBN>(acc, a3);
     }
     {
-      v4f acc[TBN][N4 / 16];
-      fwd<K4, N4, TBN>(lds + PW4, a3, acc, r, h);
-      relu_pack<N4, TBN>(acc, a4);
+      v4f acc[TBN][FN4];
+      fwd<K4, FN4, TBN>(lds + PW4, a3, acc, r, h);
+      relu_pack<N4, FN4, TBN>(acc, a4);
     }
-    fwd<K5, N5, TBN>(lds + PW5, a4, z5, r, h);
+    fwd<K5, FN5, TBN>(lds + PW5, a4, z5, r, h);
 
     STAMP(3);
     // ---- logit = deep (row 0 of the layer-5 tile: lane (r, h = 0)) + wide; loss and dlogit
@@ -866,6 +955,11 @@ __global__ __launch_bounds__(64 * (T / (16 * TBN)), 1) void wdc_fused(const uint
       v4f g[TBN][K5 / 16];
 #pragma unroll
       for (int kt = 0; kt < K5 / 16; ++kt) {
+        if (kt >= KT5) {  // padding columns of W5: mask_grad gives zero without reading g
+#pragma unroll
+          for (int tb = 0; tb < TBN; ++tb) g[tb][kt] = kZero4;
+          continue;
+        }
         const uint2 wv2 = *(const uint2*)(lds + PW5 + 16 * kt + 4 * h);  // W5 row 0 (the logit row; X(0) = 0)
         const float w5[4] = {__uint_as_float(wv2.x << 16), __uint_as_float(wv2.x & 0xffff0000u),
                              __uint_as_float(wv2.y << 16), __uint_as_float(wv2.y & 0xffff0000u)};
@@ -874,11 +968,11 @@ __global__ __launch_bounds__(64 * (T / (16 * TBN)), 1) void wdc_fused(const uint
 #pragma unroll
           for (int e = 0; e < 4; ++e) g[tb][kt][e] = w5[e] * dlb[tb];
       }
-      mask_grad<K5, TBN>(g, S5 + T * (N5 + PAD), w, r, h, dz4);
+      mask_grad<K5, KT5, TBN>(g, S5 + T * (N5 + PAD), w, r, h, dz4);
     }
     block_sync_lds();
     STAMP(6);
-    if (l5) dw_phase<K5, N5, 1, 1>(acc5, S5, 0, 0, w & 3, 0, r, h);
+    if (l5) dw_phase<K5, N5, 1, 1>(acc5, S5, 0, 0, w & 3, 0, r, h);  // (waves 0..2: the live k tiles)
     WDC_EMIT(1, acc5, ct5);
     block_sync_lds();
 
@@ -890,12 +984,12 @@ __global__ __launch_bounds__(64 * (T / (16 * TBN)), 1) void wdc_fused(const uint
     v4bf dz3[TBN][K4 / 16];
     {
       v4f g[TBN][K4 / 16];
-      bwd_dA<K4, N4, TBN>(lds + PW4, dz4, g, r, h);
-      mask_grad<K4, TBN>(g, S4 + T * (N4 + PAD), w, r, h, dz3);
+      bwd_dA<K4, N4, KT4, KT5, TBN>(lds + PW4, dz4, g, r, h);
+      mask_grad<K4, KT4, TBN>(g, S4 + T * (N4 + PAD), w, r, h, dz3);
     }
     block_sync_lds();
     STAMP(8);
-    dw_phase<K4, N4, 1, O4K>(acc4, S4, n4, 0, k4, 1, r, h);
+    if (na4) dw_phase<K4, N4, 1, O4K>(acc4, S4, n4, 0, k4, 1, r, h);
     WDC_EMIT(O4K, acc4, ct4);
     block_sync_lds();  // (T = 256: W4, W5, W1 and layer 4's stage are dead from here)
 
@@ -905,12 +999,12 @@ __global__ __launch_bounds__(64 * (T / (16 * TBN)), 1) void wdc_fused(const uint
     v4bf dz2[TBN][K3 / 16];
     {  // (before the barrier, as in layer 4)
       v4f g[TBN][K3 / 16];
-      bwd_dA<K3, N3, TBN>(lds + PW3, dz3, g, r, h);
-      mask_grad<K3, TBN>(g, S3 + T * (N3 + PAD), w, r, h, dz2);
+      bwd_dA<K3, N3, KT3, KT4, TBN>(lds + PW3, dz3, g, r, h);
+      mask_grad<K3, KT3, TBN>(g, S3 + T * (N3 + PAD), w, r, h, dz2);
     }
     block_sync_lds();
     STAMP(10);
-    dw_phase<K3, N3, 1, O3K>(acc3, S3, n3, 0, k3, 1, r, h);
+    if (na3) dw_phase_sel<K3, N3, 1, O3K, 1, 1, O3K, W4 ? O3K : 2>(acc3, S3, n3, k3, false, ka3 != O3K, r, h);
     WDC_EMIT(O3K, acc3, ct3);
     block_sync_lds();  // (T = 256: W3 and layer 3's stage are dead from here)
 
@@ -920,12 +1014,12 @@ __global__ __launch_bounds__(64 * (T / (16 * TBN)), 1) void wdc_fused(const uint
     v4bf dz1[TBN][K2 / 16];
     {  // (before the barrier, as in layer 4)
       v4f g[TBN][K2 / 16];
-      bwd_dA<K2, N2, TBN>(lds + PW2, dz2, g, r, h);
-      mask_grad<K2, TBN>(g, S2 + T * (N2 + PAD), w, r, h, dz1);
+      bwd_dA<K2, N2, KT2, KT3, TBN>(lds + PW2, dz2, g, r, h);
+      mask_grad<K2, KT2, TBN>(g, S2 + T * (N2 + PAD), w, r, h, dz1);
     }
     block_sync_lds();
     STAMP(12);
-    dw_phase<K2, N2, O2N, O2K>(acc2, S2, n2, 1, k2, 1, r, h);
+    dw_phase_sel<K2, N2, O2N, O2K, O2N, W4 ? O2N : 2, O2K, 1>(acc2, S2, n2, k2, na2 != O2N, ka2 != O2K, r, h);
     WDC_EMIT(O2N * O2K, acc2, ct2);
     block_sync_lds();
 
@@ -934,7 +1028,7 @@ __global__ __launch_bounds__(64 * (T / (16 * TBN)), 1) void wdc_fused(const uint
     stage<K1, N1, TBN>(S1, dz1, a0, w, r, h);
     block_sync_lds();
     STAMP(14);
-    dw_phase<K1, N1, O1N, 1>(acc1, S1, n1, 1, 0, 0, r, h);
+    if (na1) dw_phase_sel<K1, N1, O1N, 1, O1N, 1, 1, 1>(acc1, S1, n1, 0, na1 != O1N, false, r, h);
     WDC_EMIT(O1N, acc1, ct1);
     if constexpr (PERSIST) {  // the whole DNN update of this lane's columns (see opt_tiles)
       constexpr int NA = O1N + O2N * O2K + O3K + O4K + 1;
@@ -963,6 +1057,7 @@ __global__ __launch_bounds__(64 * (T / (16 * TBN)), 1) void wdc_fused(const uint
     dl_sum += __shfl_xor(dl_sum, o);
   }
   __syncthreads();  // last dW reads done; red/wgrad final
+  STAMP(18);  // (stamp builds: the epilogue split -- 16 -> 18 wave reduction + this barrier)
   if (lane == 0) {
     red[w] = loss_sum;
     red[NWAVE + w] = dl_sum;
@@ -1004,6 +1099,7 @@ __global__ __launch_bounds__(64 * (T / (16 * TBN)), 1) void wdc_fused(const uint
       slab_store(my4 + c4, v4f{v.x, v.y, v.z, v.w});
     }
   }
+  STAMP(19);  // (18 -> 19: second barrier + the histogram's slab stores issued; 19 -> 17: the loss sum)
   if (tid == 0 && slab_loss) {
     float l = 0.f;
 #pragma unroll
@@ -1167,9 +1263,11 @@ void launch(dim3 grid, hipStream_t stream, const void* data, long long n_data, l
 
 extern "C" {
 
-// T, LWEND (weight image elements), LDS_BYTES, WPAD (weight-image row pad), NTILE, WIDE_PAD
+// T, LWEND (weight image elements), LDS_BYTES, WPAD (weight-image row pad), NTILE, WIDE_PAD, LW1..LW5, then the
+// live tile counts the kernel is compiled for, per layer: forward n tiles, dW n tiles, C-order k tiles
 int WDC_SYM(mifx_wdc_constants)(int* out, int n) {
-  const int v[] = {T, LWEND, LDS_BYTES, WPAD, NTILE, WIDE_PAD, LW1, LW2, LW3, LW4, LW5};
+  const int v[] = {T,   LWEND, LDS_BYTES, WPAD, NTILE, WIDE_PAD, LW1, LW2, LW3, LW4, LW5, FN1, FN2,
+                   FN3, FN4,   FN5,       DN1,  DN2,   DN3,      DN4, DN5, KT1, KT2, KT3, KT4, KT5};
   const int m = (int)(sizeof(v) / sizeof(int));
   for (int i = 0; i < n && i < m; ++i) out[i] = v[i];
   return m;

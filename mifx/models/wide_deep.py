@@ -317,8 +317,11 @@ def tensors_to_records(dense, ids, label) -> np.ndarray:
 # 16 (E // 4) + 4 H + E % 4. Its LDS weight image W_l^T [N][K] therefore has natural rows and C-ordered
 # columns. Image row n sits at physical row wperm(n) (bit 4 of n flips bit 2) and rows are padded by CHAIN_PAD
 # elements (the kernel's WPAD) -- together conflict-free LDS reads (see the kernel's wperm note). dW tiles come
-# out with C-order k columns and, for layers 1-4, an n axis in "C o C" order: the kernel stages the dZ fragments
-# it holds (C positions of the layer above's k axis) as 16-byte pairs, which applies chain_perm once more.
+# out with C-order k columns and NATURAL n tiles: the kernel stages the 16-byte dZ pair a lane (h) holds for C
+# positions 32 m + 8 h at staged column 32 m + 8 (2 (h & 1) + (h >> 1)), so staged 16-column tile j holds exactly
+# the features 16 j .. 16 j + 15 (inner order 0-3, 8-11, 4-7, 12-15: chain_dw_rows). Padding therefore fills whole
+# trailing tiles on both axes: a layer's live dW tiles are (natural n tiles of its real rows) x (C-order k tiles of
+# its real columns + the bias column), which the kernel skips at compile time (chain_live_tiles).
 CHAIN_PAD = 16
 CHAIN_LW = [int(v) for v in np.cumsum([0] + [n * (k + CHAIN_PAD) for k, n in LAYER_KN])[:-1]]
 CHAIN_LWEND = sum(n * (k + CHAIN_PAD) for k, n in LAYER_KN)  # 33536
@@ -340,8 +343,23 @@ def chain_dw_rows(li: int) -> np.ndarray:
     N = LAYER_KN[li][1]
     if li == len(LAYER_KN) - 1:
         return np.arange(N)  # dZ5 is staged in natural order
-    c = chain_perm(N)
-    return c[c]
+    j = np.arange(N)
+    return 16 * (j // 16) + 8 * ((j % 8) // 4) + 4 * ((j % 16) // 8) + j % 4
+
+
+def chain_live_tiles(cfg: WideDeepConfig | None = None) -> list[tuple[int, int, int]]:
+    """Per layer (forward n tiles, dW n tiles, C-order k tiles) that hold anything but padding: the counts the
+    chained kernel is compiled for (its constants() exports them; ops.wd_chain.check_live_tiles compares).
+    Forward rows include the constant-1 row that feeds the next layer's bias column; C-order k tile 2 s + b holds
+    the features 32 s + 8 b + {0..7, 16..23}, so the live k tiles are a prefix too."""
+    cfg = cfg or WideDeepConfig()
+    out = []
+    for li, ((K, N), (kr, nr)) in enumerate(zip(LAYER_KN, _real_dims(cfg))):
+        last = li == len(LAYER_KN) - 1
+        fn = -(-(nr if last else nr + 1) // 16)
+        kt = sum(1 for t in range(K // 16) if 32 * (t // 2) + 8 * (t % 2) < kr + 1)
+        out.append((fn, -(-nr // 16), kt))
+    return out
 
 
 def chain_image_offsets(li: int) -> np.ndarray:

@@ -69,12 +69,41 @@ def fns_for(tile: int) -> dict:
     return {128: _fns, 64: _fns64, 256: _fns256}[tile]()
 
 
+_CONST_NAMES = ["T", "LWEND", "LDS_BYTES", "PAD", "NTILE", "WIDE_PAD", "LW1", "LW2", "LW3", "LW4", "LW5"] + \
+    [f"{p}{l}" for p in ("FN", "DN", "KT") for l in range(1, 6)]
+
+
 @functools.lru_cache(maxsize=None)
-def constants() -> dict[str, int]:
-    buf = (ctypes.c_int * 16)()
-    n = _fns()["constants"](buf, 16)
-    names = ["T", "LWEND", "LDS_BYTES", "PAD", "NTILE", "WIDE_PAD", "LW1", "LW2", "LW3", "LW4", "LW5"]
-    return {k: buf[i] for i, k in enumerate(names[:n])}
+def constants(tile: int = 128) -> dict[str, int]:
+    """Compile-time constants of the T = tile build. FN / DN / KT 1..5: the live tiles per layer it is compiled for
+    (forward n tiles, dW n tiles, C-order k tiles); everything else is padding it never computes."""
+    buf = (ctypes.c_int * 32)()
+    n = fns_for(tile)["constants"](buf, 32)
+    if n != len(_CONST_NAMES):
+        raise RuntimeError(f"chained W&D kernel (T = {tile}) exports {n} constants, expected {len(_CONST_NAMES)}")
+    return {k: buf[i] for i, k in enumerate(_CONST_NAMES)}
+
+
+def check_live_tiles(cfg, tmap, tile: int) -> None:
+    """Refuse a model / tile map the T = tile build was not compiled for. The kernel skips every tile outside its
+    compile-time live counts, so zero padding is not enough: the model's live tiles (models.wide_deep
+    .chain_live_tiles) and the live dW tiles of the slab's tile map (chain_maps) must be exactly the kernel's."""
+    import numpy as np
+
+    from ..models import wide_deep as wdm
+
+    c = constants(tile)
+    tmap = np.asarray(tmap.cpu() if torch.is_tensor(tmap) else tmap)
+    for li, ((K, N), (fn, dn, kt)) in enumerate(zip(wdm.LAYER_KN, wdm.chain_live_tiles(cfg))):
+        kern = (c[f"FN{li + 1}"], c[f"DN{li + 1}"], c[f"KT{li + 1}"])
+        if kern != (fn, dn, kt):
+            raise ValueError(f"chained W&D kernel (T = {tile}) is compiled for {kern} live (forward n, dW n, k) tiles "
+                             f"in layer {li + 1}; the model has {(fn, dn, kt)}")
+        live = tmap[wdm.TILE_BASE[li]:wdm.TILE_BASE[li] + (N // 16) * (K // 16)].reshape(N // 16, K // 16) >= 0
+        want = (np.arange(N // 16)[:, None] < kern[1]) & (np.arange(K // 16)[None, :] < kern[2])
+        if not np.array_equal(live, want):
+            raise ValueError(f"the tile map's live dW tiles of layer {li + 1} are not the {kern[1]} x {kern[2]} the "
+                             f"chained W&D kernel (T = {tile}) computes")
 
 
 def fused(records: torch.Tensor, n_data: int, batch: int, start_fixed: int, step_ctr: torch.Tensor | None,

@@ -210,6 +210,11 @@ class FusedWideDeepTrainer:
                                                   and not self._persist and self._ktail is None) else 128
         if self.tile == 64:
             self.waves = 4
+        if kernel == "chain":  # the builds this trainer launches (training: its tile; eval / predict: T = 128)
+            from ..ops import wd_chain as wdc
+
+            for t in sorted({128, self.tile}):
+                wdc.check_live_tiles(self.model.cfg, tmap, t)
         # one launch per step when ONE workgroup trains the batch (opt-in: one_launch=True or MIFX_WD_ONE_LAUNCH=1;
         # grid 1, one rank): the optimizer runs in extra workgroups of the fused launch, which load their columns'
         # state during the step and update once workgroup 0 has published the gradient row (csrc/wd_chain.hip

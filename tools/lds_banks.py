@@ -339,3 +339,56 @@ def perm2_report():
 
 if __name__ == "__main__" and __import__("sys").argv[1:] == ["perm2"]:
     perm2_report()
+
+
+def stage_writes_nat(LZ, LA, K, N, epw=16):
+    """dZ staged with natural 16-column tiles: the 16-byte pair of lane group h (C positions 32 m + 8 h) goes to
+    column 32 m + 8 (2 (h & 1) + (h >> 1)) -- csrc/wd_chain.hip stage(). A side as stage_writes_c."""
+    outz = []
+    for m in range(N // 32):
+        a = [LZ.addr(epw * 0 + (l & 15), 32 * m + 8 * (2 * ((l >> 4) & 1) + (l >> 5))) for l in range(64)]
+        outz.append(cycles(a, "w128"))
+    return outz, stage_writes_c(LZ, LA, K, N, epw)[1]
+
+
+# live tiles per layer (csrc/wd_chain.hip FN / DN / KT): forward n tiles, dW n tiles, C-order k tiles
+LIVE = [(7, 7, 1), (5, 5, 7), (4, 3, 5), (3, 3, 4), (1, 1, 3)]
+
+
+def nat_report():
+    """The kernel as built: weights pad 16 + wperm, staging pad 8 + sperm2, dZ staged in natural tiles, and only
+    the live tiles read (fwd: FN n tiles; dA: KT k tiles x the k-steps holding a live dZ tile; dW: DN + KT tiles;
+    mask: KT tiles). The stage writes full rows."""
+    wl = lambda K: PermLayout(K, 16, wperm)  # noqa: E731
+    sl = lambda c: PermLayout(c, 8, sperm2)  # noqa: E731
+    tot = defaultdict(lambda: [0, 0])
+
+    def add(key, cyc, ideal_each):
+        tot[key][0] += sum(cyc)
+        tot[key][1] += ideal_each * len(cyc)
+
+    for li, ((K, N), (fn, dn, kt)) in enumerate(zip(LAYERS, LIVE)):
+        ks = K // 32
+        add("fwd b128", fwd_read(wl(K), K, N)[:fn * ks], 4)
+        if li > 0 and N >= 32:
+            ns_live = (LIVE[li + 1][2] + 1) // 2  # k-steps of the dA product with a live dZ tile
+            d = dA_read(wl(K), K, N)  # ordered s, kt, (first, second)
+            kt_all = K // 16
+            add("dA tr", [d[(s * kt_all + t) * 2 + i] for s in range(ns_live) for t in range(kt) for i in (0, 1)], 2)
+        if N >= 16:
+            dz = dw_read(sl(N), N)  # ordered ts, tile, (first, second)
+            add("dW tr", [dz[(ts * (N // 16) + t) * 2 + i] for ts in range(4) for t in range(dn) for i in (0, 1)], 2)
+        da = dw_read(sl(K), K)
+        add("dW tr", [da[(ts * (K // 16) + t) * 2 + i] for ts in range(4) for t in range(kt) for i in (0, 1)], 2)
+        if N >= 32:
+            z, a = stage_writes_nat(sl(N), sl(K), K, N)
+            add("stage dZ w128", z, 8)
+            add("stage A w128", a, 8)
+        add("mask b64", mask_read(sl(K), K)[:kt], 2)
+    print("== weights pad 16 + wperm; staging pad 8 + sperm2, dZ in natural tiles (16-B writes), live tiles only")
+    for k, (c, ideal) in tot.items():
+        print(f"   {k:>14}: {c:6d} cycles (ideal {ideal:6d}, x{c / ideal:.2f})")
+
+
+if __name__ == "__main__" and __import__("sys").argv[1:] == ["nat"]:
+    nat_report()

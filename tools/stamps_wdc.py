@@ -56,6 +56,9 @@ for NW, batch, big in CFGS:
         d = [st[w][i] - st[w][i - 1] for w in range(NW)]
         nm = (NAMES256 if big else NAMES)[i]
         print(f"  {nm:>12}: " + " ".join(f"{x:8d}" for x in d))
+    # the epilogue split (stamps 18, 19 sit between 16 and 17)
+    for nm, a, b in (("epi:reduce+B", 16, 18), ("epi:B+hist", 18, 19), ("epi:loss", 19, 17)):
+        print(f"  {nm:>12}: " + " ".join(f"{st[w][b] - st[w][a]:8d}" for w in range(NW)))
     print(f"  iteration (stamp 2 -> 15), wave 0: {st[0][15] - st[0][2]}; kernel (0 -> 17): {st[0][17] - st[0][0]}")
 
 # per-block global clock (100 MHz) of the last launch (the 8-wave B=65536 trainer above): dispatch stagger and
