@@ -213,6 +213,11 @@ def run_bert_rank(spec: dict) -> dict:
                   os.path.join(exp, "variables.safetensors"))
         with open(os.path.join(exp, "config.json"), "w") as f:
             json.dump({k: getattr(cfg, k) for k in _CFG_KEYS} | {"seq_len": S, "model": "bert_seq_cls"}, f)
+        # the same directory as a mifx.saved_model/v1 export (family bert_seq_cls): saved_model.load(), Pusher and the
+        # model server take it; variables.safetensors / config.json above stay for load_bert_export
+        from ..serving.saved_model import save_bert
+
+        save_bert(exp, full, cfg, S)
         res["export"] = exp
     return res
 

@@ -194,6 +194,10 @@ def _tensor_info(spec) -> object:
             ti.tensor_shape.dim.add(size=int(d))
     elif isinstance(spec, dict) and spec.get("dtype") in ("string", "str"):
         ti.dtype = DT["string"]
+    elif isinstance(spec, dict) and spec.get("dtype") in DT:  # e.g. bert_seq_cls: int32 [-1, -1] token ids
+        ti.dtype = DT[spec["dtype"]]
+        for d in spec.get("shape") or []:
+            ti.tensor_shape.dim.add(size=int(d))
     return ti
 
 
@@ -237,6 +241,8 @@ class PredictionServicer:
         try:
             if s.model.family == "wide_deep":
                 out = s.predict({k: v.reshape(-1) for k, v in inputs.items()})  # columns
+            elif s.model.family == "bert_seq_cls":  # columnar [N, S] ids + attention mask (lengths from the mask)
+                out = s.predict(inputs)
             else:
                 if len(inputs) != 1:
                     raise ValueError(f"this signature takes one input tensor, got {sorted(inputs)}")

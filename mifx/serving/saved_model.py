@@ -8,7 +8,9 @@ Layout (mirrors TF's `<export_dir_base>/<timestamp>/` versioned exports consumed
     <dir>/assets/transform/...        copy of the Transform graph (serving/eval receivers)
 
 Families: ``wide_deep`` (taxi W&D; raw-example receiver through the Transform graph, classify
-outputs) and ``module`` (any torch.nn.Module given by ``module_class`` + config, tensor inputs).
+outputs), ``module`` (any torch.nn.Module given by ``module_class`` + config, tensor inputs) and ``bert_seq_cls``
+(the fine-tuned BERT classifier; ragged token-id inputs, served by the packed variable-length forward of
+mifx.models.bert_infer).
 """
 from __future__ import annotations
 
@@ -58,6 +60,26 @@ def save_module(path: str, model: torch.nn.Module, module_class: str, config: di
             "signatures": {"serving_default": {"method": "predict", "inputs": {"input": input_shape},
                                                "outputs": ["scores"], "class_names": class_names}}}
     _write(path, meta, model.state_dict())
+    return path
+
+
+_BERT_CFG = ("vocab_size", "hidden", "layers", "heads", "intermediate", "max_position", "type_vocab", "num_labels",
+             "ln_eps")
+
+
+def save_bert(path: str, state: dict, cfg, seq_len: int, class_names: list | None = None) -> str:
+    """Family ``bert_seq_cls``: the TP=1 state of mifx.models.bert.BertForSequenceClassification (fp32) and its
+    config. The family is built in (mifx.models.bert_infer.BertInference): the export names no class to import.
+    seq_len: the length the model was fine-tuned at (requests may have any length up to min(max_position, 512))."""
+    meta = {"format": FORMAT, "family": "bert_seq_cls",
+            "model_config": {k: getattr(cfg, k) for k in _BERT_CFG}, "seq_len": int(seq_len),
+            "signatures": {"serving_default": {
+                "method": "classify",
+                "inputs": {"input_ids": {"dtype": "int32", "shape": [-1, -1]},
+                           "token_type_ids": {"dtype": "int32", "shape": [-1, -1], "optional": True}},
+                "outputs": ["logits", "probabilities", "class_ids", "classes"],
+                "class_names": None if class_names is None else [str(c) for c in class_names]}}}
+    _write(path, meta, {k: v.detach().float() for k, v in state.items()})
     return path
 
 
@@ -120,9 +142,17 @@ class LoadedModel:
         sd = load_file(os.path.join(path, "variables", "variables.safetensors"))
         self.family = self.meta["family"]
         self.transform = None
-        if self.family not in ("wide_deep", "module"):
+        if self.family not in ("wide_deep", "module", "bert_seq_cls"):
             raise ValueError(f"{path}: unknown model family {self.family!r}")
-        if self.family == "wide_deep":
+        if self.family == "bert_seq_cls":
+            from ..models.bert import BertConfig
+            from ..models.bert_infer import BertInference
+
+            mc = self.meta.get("model_config", {})
+            if not (isinstance(mc, dict) and _json_plain(mc)):
+                raise ValueError(f"{path}: model_config must be a JSON object of plain values")
+            self.model = BertInference(sd, BertConfig(**{k: mc[k] for k in _BERT_CFG if k in mc}), self.device)
+        elif self.family == "wide_deep":
             from ..models import wide_deep as wdm
 
             mc = self.meta["model_config"]
@@ -171,8 +201,67 @@ class LoadedModel:
         with torch.no_grad():
             return self.model(dense, ids).numpy()
 
+    # ------------------------------------------------------------------ BERT sequence classification
+    def bert_sequences(self, instances):
+        """(token-id lists, token-type lists or None) of a request, validated. Row format: a list of
+        {"input_ids": [...], "token_type_ids": [...]?} of any lengths (a bare id list is taken as input_ids).
+        Columnar: {"input_ids": [N, S], "attention_mask": [N, S]?, "token_type_ids": [N, S]?}; the lengths come from
+        the mask, which must be a prefix of ones (without a mask every row has S tokens)."""
+        from ..models.bert_infer import validate
+
+        if isinstance(instances, dict):
+            if "input_ids" not in instances:
+                raise ValueError("inputs need 'input_ids'")
+            ids = np.asarray(instances["input_ids"])
+            if ids.ndim != 2:
+                raise ValueError(f"columnar input_ids must be [N, S], got shape {ids.shape}")
+            am = instances.get("attention_mask")
+            if am is None:
+                lens = np.full(len(ids), ids.shape[1], np.int64)
+            else:
+                am = np.asarray(am)
+                if am.shape != ids.shape:
+                    raise ValueError(f"attention_mask shape {am.shape} is not input_ids' {ids.shape}")
+                lens = (am != 0).sum(1)
+                for i, n in enumerate(lens):
+                    if not (am[i, :n] == 1).all() or (am[i, n:] != 0).any():
+                        raise ValueError(f"instance {i}: attention_mask is not a prefix of ones")
+            tt = instances.get("token_type_ids")
+            if tt is not None and np.asarray(tt).shape != ids.shape:
+                raise ValueError(f"token_type_ids shape {np.asarray(tt).shape} is not input_ids' {ids.shape}")
+            seqs = [ids[i, :n] for i, n in enumerate(lens)]
+            tts = None if tt is None else [np.asarray(tt)[i, :n] for i, n in enumerate(lens)]
+        else:
+            rows = [r if isinstance(r, dict) else {"input_ids": r} for r in instances]
+            for i, r in enumerate(rows):
+                if "input_ids" not in r:
+                    raise ValueError(f"instance {i}: no 'input_ids'")
+            seqs = [np.asarray(r["input_ids"]) for r in rows]
+            tts = [None if r.get("token_type_ids") is None else np.asarray(r["token_type_ids"]) for r in rows]
+            if all(t is None for t in tts):
+                tts = None
+        validate(seqs, tts, self.model.cfg)
+        return seqs, tts
+
+    def validate(self, instances) -> None:
+        """Raise ValueError for a request this model would refuse (before it is merged with others into a batch)."""
+        if self.family == "bert_seq_cls":
+            self.bert_sequences(instances)
+
+    def _bert_predict(self, instances) -> dict:
+        seqs, tts = self.bert_sequences(instances)
+        logits = self.model.logits(seqs, tts).cpu().numpy()  # packed by token capacity, not by instance count
+        z = logits - logits.max(-1, keepdims=True) if len(logits) else logits
+        p = np.exp(z) / np.exp(z).sum(-1, keepdims=True) if len(logits) else logits
+        ids = logits.argmax(-1).astype(np.int64) if len(logits) else np.zeros(0, np.int64)
+        names = self.signatures["serving_default"].get("class_names")
+        classes = np.array([names[i] if names else str(i) for i in ids], dtype=object).astype(str)
+        return {"logits": logits, "probabilities": p, "class_ids": ids[:, None], "classes": classes[:, None]}
+
     def predict(self, instances) -> dict:
         """instances: list of feature dicts (TF-Serving row format) or dict of columns."""
+        if self.family == "bert_seq_cls":
+            return self._bert_predict(instances)
         if self.family == "wide_deep":
             if isinstance(instances, list):
                 keys = sorted({k for r in instances for k in r})

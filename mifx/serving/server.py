@@ -94,6 +94,7 @@ class ServableVersion:
 
     def predict(self, instances) -> dict:
         if self.batcher is not None and isinstance(instances, list):
+            self.model.validate(instances)  # a bad request is refused alone, not with the batch it would be merged into
             return self.batcher.submit(instances).result()
         return self.model.predict(instances)
 
