@@ -13,7 +13,10 @@
   `custom_config` (defaults keep a constant learning rate, no clipping, decay on every parameter):
   `max_grad_norm` (global-norm clipping, TP = 1 only), `lr_schedule` ("constant" | "linear": warmup then decay
   to zero at train_args.num_steps), `warmup_proportion` (fraction of num_steps), `no_decay_bias_norm`. The
-  resolved settings are recorded in the result (`metrics.json`, key "optimizer").
+  resolved settings are recorded in the result (`metrics.json`, key "optimizer"). `packed_tokens` (TP = 1) selects
+  the packed variable-length step: the examples' lengths come from their `attention_mask`, batches of up to
+  `packed_tokens` tokens and `max_seqs` sequences (default 4 * packed_tokens // seq_len) are filled greedily in
+  example order, and the result records them under "packed".
 
 Contract mirrored from the TFX Trainer of the reference (`airflow-dags/taxi_pipeline.py:92-99`: examples in,
 ModelExportPath out, lineage in MLMD; train_args / eval_args num_steps)."""
@@ -176,17 +179,35 @@ def run_bert_rank(spec: dict) -> dict:
     torch.manual_seed(int(cc.get("seed", 0)))
     steps = int(spec["train_steps"])
     opt_cfg = resolve_optimizer_config(cc, steps)
+    C = cc.get("packed_tokens")
+    packed_kw = {}
+    if C is not None:
+        packed_kw = dict(packed_tokens=int(C), max_seqs=int(cc.get("max_seqs") or max(1, 4 * int(C) // S)), max_len=S)
     tr = BertTrainer(cfg, B, S, dev, tp, lr=opt_cfg["learning_rate"], graph=cc.get("graph"),
                      max_grad_norm=opt_cfg["max_grad_norm"], warmup_steps=opt_cfg["warmup_steps"],
-                     total_steps=opt_cfg["total_steps"], no_decay_bias_norm=opt_cfg["no_decay_bias_norm"])
+                     total_steps=opt_cfg["total_steps"], no_decay_bias_norm=opt_cfg["no_decay_bias_norm"], **packed_kw)
     T = {k: torch.from_numpy(v.astype(np.int64) if k != "attention_mask" else v.astype(np.float32))
          for k, v in tr_data.items()}
     n = len(T["labels"])
     losses = []
+    seen = 0
+    if C is not None:
+        from ..trainer.bert_trainer import plan_train_batches
+
+        lens = tr_data["attention_mask"].astype(np.int64).sum(1)
+        if int(lens.min()) < 1:
+            raise ValueError("packed_tokens: an example with an empty attention_mask")
+        batches = list(plan_train_batches(lens, packed_kw["packed_tokens"], packed_kw["max_seqs"]))
     t0 = time.time()
     for i in range(steps):
-        idx = (torch.arange(B) + i * B) % n
-        tr.set_batch(T["input_ids"][idx], T["token_type_ids"][idx], T["attention_mask"][idx], T["labels"][idx])
+        if C is not None:  # the attention mask of an example is a prefix: its first `len` tokens are the sequence
+            idx = batches[i % len(batches)]
+            tr.set_packed_batch([tr_data["input_ids"][j, :lens[j]] for j in idx],
+                                [tr_data["token_type_ids"][j, :lens[j]] for j in idx], tr_data["labels"][idx])
+        else:
+            idx = (torch.arange(B) + i * B) % n
+            tr.set_batch(T["input_ids"][idx], T["token_type_ids"][idx], T["attention_mask"][idx], T["labels"][idx])
+        seen += len(idx)
         loss = tr.step()
         if i % max(1, steps // 20) == 0 or i == steps - 1:
             losses.append(float(loss))
@@ -203,9 +224,13 @@ def run_bert_rank(spec: dict) -> dict:
         correct += int((logits.argmax(-1).cpu() == E["labels"][sl]).sum())
     full = gather_full_state(tr.model)  # collective
     res = {"eval": {"accuracy": correct / max(1, ne), "num_eval_examples": ne}, "losses": losses,
-           "train_sequences_per_sec": steps * B / max(secs, 1e-9), "tp": tp.size, "steps": steps,
+           "train_sequences_per_sec": seen / max(secs, 1e-9), "tp": tp.size, "steps": steps,
            "optimizer": dict(opt_cfg, final_lr=tr.last_lr() if steps else None,
                              final_grad_norm=tr.last_grad_norm() if steps else None)}
+    if C is not None:
+        res["packed"] = {"packed_tokens": packed_kw["packed_tokens"], "max_seqs": packed_kw["max_seqs"],
+                         "mean_sequences_per_step": seen / max(1, steps),
+                         "padded_padding_share": 1.0 - float(lens.mean()) / S}
     if tp.rank == 0:
         exp = os.path.join(spec["out_dir"], "serving_model_dir", "export", "bert", str(int(time.time() * 1000)))
         os.makedirs(exp, exist_ok=True)

@@ -131,13 +131,15 @@ class BertLayer(nn.Module):
         """Parameters applied to token shards under sequence parallelism (partial gradients per rank)."""
         return [self.ln1.weight, self.ln1.bias, self.ln2.weight, self.ln2.bias, self.attn_out.bias, self.ffn_out.bias]
 
-    def forward(self, x, mask, rng=None, site=0):
+    def forward(self, x, mask, rng=None, site=0, packed=None):
         """Dropout RNG: every mask is counter-based (model seed, step counter, site; csrc/counter_rng.h), never the
         torch generator. The hidden dropouts act on REPLICATED activations (every TP rank holds the same [B, S, H]
         tensor) and are fused with the row-parallel bias, the residual add and the LayerNorm
         (fb.bias_dropout_add_layernorm, sites `site` and `site + 1`); the attention-probability dropout indexes
         its mask by the global head (fb.attention, site 1000 + site), so both are identical for every TP split.
-        (With fused_attention=False the attention dropout is SDPA's, on the torch generator.)"""
+        (With fused_attention=False the attention dropout is SDPA's, on the torch generator.)
+        packed: None, or (cu, table, nseq, lmax) of a packed variable-length batch: x is [1, C, hidden] and the
+        attention runs per sequence (mifx.ops.attn_varlen.attention_varlen); everything else is row-wise."""
         B, S, _ = x.shape
         h, d = self.local_heads, self.head_dim
         c = self.cfg
@@ -166,7 +168,14 @@ class BertLayer(nn.Module):
             qkv = hg.linear(xin, self.qkv.weight, self.qkv.bias, slot=slot_a, tp_in=self.tp).view(B, S, 3, h, d)
         else:
             qkv = self.qkv(x).view(B, S, 3, h, d)
-        if c.fused_attention:
+        if packed is not None:
+            from ..ops.attn_varlen import attention_varlen
+
+            cu, table, nseq, lmax = packed
+            h0 = sum(self.heads_per_rank[:self.tp.rank])
+            ctx = attention_varlen(qkv.view(B * S, 3, h, d), cu, table, nseq, lmax, 1.0 / d ** 0.5, adrop, rng,
+                                   1000 + site, h0, c.heads).reshape(B, S, h * d)
+        elif c.fused_attention:
             # fused attention straight on the projection output (no q/k/v transposes); its dropout mask is keyed
             # by the GLOBAL head index, so it is identical for any TP split (site: this layer's attention)
             h0 = sum(self.heads_per_rank[:self.tp.rank])
@@ -279,6 +288,36 @@ class BertForSequenceClassification(nn.Module):
             for i, layer in enumerate(self.layers):
                 x = layer(x, mask, rng, 1 + 2 * i)
         pooled = torch.tanh(self.pooler(x[:, 0]))
+        return self.classifier(fb.dropout(pooled, drop, rng, 1 + 2 * len(self.layers)))
+
+    def forward_packed(self, ids, token_types, pos_ids, cu, table, nseq, lmax, cls_rows):
+        """The forward over a PACKED variable-length batch -> logits [max_seqs, num_labels].
+
+        ids, token_types, pos_ids: int [C] of the token capacity C (position ids restart at 0 in each sequence; the
+        rows from the T live tokens up to C carry id 0 and position 0); cu int32 [>= nseq + 1] cu_seqlens and table
+        int32 [n, 2] block table (mifx.ops.bert_infer.cu_seqlens / block_table, -1 entries skipped); lmax: an upper
+        bound of the longest sequence; cls_rows: int [max_seqs], the first row of each sequence (row 0 for an empty
+        slot, whose logits the caller ignores: label -100). The layers run on [1, C, hidden] with per-sequence
+        attention (BertLayer.forward, packed=...). Rows of no sequence are inert: attention neither reads nor writes
+        them and the pooler does not read them, so every gradient receives exact zeros from them. TP = 1 only."""
+        if self.tp.size > 1 or self.cfg.sequence_parallel:
+            raise ValueError("the packed variable-length forward needs TP = 1 without sequence parallelism")
+        drop = self.cfg.dropout if self.training else 0.0
+        rng = self.drop_rng
+        if drop > 0:
+            self.drop_rng[1:].add_(1)
+            rng = fb.rng_snapshot(self.drop_rng)
+        a = self.word(ids) + fb.embedding(pos_ids, self.pos.weight)
+        te = fb.embedding(token_types, self.tok_type.weight)
+        if a.is_cuda and a.dtype == torch.bfloat16 and te.dtype == a.dtype:
+            x = fb.add_layernorm(a, te, self.ln_emb.weight, self.ln_emb.bias, self.ln_emb.eps)
+        else:
+            x = self.ln_emb(a + te)
+        x = fb.dropout(x, drop, rng, 0)[None]
+        packed = (cu, table, nseq, lmax)
+        for i, layer in enumerate(self.layers):
+            x = layer(x, None, rng, 1 + 2 * i, packed=packed)
+        pooled = torch.tanh(self.pooler(x[0].index_select(0, cls_rows)))
         return self.classifier(fb.dropout(pooled, drop, rng, 1 + 2 * len(self.layers)))
 
 

@@ -41,6 +41,38 @@ def load_gemm_table(path: str = GEMM_TABLE) -> bool:
     return ok
 
 
+def plan_train_batches(lengths, packed_tokens: int, max_seqs: int):
+    """Greedily fill packed training batches in the given order: yields lists of indices into `lengths`, each of at
+    most `packed_tokens` tokens and `max_seqs` sequences (a batch is closed when the next sequence does not fit)."""
+    from ..models.bert_infer import plan_packs
+
+    if packed_tokens < 1 or max_seqs < 1:
+        raise ValueError(f"packed_tokens and max_seqs must be positive, got {packed_tokens}, {max_seqs}")
+    lengths = [int(L) for L in lengths]
+    for i, L in enumerate(lengths):
+        if L < 1:
+            raise ValueError(f"sequence {i}: empty")
+    for s0, s1 in plan_packs(lengths, packed_tokens, max_seqs):
+        yield list(range(s0, s1))
+
+
+def synthetic_sequences(cfg: BertConfig, n: int, lo: int, hi: int, seed: int = 0):
+    """n synthetic sequences with lengths uniform on [lo, hi] -> (token-id arrays, token-type arrays, labels)."""
+    import numpy as np
+
+    g = np.random.default_rng(seed)
+    floor = min(1000, cfg.vocab_size // 4)
+    seqs, tts = [], []
+    for L in g.integers(lo, hi + 1, size=n):
+        s = g.integers(floor, cfg.vocab_size, size=int(L)).astype(np.int64)
+        s[0] = min(101, cfg.vocab_size - 1)  # [CLS]
+        t = np.zeros(int(L), np.int64)
+        t[int(L) // 2:] = 1 if cfg.type_vocab > 1 else 0
+        seqs.append(s)
+        tts.append(t)
+    return seqs, tts, g.integers(0, cfg.num_labels, size=n).astype(np.int64)
+
+
 def synthetic_batch(cfg: BertConfig, batch: int, seq: int, device, seed: int = 0):
     """Same tokens on every TP rank (TP ranks consume one replicated batch)."""
     g = torch.Generator().manual_seed(seed)
@@ -70,18 +102,45 @@ class BertTrainer:
     optimizer path does the same on the host (two param groups, clip_grad_norm_, `group["lr"]` set before
     each eager step), so there a schedule cannot be combined with graph=True. `last_lr()` / `last_grad_norm()`
     report the last step's values. Clipping needs TP = 1 (the global norm over sharded plus replicated
-    parameters needs a cross-rank reduction); the schedule and the no-decay set work at any TP degree."""
+    parameters needs a cross-rank reduction); the schedule and the no-decay set work at any TP degree.
+
+    Packed variable-length batches (opt-in: `packed_tokens`; TP = 1): the step runs on [packed_tokens, hidden]
+    activations holding up to `max_seqs` sequences of 1 .. `max_len` tokens back to back, no padding inside a
+    sequence (BertForSequenceClassification.forward_packed; attention per sequence by
+    csrc/attn_varlen_train.hip). `set_packed_batch` packs on the host and rewrites the step's static buffers; the
+    captured step launches the grids of the capacity. The loss is the mean over the batch's real sequences."""
 
     def __init__(self, cfg: BertConfig, batch: int, seq: int, device, tp: TPGroup | None = None, lr: float = 2e-5,
                  graph: bool | None = None, flat_adamw: bool | None = None, sdpa: str | None = None,
                  tp_ipc: bool | None = None, max_grad_norm: float | None = None, warmup_steps: int = 0,
-                 total_steps: int | None = None, no_decay_bias_norm: bool = False):
-        """tp_ipc (TP > 1 on the GPU; default on, MIFX_TP_IPC=0 turns it off): the TP all-reduces run on the
+                 total_steps: int | None = None, no_decay_bias_norm: bool = False, packed_tokens: int | None = None,
+                 max_seqs: int | None = None, max_len: int | None = None):
+        """packed_tokens / max_seqs / max_len (all None: the padded trainer): token capacity of a packed step, its
+        sequence slots (default 4 * packed_tokens // seq) and the longest sequence (default seq; at most 512 and
+        the position table).
+        tp_ipc (TP > 1 on the GPU; default on, MIFX_TP_IPC=0 turns it off): the TP all-reduces run on the
         peer-memory kernels of mifx.parallel.tp_ipc, so the TP step is captured into a hipGraph like the TP=1
         step (otherwise they are torch.distributed collectives and TP > 1 steps eagerly)."""
         self.cfg, self.batch, self.seq, self.device = cfg, batch, seq, torch.device(device)
         self.tp = tp or TPGroup(None)
         cuda = self.device.type == "cuda"
+        self.packed = packed_tokens is not None
+        if not self.packed and (max_seqs is not None or max_len is not None):
+            raise ValueError("max_seqs and max_len belong to the packed path: set packed_tokens")
+        if self.packed:
+            from ..models import bert_infer as bim
+
+            if self.tp.size > 1 or cfg.sequence_parallel:
+                raise ValueError("packed variable-length batches need TP = 1 without sequence parallelism")
+            self.max_len = int(seq if max_len is None else max_len)
+            if not 1 <= self.max_len <= bim.max_length(cfg):
+                raise ValueError(f"max_len {self.max_len} outside 1 .. {bim.max_length(cfg)} (the attention kernels' "
+                                 f"512 and the position table)")
+            self.packed_tokens = int(packed_tokens)
+            self.max_seqs = int(max(1, 4 * self.packed_tokens // seq) if max_seqs is None else max_seqs)
+            if self.packed_tokens < self.max_len or self.max_seqs < 1:
+                raise ValueError(f"packed_tokens {self.packed_tokens} must hold a sequence of max_len {self.max_len}, "
+                                 f"and max_seqs {self.max_seqs} must be positive")
         self.flat = cuda if flat_adamw is None else (flat_adamw and cuda)
         if max_grad_norm is not None and self.tp.size > 1:
             raise ValueError("max_grad_norm needs TP = 1: the global gradient norm over sharded and replicated "
@@ -141,7 +200,9 @@ class BertTrainer:
             ws = [m.weight for layer in self.model.layers for m in (layer.qkv, layer.attn_out, layer.ffn_in,
                                                                       layer.ffn_out)]
             self.tcache = hg.TransposeCache(ws)
-        self.data = synthetic_batch(cfg, batch, seq, self.device)
+        self.data = None if self.packed else synthetic_batch(cfg, batch, seq, self.device)
+        if self.packed:
+            self._init_packed(cuda)
         self.amp = cuda
         self.sdpa = sdpa  # None = PyTorch's choice; "math" / "efficient" / "flash" pins the SDPA backend
         self.graph = None
@@ -163,6 +224,66 @@ class BertTrainer:
         for dst, src in zip(self.data, (ids, tt, am, y)):
             dst.copy_(src.to(dst.dtype), non_blocking=True)
 
+    def _init_packed(self, cuda: bool) -> None:
+        """Static buffers of the packed step: one int32 staging buffer (mifx.models.bert_infer.staging_views: ids,
+        token types, position ids, cu_seqlens, first rows, block table; then max_seqs labels), pinned on the host and
+        mirrored on the device, and a first synthetic batch of full-length sequences."""
+        from ..models import bert_infer as bim
+
+        C, B = self.packed_tokens, self.max_seqs
+        n = bim.staging_size(C, B)
+        self._phost = torch.empty(n + B, dtype=torch.int32, pin_memory=cuda)
+        self._pnp = self._phost.numpy()
+        self._pdev = torch.empty(n + B, dtype=torch.int32, device=self.device) if cuda else self._phost
+        self.pviews = bim.staging_views(self._pdev[:n], C, B)
+        self.plabels = self._pdev[n:]
+        self._pcopied = torch.cuda.Event() if cuda else None
+        self.packed_batch = (0, 0)  # (tokens, sequences) of the current batch
+        k = max(1, min(B, C // self.max_len))
+        seqs, tts, y = synthetic_sequences(self.cfg, k, self.max_len, self.max_len)
+        self.set_packed_batch(seqs, tts, y)
+
+    def set_packed_batch(self, seqs, token_types, labels) -> None:
+        """Next packed training batch: `seqs` a list of token-id lists (1 .. max_len ids each, at most max_seqs of
+        them and packed_tokens tokens in all), `token_types` None or per-sequence lists (None entries: zeros),
+        `labels` one class per sequence. Packed on the host and copied INTO the step's static buffers in one copy
+        (a captured hipGraph reads the same buffers on every replay). Padding rows carry id 0 and position 0, empty
+        sequence slots label -100."""
+        import numpy as np
+
+        from ..models import bert_infer as bim
+
+        if not self.packed:
+            raise ValueError("set_packed_batch needs a trainer built with packed_tokens")
+        seqs = [np.asarray(s) for s in seqs]
+        if not seqs:
+            raise ValueError("a packed batch needs at least one sequence")
+        bim.validate(seqs, token_types, self.cfg)
+        lens = [len(s) for s in seqs]
+        for i, L in enumerate(lens):
+            if L > self.max_len:
+                raise ValueError(f"sequence {i}: length {L} above max_len {self.max_len}")
+        if len(seqs) > self.max_seqs:
+            raise ValueError(f"{len(seqs)} sequences above max_seqs {self.max_seqs}")
+        if sum(lens) > self.packed_tokens:
+            raise ValueError(f"{sum(lens)} tokens above packed_tokens {self.packed_tokens}")
+        y = np.asarray(labels)
+        if y.shape != (len(seqs),) or y.dtype.kind not in "iu":
+            raise ValueError(f"{y.size} labels for {len(seqs)} sequences (one integer class each)")
+        if int(y.min()) < 0 or int(y.max()) >= self.cfg.num_labels:
+            raise ValueError(f"label outside [0, {self.cfg.num_labels})")
+        if self._pcopied is not None:
+            self._pcopied.synchronize()  # the previous copy out of the pinned buffer is done
+        n = bim.staging_size(self.packed_tokens, self.max_seqs)
+        p = bim.pack(seqs, token_types, self.packed_tokens, self.max_seqs, out=self._pnp[:n])
+        p.ids[p.tokens:] = 0  # a valid id: the embedding lookup reads every row (inference marks them -1)
+        self._pnp[n:n + len(seqs)] = y
+        self._pnp[n + len(seqs):] = -100
+        if self._pcopied is not None:
+            self._pdev.copy_(self._phost, non_blocking=True)
+            self._pcopied.record(torch.cuda.current_stream(self.device))
+        self.packed_batch = (p.tokens, p.seqs)
+
     @torch.no_grad()
     def predict(self, ids, tt, am) -> torch.Tensor:
         """Eval-mode logits (every TP rank must call it: the forward all-reduces)."""
@@ -174,15 +295,24 @@ class BertTrainer:
             self.model.train()
 
     def _eager_step(self) -> torch.Tensor:
-        ids, tt, am, y = self.data
+        if not self.packed:
+            ids, tt, am, y = self.data
         if self.flat:
             self.opt.zero_grad()  # in-place (gradients are views of one flat buffer): part of the step
         # the autocast weight-cast cache must be off for a step that is captured into a graph (PyTorch's
         # CUDA-graph rules: cached casts created outside the capture must not be referenced by it)
         with torch.autocast(self.device.type, dtype=torch.bfloat16, enabled=self.amp,
                             cache_enabled=not self.use_graph), self._sdpa_ctx():
-            logits = self.model(ids, tt, am)
-        loss = F.cross_entropy(logits.float(), y)
+            if self.packed:
+                v = self.pviews
+                logits = self.model.forward_packed(v.ids, v.tts, v.pos, v.cu, v.table, self.max_seqs, self.max_len,
+                                                   v.first)
+            else:
+                logits = self.model(ids, tt, am)
+        if self.packed:  # the mean over the real sequences (empty slots: label -100), on the device
+            loss = F.cross_entropy(logits.float(), self.plabels.long(), ignore_index=-100)
+        else:
+            loss = F.cross_entropy(logits.float(), y)
         from ..ops import gemm as hg
 
         if self.tcache is not None:
@@ -310,7 +440,18 @@ def main(argv=None):
                     help="linear decay of the learning rate to zero at this step (default: constant)")
     ap.add_argument("--no-decay-bias-norm", action="store_true",
                     help="no weight decay on biases and LayerNorm parameters")
+    ap.add_argument("--packed-tokens", type=int, default=None, metavar="C",
+                    help="packed variable-length batches: token capacity of a step (TP = 1; default: padded batches)")
+    ap.add_argument("--max-seqs", type=int, default=None,
+                    help="sequence slots of a packed step (default 4 * packed-tokens / seq)")
+    ap.add_argument("--length-range", type=int, nargs=2, default=None, metavar=("LO", "HI"),
+                    help="synthetic sequences with lengths uniform on [LO, HI] (seeded), a new batch every step: "
+                         "padded to --seq with the attention mask, or packed with --packed-tokens")
     a = ap.parse_args(argv)
+    if a.max_seqs is not None and a.packed_tokens is None:
+        ap.error("--max-seqs needs --packed-tokens")
+    if a.length_range is not None and not 1 <= a.length_range[0] <= a.length_range[1] <= a.seq:
+        ap.error("--length-range needs 1 <= LO <= HI <= --seq")
     if a.seed is not None:
         torch.manual_seed(a.seed)
     if a.tunable and torch.cuda.is_available():
@@ -331,14 +472,42 @@ def main(argv=None):
     tr = BertTrainer(cfg, a.batch, a.seq, dev, tp,
                      graph=False if a.no_graph else (True if a.graph else None),
                      flat_adamw=False if a.no_flat_adamw else None, sdpa=a.sdpa, max_grad_norm=a.max_grad_norm,
-                     warmup_steps=a.warmup_steps, total_steps=a.total_steps, no_decay_bias_norm=a.no_decay_bias_norm)
+                     warmup_steps=a.warmup_steps, total_steps=a.total_steps, no_decay_bias_norm=a.no_decay_bias_norm,
+                     packed_tokens=a.packed_tokens, max_seqs=a.max_seqs)
     from ..ops import native_stats
+
+    # the batches of the run: None (the trainer's own static batch, as always), or a cycle over synthetic
+    # variable-length sequences, packed greedily or padded in groups of --batch
+    feed = None
+    if a.length_range is not None or a.packed_tokens is not None:
+        lo, hi = a.length_range or (a.seq, a.seq)
+        seqs, tts, ys = synthetic_sequences(cfg, 16 * a.batch, lo, hi, seed=0 if a.seed is None else a.seed)
+        if a.packed_tokens is not None:
+            groups = list(plan_train_batches([len(s) for s in seqs], tr.packed_tokens, tr.max_seqs))
+        else:
+            groups = [list(range(i, i + a.batch)) for i in range(0, len(seqs), a.batch)]
+        feed = [([seqs[j] for j in g], [tts[j] for j in g], ys[g]) for g in groups]
+    n_seq = n_tok = 0
+
+    def next_batch(i: int) -> tuple:
+        """Set step i's batch; returns its (sequences, real tokens)."""
+        if feed is None:
+            return a.batch, a.batch * a.seq
+        b = feed[i % len(feed)]
+        if tr.packed:
+            tr.set_packed_batch(*b)
+        else:
+            from ..models.bert_infer import _pad_arrays
+
+            tr.set_batch(*(torch.from_numpy(x) for x in _pad_arrays(b[0], b[1], a.seq)), torch.from_numpy(b[2]))
+        return len(b[0]), sum(len(s) for s in b[0])
 
     per_step = None
     with heartbeat("bert warmup"):
         for i in range(a.warmup):
             if i == 0:
                 native_stats.reset()
+            next_batch(i)
             tr.step()
             if i == 0:  # the first step runs every dispatch in Python: which path each GEMM / attention call took
                 per_step = native_stats.snapshot()
@@ -352,6 +521,8 @@ def main(argv=None):
     sync_each = os.environ.get("MIFX_BERT_SYNC") == "1"  # diagnostic: device sync after every step
     t0 = time.perf_counter()
     for i in range(a.steps):
+        ns, nt = next_batch(a.warmup + i)
+        n_seq, n_tok = n_seq + ns, n_tok + nt
         loss = tr.step()
         if sync_each and dev.type == "cuda":
             torch.cuda.synchronize()
@@ -363,8 +534,11 @@ def main(argv=None):
     dt = mdist.max_over_ranks(time.perf_counter() - t0)
     tr.check()  # ... and during the timed steps: never report a throughput of garbage activations
     if env.rank == 0:
-        print(json.dumps({"metric": "BERT-base fine-tune sequences/sec (TP over the node)", "value": a.batch * a.steps / dt,
-                          "unit": "sequences/s", "n_gpus": env.world_size, "tp": tp.size,
+        print(json.dumps({"metric": "BERT-base fine-tune sequences/sec (TP over the node)", "value": n_seq / dt,
+                          "unit": "sequences/s", "sequences/s": n_seq / dt, "tokens/s": n_tok / dt,
+                          "packed_tokens": a.packed_tokens, "max_seqs": tr.max_seqs if tr.packed else None,
+                          "length_range": a.length_range, "mean_sequences_per_step": n_seq / max(1, a.steps),
+                          "n_gpus": env.world_size, "tp": tp.size,
                           "sequence_parallel": tr.model.sequence_parallel, "batch": a.batch,
                           "seq_len": a.seq, "ms_per_step": 1e3 * dt / a.steps, "loss": float(loss),
                           "dtype": "bf16", "data": "synthetic", "layers": a.layers,

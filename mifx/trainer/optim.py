@@ -312,6 +312,10 @@ class FlatAdamW:
                 raise RuntimeError("FlatAdamW(grads='own') supports one captured step per optimizer")
             self._capture_host.numpy()[:] = addr
             self._gptr.copy_(self._capture_host, non_blocking=True)
+            # the pinned table must outlive the graph: once released, the host allocator hands the block to the next
+            # pinned allocation of its size (another optimizer's eager address upload, a pinned batch), and every
+            # replay of this step would copy that tensor's contents in as gradient addresses
+            self._captured_table = self._capture_host
             self._capture_host, self._addr = None, addr
         elif addr != self._addr:  # eager: upload only when autograd handed out new gradient addresses
             self._gptr.copy_(torch.tensor(addr, dtype=torch.int64).pin_memory(), non_blocking=True)
