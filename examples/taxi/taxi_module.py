@@ -49,8 +49,13 @@ def _input_fn(files, device=None):
 
 
 def trainer_fn(hparams, schema):
-    first_dnn_layer_size, num_dnn_layers, dnn_decay_factor = 100, 4, 0.7
-    train_batch_size = int((hparams.custom_config or {}).get("batch_size", 40))
+    # the tower knobs of the reference's trainer_fn (`taxi_utils.py:300-302`), tunable through custom_config; any
+    # tower other than the default trains on the general fused kernel on a GPU (single GPU)
+    custom = hparams.custom_config or {}
+    first_dnn_layer_size = int(custom.get("first_dnn_layer_size", 100))
+    num_dnn_layers = int(custom.get("num_dnn_layers", 4))
+    dnn_decay_factor = float(custom.get("dnn_decay_factor", 0.7))
+    train_batch_size = int(custom.get("batch_size", 40))
     eval_batch_size = 40
     run_config = RunConfig(save_checkpoints_steps=999, keep_checkpoint_max=1, device=hparams.device)
     run_config = run_config.replace(model_dir=hparams.serving_model_dir)

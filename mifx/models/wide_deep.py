@@ -419,3 +419,148 @@ def chain_maps(cfg: WideDeepConfig | None = None):
     gidx[WTOT:] = stride - WIDE_PAD + np.arange(NWIDE)
     mask[WTOT:] = 1
     return tmap, stride, gidx, mask, wmap
+
+
+# ---- tower-independent ("flat") parameter layout ---------------------------------------------
+# Every layer as [n_out][n_in + 1] with the bias in the last column, head included; then the wide weights and
+# the wide bias. The checkpoint layout of every tower the canonical padding above cannot hold (pack_state).
+def flat_size(cfg: WideDeepConfig) -> int:
+    return sum(nr * (kr + 1) for kr, nr in _real_dims(cfg)) + cfg.wide_rows + 1
+
+
+def pack_flat(model: WideDeepModel) -> np.ndarray:
+    """torch model -> fp32 flat parameter vector [flat_size(cfg)]."""
+    parts = []
+    for lin in list(model.dnn) + [model.head]:
+        w = lin.weight.detach().cpu().numpy().astype(np.float32)
+        b = lin.bias.detach().cpu().numpy().astype(np.float32)
+        parts.append(np.concatenate([w, b[:, None]], 1).reshape(-1))
+    parts.append(model.wide.detach().cpu().numpy().astype(np.float32).reshape(-1))
+    parts.append(model.wide_bias.detach().cpu().numpy().astype(np.float32).reshape(-1))
+    return np.concatenate(parts)
+
+
+def unpack_flat(vec, model: WideDeepModel) -> WideDeepModel:
+    """fp32 flat vector -> torch model parameters (in place)."""
+    vec = np.asarray(vec.detach().cpu() if torch.is_tensor(vec) else vec, dtype=np.float32).reshape(-1)
+    if vec.size != flat_size(model.cfg):
+        raise ValueError(f"flat vector of {vec.size} entries does not fit hidden_units {model.cfg.hidden_units} "
+                         f"({flat_size(model.cfg)} entries)")
+    o = 0
+    with torch.no_grad():
+        for lin in list(model.dnn) + [model.head]:
+            nr, kr = lin.weight.shape
+            blk = vec[o:o + nr * (kr + 1)].reshape(nr, kr + 1)
+            lin.weight.copy_(torch.from_numpy(blk[:, :kr].copy()))
+            lin.bias.copy_(torch.from_numpy(blk[:, kr].copy()))
+            o += nr * (kr + 1)
+        nw = model.wide.numel()
+        model.wide.copy_(torch.from_numpy(vec[o:o + nw].copy()))
+        model.wide_bias.fill_(float(vec[o + nw]))
+    return model
+
+
+def uses_canonical_layout(cfg: WideDeepConfig) -> bool:
+    """True for the towers inside the canonical padding: their checkpoints keep the canonical vectors."""
+    try:
+        check_fused_compatible(cfg)
+        return True
+    except ValueError:
+        return False
+
+
+def pack_state(model: WideDeepModel) -> np.ndarray:
+    """The checkpoint vector of a model: canonical where the tower fits it (as always), flat otherwise."""
+    return pack_canonical(model) if uses_canonical_layout(model.cfg) else pack_flat(model)
+
+
+def unpack_state(vec, model: WideDeepModel) -> WideDeepModel:
+    return unpack_canonical(vec, model) if uses_canonical_layout(model.cfg) else unpack_flat(vec, model)
+
+
+# ---- general kernel layout (csrc/wd_general.hip) ----------------------------------------------
+GEN_MAX_HIDDEN = 6
+GEN_MAX_WIDTH = 256
+GEN_T = 64
+GEN_PAD = 8
+GEN_DESC_HDR, GEN_DESC_LAYER = 8, 8
+GEN_DESC_LEN = GEN_DESC_HDR + GEN_DESC_LAYER * (GEN_MAX_HIDDEN + 1)
+
+
+def check_general_compatible(cfg: WideDeepConfig) -> None:
+    """The limits of the general fused kernel: 1..6 hidden layers of width 2..256, the taxi record."""
+    hu = list(cfg.hidden_units)
+    if not 1 <= len(hu) <= GEN_MAX_HIDDEN:
+        raise ValueError(f"general fused kernel: 1 to {GEN_MAX_HIDDEN} hidden layers, got {len(hu)}")
+    for wdt in hu:
+        if not 2 <= int(wdt) <= GEN_MAX_WIDTH:
+            raise ValueError(f"general fused kernel: hidden width in [2, {GEN_MAX_WIDTH}], got {wdt}")
+    if len(cfg.dense_features) != 3:
+        raise ValueError("general fused kernel: the taxi record has 3 dense features")
+    if [nb for _, nb in cfg.wide] != [1010, 1010, 10, 10, 10, 10, 24, 31, 12]:
+        raise ValueError("general fused kernel is specialised for the taxi wide columns")
+
+
+@dataclass
+class GeneralLayout:
+    """Geometry and index maps of the general kernel for one tower. K / N / off: per layer (head included) the
+    padded input / output widths and the offset of its [N][K] block in the W^T image, which is also its place in
+    the gradient slab and in the slab-column-order master state. pidx [flat_size]: flat parameter -> slab column;
+    kind [stride]: -1 padding (never updated), -2 wide, >= 0 DNN entry with its offset in the transposed image
+    (second half of the bf16 image); ones: the columns that hold the constant 1 feeding the next layer's bias."""
+    K: list
+    N: list
+    off: list
+    wtot: int
+    stride: int
+    scratch: int
+    desc: np.ndarray
+    pidx: np.ndarray
+    kind: np.ndarray
+    ones: np.ndarray
+
+
+def general_layout(cfg: WideDeepConfig) -> GeneralLayout:
+    check_general_compatible(cfg)
+    real = _real_dims(cfg)
+    K = [-(-(kr + 1) // 32) * 32 for kr, _ in real]
+    N = K[1:] + [32]
+    off = [int(v) for v in np.cumsum([0] + [k * n for k, n in zip(K, N)])]
+    wtot, off = off[-1], off[:-1]
+    stride = wtot + WIDE_PAD
+    desc = np.zeros(GEN_DESC_LEN, np.int32)
+    desc[0], desc[1], desc[2] = len(real), max(K) + GEN_PAD, wtot
+    so = 0
+    pidx, ones = [], []
+    kind = np.full(stride, -1, np.int32)
+    for li, ((kr, nr), k, n, o) in enumerate(zip(real, K, N, off)):
+        b = GEN_DESC_HDR + GEN_DESC_LAYER * li
+        desc[b:b + 6] = [k, n, o, -(-nr // 16), -(-(kr + 1) // 16), so]
+        so += GEN_T * k
+        nn = np.arange(nr)[:, None]
+        kk = np.arange(kr + 1)[None, :]
+        col = o + nn * k + kk
+        pidx.append(col.reshape(-1))
+        kind[col] = o + kk * n + nn
+        if li < len(real) - 1:
+            ones.append(o + nr * k + kr)
+    nw = cfg.wide_rows + 1
+    assert nw == NWIDE
+    pidx.append(wtot + np.arange(nw))
+    kind[wtot:wtot + nw] = -2
+    return GeneralLayout(K, N, off, wtot, stride, so, desc, np.concatenate(pidx).astype(np.int64), kind,
+                         np.asarray(ones, np.int64))
+
+
+def flat_grad_to_torch(flat: np.ndarray, model: WideDeepModel) -> dict[str, np.ndarray]:
+    """A flat-order gradient (or parameter) vector as named torch-shaped arrays (for tests)."""
+    out, o = {}, 0
+    names = [f"dnn.{i}" for i in range(len(model.dnn))] + ["head"]
+    for nm, lin in zip(names, list(model.dnn) + [model.head]):
+        nr, kr = lin.weight.shape
+        blk = np.asarray(flat[o:o + nr * (kr + 1)]).reshape(nr, kr + 1)
+        out[nm + ".weight"], out[nm + ".bias"] = blk[:, :kr], blk[:, kr]
+        o += nr * (kr + 1)
+    nw = model.wide.numel()
+    out["wide"], out["wide_bias"] = np.asarray(flat[o:o + nw]), np.asarray(flat[o + nw:o + nw + 1])
+    return out

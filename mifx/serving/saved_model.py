@@ -193,9 +193,10 @@ class LoadedModel:
         t = torch.from_numpy(rec.view(np.uint8).reshape(-1, 32).copy())
         if self.device.type == "cuda" and len(rec):
             if self._fused is None:
-                from ..trainer.fused_wide_deep import FusedWideDeepTrainer
+                from ..trainer.dispatch import make_wide_deep_trainer
 
-                self._fused = FusedWideDeepTrainer(self.model, batch=64, device=self.device)
+                # the chained kernel for the taxi tower, the general fused kernel for any other hidden_units
+                self._fused = make_wide_deep_trainer(self.model, self.device, batch=64)
             return self._fused.predict_logits(t).cpu().numpy()
         dense, ids, _ = wdm.records_to_tensors(t)
         with torch.no_grad():

@@ -1,0 +1,65 @@
+"""Which Wide&Deep trainer a model trains on.
+
+CPU: the PyTorch trainer. GPU: the chained kernel (FusedWideDeepTrainer) when it is compiled for the tower --
+`check_fused_compatible` and `ops.wd_chain.check_live_tiles` accept it, which today means the live 16x16 tiles of the
+taxi tower [100, 70, 48, 34] -- and the general fused kernel (GeneralWideDeepTrainer) for every other tower.
+"""
+from __future__ import annotations
+
+import torch
+
+from ..models import wide_deep as wdm
+
+
+def chain_kernel_accepts(cfg: wdm.WideDeepConfig) -> bool:
+    """True when every build of the chained kernel (T = 64 / 128 / 256) is compiled for this tower."""
+    from ..ops import wd_chain as wdc
+
+    try:
+        wdm.check_fused_compatible(cfg)
+        tmap = wdm.chain_maps(cfg)[0]
+        for tile in (64, 128, 256):
+            wdc.check_live_tiles(cfg, tmap, tile)
+    except ValueError:
+        return False
+    return True
+
+
+def select_kernel(cfg: wdm.WideDeepConfig, kernel: str | None = None) -> str:
+    """"chain" / "tile" / "general" for a GPU trainer. kernel=None: the chained kernel where it accepts the tower,
+    else the general one; a forced specialised kernel on a tower it cannot run raises as before."""
+    if kernel is None:
+        return "chain" if chain_kernel_accepts(cfg) else "general"
+    if kernel not in ("chain", "tile", "general"):
+        raise ValueError("kernel must be 'chain', 'tile', 'general' or None")
+    return kernel
+
+
+def check_world(cfg: wdm.WideDeepConfig, world: int, device_type: str = "cuda", kernel: str | None = None) -> None:
+    """Raise before any rank starts when a data-parallel GPU job asks for a tower only the general kernel trains."""
+    if world > 1 and device_type == "cuda" and select_kernel(cfg, kernel) == "general":
+        wdm.check_general_compatible(cfg)
+        raise ValueError(f"general towers are single-GPU: hidden_units {list(cfg.hidden_units)} train on the general "
+                         f"fused kernel, which has no data-parallel path yet (num_gpus / world = {world}); use one "
+                         f"GPU or the taxi tower {wdm.dnn_hidden_units()}")
+
+
+def make_wide_deep_trainer(model: wdm.WideDeepModel, device, *, batch: int = 40, dnn_opt=None, wide_opt=None,
+                           loss_reduction: str = "sum", process_group=None, kernel: str | None = None,
+                           shuffle_seed: int = 0, feed_stride: int | None = None, feed_offset: int = 0, **kw):
+    """The trainer for `model` on `device`. kernel (GPU only): None = automatic, "general" forces the general
+    kernel (tests, A/B), "chain" / "tile" the specialised ones. **kw goes to the chosen trainer."""
+    from .fused_wide_deep import FusedWideDeepTrainer
+    from .general_wide_deep import GeneralWideDeepTrainer
+    from .torch_wide_deep import TorchWideDeepTrainer
+
+    device = torch.device(device)
+    common = dict(batch=batch, device=device, dnn_opt=dnn_opt, wide_opt=wide_opt, loss_reduction=loss_reduction,
+                  process_group=process_group, shuffle_seed=shuffle_seed, feed_stride=feed_stride,
+                  feed_offset=feed_offset)
+    if device.type != "cuda":
+        return TorchWideDeepTrainer(model, **common, **kw)
+    k = select_kernel(model.cfg, kernel)
+    if k == "general":
+        return GeneralWideDeepTrainer(model, **common, **kw)
+    return FusedWideDeepTrainer(model, kernel=k, **common, **kw)

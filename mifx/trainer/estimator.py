@@ -138,6 +138,10 @@ class WideDeepEstimator:
         self.steps_per_graph = int(steps_per_graph)
         self.cfg = wdm.WideDeepConfig(hidden_units=list(hidden_units or wdm.dnn_hidden_units()))
         self.device = _default_device(config)
+        if self.world > 1:  # a tower only the general (single-GPU) kernel trains: refuse before any training starts
+            from .dispatch import check_world
+
+            check_world(self.cfg, self.world, self.device.type)
         self.batch_size = batch_size
         self.eval_batch_size = int(eval_batch_size or batch_size)
         self.loss_reduction = loss_reduction
@@ -202,8 +206,8 @@ class WideDeepEstimator:
 
     # ------------------------------------------------------------------ train / eval
     def _make_trainer(self, records: torch.Tensor):
-        from .fused_wide_deep import FusedWideDeepTrainer, default_dnn_opt, default_wide_opt
-        from .torch_wide_deep import TorchWideDeepTrainer
+        from .dispatch import make_wide_deep_trainer
+        from .fused_wide_deep import default_dnn_opt, default_wide_opt
 
         dopt = self.dnn_optimizer or default_dnn_opt()
         wopt = self.linear_optimizer or default_wide_opt(len(self.cfg.wide))
@@ -216,12 +220,10 @@ class WideDeepEstimator:
             raise ValueError(f"{n} records < one global batch ({self.world} x {self.batch_size})")
         feed = dict(shuffle_seed=self.shuffle_seed() if self.shuffle else 0, feed_stride=self.world * bs,
                     feed_offset=self.rank * bs)
-        if self.device.type == "cuda":
-            tr = FusedWideDeepTrainer(self.model, batch=bs, device=self.device, dnn_opt=dopt, wide_opt=wopt,
-                                      loss_reduction=self.loss_reduction, process_group=self.pg, **feed)
-        else:
-            tr = TorchWideDeepTrainer(self.model, batch=bs, device=self.device, dnn_opt=dopt, wide_opt=wopt,
-                                      loss_reduction=self.loss_reduction, process_group=self.pg, **feed)
+        # CPU: the PyTorch trainer; GPU: the chained kernel where it is compiled for the tower, the general fused
+        # kernel for every other hidden_units (trainer.dispatch)
+        tr = make_wide_deep_trainer(self.model, self.device, batch=bs, dnn_opt=dopt, wide_opt=wopt,
+                                    loss_reduction=self.loss_reduction, process_group=self.pg, **feed)
         st = getattr(self, "_opt_state", None) or {}
         tr.load_state_dict({"param": None, "s0": st.get("s0"), "s1": st.get("s1"),
                             "step": torch.tensor([self.global_step])})

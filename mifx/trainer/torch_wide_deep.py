@@ -2,8 +2,9 @@
 fused HIP trainer). Used by the Trainer component on CPU-only hosts and as the numerics oracle
 in tests.
 
-Checkpoint state uses the fused trainer's canonical layout (`state_dict()`: param / s0 / s1 vectors
-[WTOT + NWIDE] + step), so a checkpoint written on one path resumes on the other: s0 / s1 are the
+Checkpoint state uses the fused trainers' layout (`state_dict()`: param / s0 / s1 vectors + step; canonical
+[WTOT + NWIDE] for the towers inside the canonical padding, the tower-independent flat layout of
+models.wide_deep.pack_flat for every other), so a checkpoint written on one path resumes on the other: s0 / s1 are the
 Adagrad accumulator, FTRL (accumulator, linear) and Adam (m, v) slots of csrc/wide_deep.hip
 opt_update."""
 from __future__ import annotations
@@ -126,17 +127,17 @@ class TorchWideDeepTrainer:
                             continue
                         st = opt.state.get(p, {})
                         q.copy_(st[key].cpu() if key in st else torch.full_like(q, init))
-            out.append(wdm.pack_canonical(m))
+            out.append(wdm.pack_state(m))
         return out[0], out[1]
 
     def state_dict(self) -> dict:
         s0, s1 = self._slot_vectors()
-        return {"param": torch.from_numpy(wdm.pack_canonical(self.model)), "s0": torch.from_numpy(s0),
+        return {"param": torch.from_numpy(wdm.pack_state(self.model)), "s0": torch.from_numpy(s0),
                 "s1": torch.from_numpy(s1), "step": torch.tensor([self.step_idx], dtype=torch.int64)}
 
     def load_state_dict(self, sd: dict) -> None:
         if sd.get("param") is not None:
-            wdm.unpack_canonical(sd["param"], self.model)
+            wdm.unpack_state(sd["param"], self.model)
         if "step" in sd:
             self.step_idx = int(torch.as_tensor(sd["step"]).reshape(-1)[0])
         slots = [sd.get("s0"), sd.get("s1")]
@@ -146,7 +147,7 @@ class TorchWideDeepTrainer:
                 views.append(None)
                 continue
             m = copy.deepcopy(self.model).cpu()
-            wdm.unpack_canonical(v, m)
+            wdm.unpack_state(v, m)
             views.append(dict(m.named_parameters()))
         for (opt, kind, sel, _) in self._opts():
             for n, p in self.model.named_parameters():
