@@ -26,35 +26,7 @@ constexpr int kChunk = 8192;  // columns per dp_row_sumsq block (256 threads x 4
 constexpr int kMaxRows = 4096;
 constexpr int kMaxC = 64;
 
-// ---- Philox4x32-10 counter-based RNG --------------------------------------------------------
-struct U4 {
-  uint32_t x, y, z, w;
-};
-
-__device__ __forceinline__ U4 philox(U4 c, uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c.x;
-    const uint64_t p1 = (uint64_t)0xCD9E8D57u * c.z;
-    const uint32_t hi0 = (uint32_t)(p0 >> 32), lo0 = (uint32_t)p0;
-    const uint32_t hi1 = (uint32_t)(p1 >> 32), lo1 = (uint32_t)p1;
-    c = U4{hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0};
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  return c;
-}
-
-// uniform in (0, 1]: never 0, so log() is finite
-__device__ __forceinline__ float u01(uint32_t v) { return ((float)(v >> 8) + 1.0f) * (1.0f / 16777216.0f); }
-
-__device__ __forceinline__ void box_muller(uint32_t a, uint32_t b, float& z0, float& z1) {
-  const float r = sqrtf(-2.0f * logf(u01(a)));
-  float s, c;
-  sincosf(6.283185307179586f * u01(b), &s, &c);
-  z0 = r * c;
-  z1 = r * s;
-}
+#include "philox.h"  // Philox4x32-10, u01, box_muller
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

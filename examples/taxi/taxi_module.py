@@ -57,12 +57,24 @@ def trainer_fn(hparams, schema):
     dnn_decay_factor = float(custom.get("dnn_decay_factor", 0.7))
     train_batch_size = int(custom.get("batch_size", 40))
     eval_batch_size = 40
+    # differentially private training (per-example DP-SGD, single GPU; every tower then trains on the general fused
+    # kernel): dp_l2_norm_clip and dp_noise_multiplier switch it on, dp_delta is the delta privacy.json reports
+    # epsilon for. Absent: no DP.
+    dp = None
+    if custom.get("dp_l2_norm_clip") is not None or custom.get("dp_noise_multiplier") is not None:
+        from mifx.privacy.spec import DPSpec
+
+        if custom.get("dp_l2_norm_clip") is None or custom.get("dp_noise_multiplier") is None:
+            raise ValueError("DP training needs both dp_l2_norm_clip and dp_noise_multiplier in custom_config")
+        dp = DPSpec(float(custom["dp_l2_norm_clip"]), float(custom["dp_noise_multiplier"]))
     run_config = RunConfig(save_checkpoints_steps=999, keep_checkpoint_max=1, device=hparams.device)
     run_config = run_config.replace(model_dir=hparams.serving_model_dir)
     est = WideDeepEstimator(run_config, hidden_units=[max(2, int(first_dnn_layer_size * dnn_decay_factor ** i))
                                                       for i in range(num_dnn_layers)],
                             warm_start_from=hparams.warm_start_from, batch_size=train_batch_size,
-                            eval_batch_size=eval_batch_size)
+                            eval_batch_size=eval_batch_size, dp=dp)
+    if dp is not None:
+        est.dp_delta = float(custom.get("dp_delta", 1e-5))
     dev = est.device
     serving_receiver = lambda: {"kind": "raw_examples", "transform_output": hparams.transform_output,  # noqa: E731
                                 "raw_feature_spec": {f.name: f.type for f in schema.feature if f.name != LABEL_KEY}}

@@ -44,7 +44,13 @@ class TrainerSpec(ComponentSpec):
 class TrainerExecutor(BaseExecutor):
     """custom_config["num_gpus"] = N > 1 trains data-parallel: N ranks (one per GPU; gloo processes on a CPU
     host) launched by mifx.trainer.distributed, each running the same trainer_fn on its shard of every global
-    batch; rank 0 evaluates and exports. Otherwise trainer_fn runs in this process."""
+    batch; rank 0 evaluates and exports. Otherwise trainer_fn runs in this process.
+
+    Differentially private training (read by the taxi user module): custom_config["dp_l2_norm_clip"] = C and
+    custom_config["dp_noise_multiplier"] = sigma switch on per-example DP-SGD (every example's gradient clipped to
+    L2 norm C, N(0, (sigma C)^2) noise on the clipped sum), custom_config["dp_delta"] (default 1e-5) is the delta
+    for which the export's privacy.json reports epsilon. Absent: no DP. DP is single-GPU: together with
+    num_gpus > 1 it is refused here, before any rank starts."""
 
     def Do(self, input_dict, output_dict, exec_properties):  # noqa: N802
         ex = {a.split: a.uri for a in input_dict["transformed_examples"]}
@@ -62,6 +68,11 @@ class TrainerExecutor(BaseExecutor):
         n = int(custom.get("num_gpus", 1) or 1)
         if n > 1:
             from ..trainer import distributed
+            from ..models import wide_deep as wdm
+            from ..trainer.dispatch import check_world
+
+            if custom.get("dp_l2_norm_clip") is not None or custom.get("dp_noise_multiplier") is not None:
+                check_world(wdm.WideDeepConfig(), n, dp=True)  # raises: DP has no data-parallel path
 
             res = distributed.launch({"module_file": module_file, "hparams": hp, "schema_uri": schema_uri,
                                       "out_dir": out.uri, "work_dir": os.path.join(out.uri, "dp_run")},

@@ -535,7 +535,7 @@ def general_layout(cfg: WideDeepConfig) -> GeneralLayout:
     kind = np.full(stride, -1, np.int32)
     for li, ((kr, nr), k, n, o) in enumerate(zip(real, K, N, off)):
         b = GEN_DESC_HDR + GEN_DESC_LAYER * li
-        desc[b:b + 6] = [k, n, o, -(-nr // 16), -(-(kr + 1) // 16), so]
+        desc[b:b + 7] = [k, n, o, -(-nr // 16), -(-(kr + 1) // 16), so, nr]  # nr: read by the DP norm sweep
         so += GEN_T * k
         nn = np.arange(nr)[:, None]
         kk = np.arange(kr + 1)[None, :]

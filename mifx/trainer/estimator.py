@@ -124,7 +124,7 @@ class WideDeepEstimator:
 
     def __init__(self, config: RunConfig, hidden_units: list[int] | None = None, warm_start_from: str | None = None,
                  batch_size: int = 40, loss_reduction: str = "sum", dnn_optimizer=None, linear_optimizer=None,
-                 steps_per_graph: int = 100, shuffle: bool = True, eval_batch_size: int | None = None):
+                 steps_per_graph: int = 100, shuffle: bool = True, eval_batch_size: int | None = None, dp=None):
         """batch_size is per replica: a data-parallel Trainer with N ranks trains on N x batch_size examples per
         step (TF distributed Estimator semantics). steps_per_graph: training steps per hipGraph replay on the
         GPU (checkpoint boundaries and max_steps are honoured exactly; remainders replay a one-step graph).
@@ -132,7 +132,11 @@ class WideDeepEstimator:
         config.tf_random_seed (`read_batch_features(randomize_input=True)`, `taxi_utils.py:275-276`); the same
         order on the CPU and GPU paths and for any number of data-parallel ranks (mifx.data.shuffle).
         eval_batch_size: the evaluation input's batch (default batch_size): evaluate(steps) reads steps x
-        eval_batch_size examples, whatever the number of training ranks (`taxi_utils.py:304-305`: 40 / 40)."""
+        eval_batch_size examples, whatever the number of training ranks (`taxi_utils.py:304-305`: 40 / 40).
+        dp: privacy.DPSpec -- per-example DP-SGD (single process; on the GPU every tower then trains on the general
+        fused kernel). A spec with seed 0 takes its noise seed from config.tf_random_seed. The noise stream is keyed
+        by the optimizer step, so checkpoints need nothing new; privacy_spent() reports epsilon and the exporters
+        write it beside the model as privacy.json."""
         self.config = config
         self.pg, self.rank, self.world = _dist_info()
         self.steps_per_graph = int(steps_per_graph)
@@ -141,7 +145,11 @@ class WideDeepEstimator:
         if self.world > 1:  # a tower only the general (single-GPU) kernel trains: refuse before any training starts
             from .dispatch import check_world
 
-            check_world(self.cfg, self.world, self.device.type)
+            check_world(self.cfg, self.world, self.device.type, dp=dp is not None)
+        if dp is not None and int(dp.seed) == 0:
+            dp = dataclasses.replace(dp, seed=self.noise_seed())
+        self.dp = dp
+        self.dp_delta = 1e-5  # the delta privacy.json is written for
         self.batch_size = batch_size
         self.eval_batch_size = int(eval_batch_size or batch_size)
         self.loss_reduction = loss_reduction
@@ -223,7 +231,8 @@ class WideDeepEstimator:
         # CPU: the PyTorch trainer; GPU: the chained kernel where it is compiled for the tower, the general fused
         # kernel for every other hidden_units (trainer.dispatch)
         tr = make_wide_deep_trainer(self.model, self.device, batch=bs, dnn_opt=dopt, wide_opt=wopt,
-                                    loss_reduction=self.loss_reduction, process_group=self.pg, **feed)
+                                    loss_reduction=self.loss_reduction, process_group=self.pg, **feed,
+                                    **({} if self.dp is None else {"dp": self.dp}))
         st = getattr(self, "_opt_state", None) or {}
         tr.load_state_dict({"param": None, "s0": st.get("s0"), "s1": st.get("s1"),
                             "step": torch.tensor([self.global_step])})
@@ -233,6 +242,34 @@ class WideDeepEstimator:
     def shuffle_seed(self) -> int:
         """The (non-zero) shuffle key derived from config.tf_random_seed."""
         return ((int(self.config.tf_random_seed or 0) * 0x9E3779B97F4A7C15) ^ 0x5EEDF00D) % (2**64 - 1) + 1
+
+    def noise_seed(self) -> int:
+        """The (non-zero) DP noise seed derived from config.tf_random_seed (for a DPSpec with seed 0)."""
+        return ((int(self.config.tf_random_seed or 0) * 0xD1B54A32D192ED03) ^ 0xD9B0A11CE) % (2**63 - 1) + 1
+
+    def privacy_spent(self, n_examples: int, delta: float = 1e-5) -> dict:
+        """(epsilon, delta) of the training so far, by the RDP accountant (privacy.rdp.compute_dp_sgd_privacy) from
+        the global step, the batch and the noise multiplier, for a training set of n_examples. The accountant
+        assumes Poisson sampling at rate batch / n_examples while the feed is a shuffled epoch stream: the caveat
+        of TF-Privacy's compute_dp_sgd_privacy."""
+        import math
+
+        from ..privacy.rdp import compute_dp_sgd_privacy
+
+        if self.dp is None:
+            raise RuntimeError("privacy_spent() needs an estimator built with dp=DPSpec(...)")
+        n, steps = int(n_examples), int(self.global_step)
+        batch = int(self._trainer.batch) if self._trainer is not None else min(int(self.batch_size), n)
+        eps = math.inf
+        if self.dp.noise_multiplier > 0 and steps == 0:
+            eps = 0.0
+        elif self.dp.noise_multiplier > 0:
+            epochs = steps * batch / n
+            while math.ceil(epochs * n / batch) > steps:  # the accountant recovers the step count from the epochs
+                epochs = math.nextafter(epochs, 0.0)
+            eps = float(compute_dp_sgd_privacy(n, batch, float(self.dp.noise_multiplier), epochs, delta)[0])
+        return {"epsilon": eps, "delta": float(delta), "noise_multiplier": float(self.dp.noise_multiplier),
+                "l2_norm_clip": float(self.dp.l2_norm_clip), "steps": steps, "sampling_rate": batch / n}
 
     def _graph_setup(self, tr) -> None:
         """GPU: capture S-step hipGraphs (data-parallel: the xGMI exchange inside the graph, the direct RCCL
@@ -261,6 +298,7 @@ class WideDeepEstimator:
         every save_checkpoints_steps. On the GPU the steps between checkpoints run as multi-step hipGraph
         replays (per-step `hooks` force one host step at a time)."""
         records = input_fn()
+        self._n_train = int(records.shape[0])
         self._trainer = tr = self._make_trainer(records)
         every = self.config.save_checkpoints_steps or 0
         cuda = self.device.type == "cuda"
@@ -343,6 +381,11 @@ class WideDeepEstimator:
         receiver = serving_input_receiver_fn() if serving_input_receiver_fn else {}
         path = os.path.join(export_dir_base, str(int(time.time() * 1000)))
         saved_model.save_wide_deep(path, self.model, receiver, global_step=self.global_step)
+        if self.dp is not None and getattr(self, "_n_train", None):
+            import json
+
+            with open(os.path.join(path, "privacy.json"), "w") as f:  # what the training spent, beside the model
+                json.dump(self.privacy_spent(self._n_train, self.dp_delta), f)
         return path
 
     export_savedmodel = export_saved_model

@@ -7,6 +7,11 @@ master weights and optimizer slots live in slab-column order (models.wide_deep.g
 data offset advance through a device-side counter, so a step (or S steps) replays as one hipGraph. Slower than the
 chained kernel, which is compiled for the taxi tower and stays the default for it (trainer.dispatch); this is the
 path for every other `hidden_units`. The surface is FusedWideDeepTrainer's, as the estimator and serving use it.
+
+dp=DPSpec(...): differentially private training, per example. The fused kernel measures every example's gradient
+norm through the exact layer-wise factorisation, clips by c_i = min(1, s C / n_i) inside the step (no per-example
+gradient is ever materialised) and the reduce / optimizer pass adds the Gaussian noise from a Philox stream keyed by
+(seed, optimizer step): graph replays draw fresh noise without host state, a resumed run continues the stream.
 """
 from __future__ import annotations
 
@@ -17,6 +22,7 @@ import torch
 
 from ..models import wide_deep as wdm
 from ..ops import wd_general as wdg
+from ..privacy.spec import DPSpec
 from .fused_wide_deep import OptSpec, default_dnn_opt, default_wide_opt
 
 
@@ -24,13 +30,18 @@ class GeneralWideDeepTrainer:
     def __init__(self, model: wdm.WideDeepModel | None = None, batch: int = 40, device="cuda",
                  dnn_opt: OptSpec | None = None, wide_opt: OptSpec | None = None, loss_reduction: str = "sum",
                  grid: int | None = None, process_group=None, max_grid: int = 256, shuffle_seed: int = 0,
-                 feed_stride: int | None = None, feed_offset: int = 0):
+                 feed_stride: int | None = None, feed_offset: int = 0, dp: DPSpec | None = None):
         """grid: workgroups of the fused launch (default: one per 64-example tile, at most max_grid and at most what
         keeps grid x slab bytes inside the kernel's slab bound). shuffle_seed / feed_stride / feed_offset: the record
-        stream of csrc/feed.h, as FusedWideDeepTrainer."""
+        stream of csrc/feed.h, as FusedWideDeepTrainer. dp: per-example DP-SGD (privacy.DPSpec); None launches
+        exactly the non-private step."""
         self.device = torch.device(device)
         self.model = model or wdm.WideDeepModel()
         self.world = torch.distributed.get_world_size(process_group) if process_group is not None else 1
+        self.dp = dp
+        if dp is not None and self.world > 1:
+            raise ValueError(f"DP training is single-GPU: the clipped, noised step runs on the general fused kernel, "
+                             f"which has no data-parallel path (world = {self.world})")
         if self.world > 1:
             raise ValueError(f"general towers are single-GPU: hidden_units {list(self.model.cfg.hidden_units)} train "
                              f"on the general fused kernel, which has no data-parallel path (world = {self.world})")
@@ -39,6 +50,8 @@ class GeneralWideDeepTrainer:
         self.T = c["T"]
         self.kernel = "general"
         self.batch = int(batch)
+        if dp is not None:
+            dp.check_batch(self.batch)
         self.shuffle_seed = int(shuffle_seed)
         self.feed_stride = int(feed_stride) if feed_stride is not None else self.batch
         self.feed_offset = int(feed_offset)
@@ -70,6 +83,7 @@ class GeneralWideDeepTrainer:
         self.slab_loss = torch.zeros(self.grid, device=dev)
         self.scratch = torch.zeros(self.grid * lay.scratch, dtype=torch.int16, device=dev)
         self.grad = torch.empty(self.stride, device=dev)
+        self.norms = torch.zeros(self.batch, device=dev) if dp is not None else None
         self.h_dnn = self.dnn_opt.encode()
         self.h_wide = self.wide_opt.encode()
         self.records = None
@@ -141,12 +155,19 @@ class GeneralWideDeepTrainer:
     def _fwd_bwd(self) -> None:
         wdg.fused(self.records, self.n_data, self.batch, 0, self.step_ctr, self.wt, self.wide_weights, self.slab,
                   self.slab_loss, None, self.grad_scale, self.grid, True, self.layout.desc, self.desc_dev,
-                  self.scratch, self.layout.scratch, feed=self.feed_args())
+                  self.scratch, self.layout.scratch, feed=self.feed_args(),
+                  **({} if self.dp is None else {"l2_norm_clip": self.dp.l2_norm_clip, "norms_out": self.norms}))
+
+    def _dp_reduce(self, noise: bool):
+        """The dp argument of ops.wd_general.reduce_*: (noise stddev or None, grad_scale, seed)."""
+        if self.dp is None:
+            return None
+        return (self.dp.stddev if noise and self.dp.noise_multiplier > 0 else None, self.grad_scale, self.dp.seed)
 
     def _step_impl(self) -> None:
         self._fwd_bwd()
         wdg.reduce_apply(self.slab, self.grid, self.kind, self.param_sc, self.s0_sc, self.s1_sc, self.wt,
-                         self.step_ctr, self.h_dnn, self.h_wide)
+                         self.step_ctr, self.h_dnn, self.h_wide, dp=self._dp_reduce(True))
 
     def step(self) -> None:
         if self.records is None:
@@ -201,13 +222,24 @@ class GeneralWideDeepTrainer:
     def set_step(self, step: int) -> None:
         self.step_ctr.fill_(int(step))
 
-    def gradients_once(self) -> np.ndarray:
+    def last_norms(self) -> torch.Tensor:
+        """DP: the [batch] device buffer of per-example gradient L2 norms (before clipping) of the latest step or
+        gradients_once(), by position in the batch."""
+        if self.dp is None:
+            raise RuntimeError("last_norms() needs a trainer built with dp=DPSpec(...)")
+        return self.norms
+
+    def gradients_once(self, noise: bool = False) -> np.ndarray:
         """Forward / backward on the current batch WITHOUT updating; the summed slab row (index it with
-        `self.gidx_np` for the flat parameter order of models.wide_deep.pack_flat)."""
+        `self.gidx_np` for the flat parameter order of models.wide_deep.pack_flat). DP: the sum of the clipped
+        per-example gradients, with noise=True plus the noise the optimizer step at the current step would add."""
         if self.records is None:
             raise RuntimeError("call set_data() first")
+        if noise and self.dp is None:
+            raise ValueError("gradients_once(noise=True) needs a trainer built with dp=DPSpec(...)")
         self._fwd_bwd()
-        wdg.reduce_sum(self.slab, self.grid, self.grad)
+        wdg.reduce_sum(self.slab, self.grid, self.grad, dp=self._dp_reduce(noise), kind=self.kind,
+                       step_ctr=self.step_ctr)
         return self.grad.cpu().numpy()
 
     @torch.no_grad()
