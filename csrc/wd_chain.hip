@@ -22,7 +22,8 @@
 //    back with ds_read_b64_tr_b16; every wave owns a fixed set of 16x16 dW tiles and keeps their fp32
 //    accumulators in registers across ALL iterations (MFMA K-accumulation == batch reduction), so the
 //    workgroup writes one gradient slab at the end, in the same tile-native layout as wd_fused.
-//    The ReLU masks of the backward come from the staged activations (C order, 8-byte reads).
+//    The ReLU masks of the backward come from the activation fragments the wave still holds in registers, moved to
+//    the gradient tiles' lanes by two VALU lane swaps per register pair (mask_grad): no LDS read.
 //  * Only live tiles are computed. The model 3 -> 100 -> 70 -> 48 -> 34 -> 1 is padded to 32 -> 128 -> 96 -> 64 -> 64
 //    -> 16, and the padding fills whole trailing 16x16 tiles on every axis the kernel walks: natural n tiles in the
 //    forward (7, 5, 4, 3, 1 of 8, 6, 4, 4, 1), C-order k tiles in the activation gradient, the mask reads and the dW
@@ -33,7 +34,10 @@
 //  * Wide part: embedding-bag gather of 9 fp32 weights per example (issued before the forward), fixed-point
 //    LDS histogram for its gradient (order-independent -> deterministic), as in wd_fused.
 //
-// MIFX_HIPCC_FLAGS: -fno-honor-nans -fno-honor-infinities
+// -amdgpu-kernarg-preload-count: the first 14 argument dwords (data .. wide, what the prologue needs first) arrive
+// in SGPRs at wave launch instead of by a load every wave starts with; the compiler keeps a fall-back prologue
+// for firmware that does not preload.
+// MIFX_HIPCC_FLAGS: -fno-honor-nans -fno-honor-infinities -mllvm -amdgpu-kernarg-preload-count=14
 #include <hip/hip_runtime.h>
 #include "xcd.h"
 #include "feed.h"
@@ -337,25 +341,45 @@ __device__ __forceinline__ void bwd_dA(const uint16_t* W, const v4bf (&dz)[TBN][
   }
 }
 
-// ReLU mask of the layer input from the staged activation (C order) and bf16 pack of the gradient
-// (KTL live k tiles; the gradient of a dead tile is zero without reading its mask)
+// ReLU mask of the layer input from the wave's own activation fragments a[tb][s] (the registers stage() stores) and
+// bf16 pack of the gradient (KTL live k tiles; the gradient of a dead tile is zero without building its mask).
+// Lane (r, h) needs, for gradient tile kt = 2 s + b, the activations at C positions 16 kt + 4 h + {0..3}: the words
+// 2 (h & 1) + {0, 1} of a[tb][s] in lane (r, 2 b + (h >> 1)) -- a rotation of (word pair, lane bit 5, lane bit 4),
+// done on the VALU: v_permlane16_swap on words (j, j + 2) (rows 1, 3 of the first with rows 0, 2 of the second),
+// then v_permlane32_swap on the result (lanes 32-63 of the first with lanes 0-31 of the second). The first output
+// is word j of the mask for tile 2 s, the second for tile 2 s + 1: the same 8 bytes the staged row holds there.
+typedef unsigned int v2u __attribute__((ext_vector_type(2)));
+typedef unsigned int v4u __attribute__((ext_vector_type(4)));
 template <int K, int KTL, int TBN>
-__device__ __forceinline__ void mask_grad(const v4f (&g)[TBN][K / 16], const uint16_t* SA, int w, int r, int h,
+__device__ __forceinline__ void mask_grad(const v4f (&g)[TBN][K / 16], const v8bf (&a)[TBN][K / 32],
                                           v4bf (&dz)[TBN][K / 16]) {
-  const int rp = sperm16(r);
+  static_assert((K / 16) % 2 == 0, "k tiles come in pairs (one k-step)");
 #pragma unroll
   for (int tb = 0; tb < TBN; ++tb)
 #pragma unroll
-    for (int kt = 0; kt < K / 16; ++kt) {
-      if (kt >= KTL) {
-        dz[tb][kt] = (v4bf){(bf16)0.f, (bf16)0.f, (bf16)0.f, (bf16)0.f};
-        continue;
+    for (int s = 0; s < K / 32; ++s) {
+      unsigned int m[2][2];  // [tile of the k-step][word]
+      if (2 * s < KTL) {
+        const v4u aw = __builtin_bit_cast(v4u, a[tb][s]);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          const v2u p = __builtin_amdgcn_permlane16_swap(aw[j], aw[j + 2], false, false);
+          const v2u q = __builtin_amdgcn_permlane32_swap(p[0], p[1], false, false);
+          m[0][j] = q[0];
+          m[1][j] = q[1];  // (not used where the k-step's odd tile is dead: KTL odd)
+        }
       }
-      const int row = 16 * TBN * w + 16 * tb + rp;
-      const uint2 m = *(const uint2*)(SA + row * (K + PAD) + 16 * kt + 4 * h);
-      const unsigned int u[2] = {mask_pk(cvt_pk(g[tb][kt][0], g[tb][kt][1]), m.x),
-                                 mask_pk(cvt_pk(g[tb][kt][2], g[tb][kt][3]), m.y)};
-      dz[tb][kt] = __builtin_bit_cast(v4bf, u);
+#pragma unroll
+      for (int b = 0; b < 2; ++b) {
+        const int kt = 2 * s + b;
+        if (kt >= KTL) {
+          dz[tb][kt] = (v4bf){(bf16)0.f, (bf16)0.f, (bf16)0.f, (bf16)0.f};
+          continue;
+        }
+        const unsigned int u[2] = {mask_pk(cvt_pk(g[tb][kt][0], g[tb][kt][1]), m[b][0]),
+                                   mask_pk(cvt_pk(g[tb][kt][2], g[tb][kt][3]), m[b][1])};
+        dz[tb][kt] = __builtin_bit_cast(v4bf, u);
+      }
     }
 }
 
@@ -968,7 +992,7 @@ __global__ __launch_bounds__(64 * (T / (16 * TBN)), 1) void wdc_fused(const uint
 #pragma unroll
           for (int e = 0; e < 4; ++e) g[tb][kt][e] = w5[e] * dlb[tb];
       }
-      mask_grad<K5, KT5, TBN>(g, S5 + T * (N5 + PAD), w, r, h, dz4);
+      mask_grad<K5, KT5, TBN>(g, a4, dz4);
     }
     block_sync_lds();
     STAMP(6);
@@ -979,13 +1003,13 @@ __global__ __launch_bounds__(64 * (T / (16 * TBN)), 1) void wdc_fused(const uint
     // ---- layer 4
     STAMP(7);
     stage<K4, N4, TBN>(S4, dz4, a3, w, r, h);
-    // the activation gradient needs only the weights, this wave's dZ and its own staged rows (the relu mask):
-    // issued before the barrier so its MFMAs and weight reads overlap the other waves' staging
+    // the activation gradient needs only the weights, this wave's dZ and its input activations (the relu mask, from
+    // registers): issued before the barrier so its MFMAs and weight reads overlap the other waves' staging
     v4bf dz3[TBN][K4 / 16];
     {
       v4f g[TBN][K4 / 16];
       bwd_dA<K4, N4, KT4, KT5, TBN>(lds + PW4, dz4, g, r, h);
-      mask_grad<K4, KT4, TBN>(g, S4 + T * (N4 + PAD), w, r, h, dz3);
+      mask_grad<K4, KT4, TBN>(g, a3, dz3);
     }
     block_sync_lds();
     STAMP(8);
@@ -1000,7 +1024,7 @@ __global__ __launch_bounds__(64 * (T / (16 * TBN)), 1) void wdc_fused(const uint
     {  // (before the barrier, as in layer 4)
       v4f g[TBN][K3 / 16];
       bwd_dA<K3, N3, KT3, KT4, TBN>(lds + PW3, dz3, g, r, h);
-      mask_grad<K3, KT3, TBN>(g, S3 + T * (N3 + PAD), w, r, h, dz2);
+      mask_grad<K3, KT3, TBN>(g, a2, dz2);
     }
     block_sync_lds();
     STAMP(10);
@@ -1015,7 +1039,7 @@ __global__ __launch_bounds__(64 * (T / (16 * TBN)), 1) void wdc_fused(const uint
     {  // (before the barrier, as in layer 4)
       v4f g[TBN][K2 / 16];
       bwd_dA<K2, N2, KT2, KT3, TBN>(lds + PW2, dz2, g, r, h);
-      mask_grad<K2, KT2, TBN>(g, S2 + T * (N2 + PAD), w, r, h, dz1);
+      mask_grad<K2, KT2, TBN>(g, a1, dz1);
     }
     block_sync_lds();
     STAMP(12);

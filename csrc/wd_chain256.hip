@@ -8,6 +8,6 @@
 // of dW operands once, from where the dead weights begin (csrc/wd_chain.hip, "LDS placement"). Same global weight
 // image, tile map and gradient slab as the T = 128 library; exported names end in _t256.
 //
-// MIFX_HIPCC_FLAGS: -fno-honor-nans -fno-honor-infinities
+// MIFX_HIPCC_FLAGS: -fno-honor-nans -fno-honor-infinities -mllvm -amdgpu-kernarg-preload-count=14
 #define WDC_T 256
 #include "wd_chain.hip"

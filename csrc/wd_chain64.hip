@@ -5,6 +5,6 @@
 // barrier waits for 4 waves instead of 8. Same weight image, tile map and gradient slab as the T = 128 library;
 // exported names end in _t64.
 //
-// MIFX_HIPCC_FLAGS: -fno-honor-nans -fno-honor-infinities
+// MIFX_HIPCC_FLAGS: -fno-honor-nans -fno-honor-infinities -mllvm -amdgpu-kernarg-preload-count=14
 #define WDC_T 64
 #include "wd_chain.hip"

@@ -32,9 +32,10 @@
 //    re-emits the bf16 weight image. A device-side step counter drives the data offset so
 //    the whole step is hipGraph-capturable.
 //
-// MIFX_HIPCC_FLAGS: -fno-honor-nans -fno-honor-infinities -mllvm -amdgpu-mfma-vgpr-form
+// MIFX_HIPCC_FLAGS: -fno-honor-nans -fno-honor-infinities -mllvm -amdgpu-mfma-vgpr-form -mllvm -amdgpu-kernarg-preload-count=14
 // (no NaN canonicalisation v_max before every ReLU; MFMA results in VGPRs instead of
-//  AGPR->VGPR copies feeding the epilogues)
+//  AGPR->VGPR copies feeding the epilogues; the first 14 kernel-argument dwords preloaded into SGPRs at wave
+//  launch -- the step's tail kernels wd_reduce_res / wd_res_opt_sc start without the argument load)
 #include <hip/hip_runtime.h>
 #include "feed.h"
 #include <stdlib.h>
