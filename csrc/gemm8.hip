@@ -255,7 +255,7 @@ __device__ __forceinline__ void gemm8_tile(const bf16* __restrict__ X, const bf1
   if constexpr (CV == 2) {
 #pragma unroll
     for (int i = 0; i < WR; ++i) {
-      const int qq = i * NT + tid, t = qq / CPB, pc = qq % CPB;
+      const int qq = WDUP ? tid % BDMA : i * NT + tid, t = qq / CPB, pc = qq % CPB;  // (narrow: as boff above)
       int c = pc - rot<CPB>(t);
       c = c < 0 ? c + CPB : c;
       btok[i] = t;
@@ -309,9 +309,11 @@ __device__ __forceinline__ void gemm8_tile(const bf16* __restrict__ X, const bf1
         const bool ok = (unsigned)ih < (unsigned)geo.H && (unsigned)iw < (unsigned)geo.W;
         const bf16* src =
             ok ? W + ((size_t)((nb * geo.H + ih) * geo.W + iw) << geo.cshift) + c0 + bcol[i] : g_zero_page;
-        __builtin_amdgcn_global_load_lds((const void*)src,
-                                         (__attribute__((address_space(3))) void*)(dst + (i * NT + 64 * w) * 16), 16,
-                                         0, 0);
+        // (narrow B half: waves 4-7 re-issue waves 0-3's DMAs -- same token rows, same LDS bytes -- not the next
+        // K-tile's rows into the A half behind it)
+        __builtin_amdgcn_global_load_lds(
+            (const void*)src,
+            (__attribute__((address_space(3))) void*)(dst + (WDUP ? (64 * w) % BDMA : i * NT + 64 * w) * 16), 16, 0, 0);
       }
       return;
     }

@@ -263,7 +263,8 @@ def test_proj_pair_matches_separate_convs(couple, stride, cin, cs, c1):
         torch.testing.assert_close(got, want, rtol=5e-2, atol=5e-2 * want.abs().max().item())
 
 
-@pytest.mark.parametrize("nb,h,cin,cout", [(4, 16, 256, 512), (2, 15, 128, 256), (8, 16, 512, 1024)])
+@pytest.mark.parametrize("nb,h,cin,cout", [(4, 16, 256, 512), (2, 15, 128, 256), (8, 16, 512, 1024),
+                                           (128, 14, 128, 256), (8, 56, 64, 128)])
 def test_strided_1x1_center_tap(nb, h, cin, cout):
     """Strided 1x1 convolution as the center tap of the implicit 3x3 GEMM (csrc/gemm8.hip, tap0 = 4): output and
     per-tile BatchNorm statistics against an fp32 conv2d(stride 2), odd input sizes included."""
@@ -279,17 +280,15 @@ def test_strided_1x1_center_tap(nb, h, cin, cout):
     torch.testing.assert_close(part[0].double().mean(0), y.float().double().mean(0), rtol=1e-5, atol=1e-5)
 
 
-def test_proj_pair_deferred_shortcut_weight_grad():
-    """Inside deferred_weight_grads(): the shortcut's weight gradient is recorded with the center-tap geometry and
-    computed by the grouped TN flush -- equal to the fp32 reference (and the node's other gradients unchanged)."""
+def _proj_pair_deferred_shortcut_weight_grad(nb, hw):
     from mifx.ops import gemm as hg
     from mifx.ops.conv1x1 import proj_pair
 
     torch.manual_seed(6)
-    x = _x(4, 256, 16, 16, 31).requires_grad_()
+    x = _x(nb, 256, hw, hw, 31).requires_grad_()
     wsc = (torch.randn(512, 256, 1, 1, device="cuda") * 256 ** -0.5).requires_grad_()
     w1 = (torch.randn(256, 256, 1, 1, device="cuda") * 256 ** -0.5).requires_grad_()
-    gsc, g1 = _x(4, 512, 8, 8, 32), _x(4, 256, 16, 16, 33)
+    gsc, g1 = _x(nb, 512, hw // 2, hw // 2, 32), _x(nb, 256, hw, hw, 33)
     before = len(hg._DEFER["pending_f32"])
     with hg.deferred_weight_grads():
         sc, y1, _ = proj_pair(x, wsc, 2, w1)
@@ -304,3 +303,14 @@ def test_proj_pair_deferred_shortcut_weight_grad():
     torch.testing.assert_close(sc.float(), scr, rtol=3e-2, atol=3e-2)
     for got, want in ((wsc.grad, ar.grad), (w1.grad, br.grad), (x.grad.float(), xr.grad)):
         torch.testing.assert_close(got, want, rtol=3e-2, atol=3e-2 * want.abs().max().item())
+
+
+def test_proj_pair_deferred_shortcut_weight_grad():
+    """Inside deferred_weight_grads(): the shortcut's weight gradient is recorded with the center-tap geometry and
+    computed by the grouped TN flush -- equal to the fp32 reference (and the node's other gradients unchanged)."""
+    _proj_pair_deferred_shortcut_weight_grad(4, 16)
+
+
+def test_proj_pair_deferred_shortcut_weight_grad_14_to_7():
+    """As above at the workload's 14 -> 7 (49-pixel output images: the token chunks start mid-image)."""
+    _proj_pair_deferred_shortcut_weight_grad(128, 14)

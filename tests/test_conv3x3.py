@@ -25,7 +25,11 @@ def _w(cout, cin, seed):
 
 @pytest.mark.parametrize("n,cin,hw,cout,stride", [(4, 128, 16, 128, 1), (4, 128, 16, 256, 1), (2, 256, 16, 128, 1),
                                                    (4, 128, 32, 128, 2), (2, 256, 16, 256, 2), (8, 512, 4, 512, 1),
-                                                   (4, 256, 16, 256, 1), (8, 512, 8, 512, 2)])
+                                                   (4, 256, 16, 256, 1), (8, 512, 8, 512, 2),
+                                                   # the workload's 14 / 7 images: tiles and the deferred weight
+                                                   # gradient's 2048-pixel chunks start mid-row and mid-image
+                                                   (32, 128, 14, 128, 1), (128, 128, 7, 128, 1),
+                                                   (128, 128, 14, 128, 2), (32, 256, 14, 256, 1)])
 def test_conv3x3_forward_stats_backward(n, cin, hw, cout, stride):
     from mifx.ops import gemm as hg
     from mifx.ops.conv3x3 import conv3x3, eligible
