@@ -14,12 +14,17 @@
 //  * determinism: ties go to the lowest feature, then the lowest cut; histograms are summed in row order, so a
 //    model is bit-reproducible for any thread count (threads split the features, never the rows of one feature).
 // Rows of a node are a contiguous range of one permutation array, partitioned in place after each split.
+//
+// mifx_gbdt_grow_fixed is the same learner on fixed-point (int64) histograms with the split rule of gbdt_split.h:
+// the host twin of the device learner in gbdt_gpu.hip (larger tables, device="gpu"), which it reproduces bit for bit.
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <thread>
 #include <vector>
+
+#include "gbdt_split.h"
 
 namespace {
 
@@ -245,6 +250,147 @@ int mifx_gbdt_grow(const uint16_t* bins, long n, int f, const int* nbins, const 
         for (int k = 0; k < hsize; ++k) {
           large.hist[k].g -= small.hist[k].g;
           large.hist[k].h -= small.hist[k].h;
+        }
+      }
+      next.push_back(std::move(L));
+      next.push_back(std::move(R));
+    }
+    level = std::move(next);
+  }
+  return count;
+}
+
+// ---- fixed-point twin of mifx_gbdt_grow (gbdt_split.h): int64 histograms, so the tree cannot depend on the order
+// of any sum -- the host reference that the device learner (csrc/gbdt_gpu.hip) reproduces bit for bit.
+
+int mifx_gbdt_quant_exp(double amax, long n) { return mifx_gb_quant_exp(amax, n); }
+
+// mifx_gbdt_grow's signature and outputs; the semantics are the fixed-point ones of gbdt_split.h. On gradients that
+// quantise exactly and sum exactly in double (small dyadic rationals) it grows exactly mifx_gbdt_grow's tree.
+int mifx_gbdt_grow_fixed(const uint16_t* bins, long n, int f, const int* nbins, const float* g, const float* h,
+                         int max_depth, double min_child_weight, double lambda, double gamma, double eta, int threads,
+                         int max_nodes, int* feature, int* split_bin, uint8_t* default_left, int* left, int* right,
+                         double* value, int* leaf_of_row) {
+  struct QNode {
+    int begin, end, depth, id;
+    long long g, h;
+    std::vector<long long> hg, hh;  // [features][nbins + 1], the last slot is "missing"
+    std::vector<int> hc;            // rows per slot
+  };
+  const MifxGbParams prm{lambda, gamma, min_child_weight, eta};
+  std::vector<int> off(f + 1, 0);
+  for (int j = 0; j < f; ++j) off[j + 1] = off[j] + nbins[j] + 1;
+  const int hsize = off[f];
+  std::vector<int> rows(n);
+  for (long i = 0; i < n; ++i) rows[i] = (int)i;
+  const int th = n * (long)f > 200000 ? threads : 1;
+
+  // quantisation: the largest magnitudes (max is order-independent), one exponent each, then the rows
+  auto amax = [&](const float* v) {
+    double a = 0.0;
+    for (long i = 0; i < n; ++i) {
+      const double x = std::fabs((double)v[i]);
+      if (!(x <= a)) a = x;  // a NaN sticks: the exponent is then 0
+      if (std::isnan(x)) return x;
+    }
+    return a;
+  };
+  const int eg = mifx_gb_quant_exp(amax(g), n), eh = mifx_gb_quant_exp(amax(h), n);
+  std::vector<long long> qg(n), qh(n);
+  for (long i = 0; i < n; ++i) {
+    qg[i] = mifx_gb_quantise(g[i], eg);
+    qh[i] = mifx_gb_quantise(h[i], eh);
+  }
+
+  auto build = [&](QNode& nd) {
+    nd.hg.assign(hsize, 0);
+    nd.hh.assign(hsize, 0);
+    nd.hc.assign(hsize, 0);
+    parallel_for(f, th, [&](int j) {
+      const uint16_t* bj = bins + (size_t)j * n;
+      const int nb = nbins[j];
+      for (int k = nd.begin; k < nd.end; ++k) {
+        const int r = rows[k];
+        const uint16_t b = bj[r];
+        const int s = off[j] + ((int)b < nb ? (int)b : nb);  // 0xFFFF, or anything past the bins: missing
+        nd.hg[s] += qg[r];
+        nd.hh[s] += qh[r];
+        nd.hc[s] += 1;
+      }
+    });
+  };
+  auto best_split = [&](const QNode& nd) {
+    std::vector<MifxGbSplit> per(f);
+    const double parent = mifx_gb_parent_score(nd.g, nd.h, eg, eh, prm);
+    parallel_for(f, th, [&](int j) {
+      MifxGbSplit bs = mifx_gb_no_split();
+      mifx_gb_scan(nd.hg.data() + off[j], nd.hh.data() + off[j], nd.hc.data() + off[j], nbins[j], 0, nbins[j], 0, 0,
+                   0, nd.g, nd.h, eg, eh, j, prm, parent, &bs);
+      per[j] = bs;
+    });
+    MifxGbSplit best = mifx_gb_no_split();
+    for (int j = 0; j < f; ++j)
+      if (mifx_gb_feature_wins(per[j], best)) best = per[j];
+    return best;
+  };
+
+  int count = 0;
+  auto new_node = [&]() -> int {
+    if (count >= max_nodes) return -1;
+    feature[count] = -1;
+    split_bin[count] = -1;
+    default_left[count] = 0;
+    left[count] = right[count] = -1;
+    value[count] = 0.0;
+    return count++;
+  };
+  QNode root{0, (int)n, 0, new_node(), 0, 0, {}, {}, {}};
+  if (root.id < 0) return -1;
+  for (long i = 0; i < n; ++i) {
+    root.g += qg[i];
+    root.h += qh[i];
+  }
+  if (max_depth > 0) build(root);
+  std::vector<QNode> level;
+  level.push_back(std::move(root));
+  while (!level.empty()) {
+    std::vector<QNode> next;
+    for (QNode& nd : level) {
+      MifxGbSplit s = mifx_gb_no_split();
+      if (nd.depth < max_depth && nd.end - nd.begin >= 2) s = best_split(nd);
+      if (mifx_gb_is_leaf(s)) {
+        value[nd.id] = mifx_gb_leaf_value(nd.g, nd.h, eg, eh, prm);
+        for (int k = nd.begin; k < nd.end; ++k) leaf_of_row[rows[k]] = nd.id;
+        continue;
+      }
+      const uint16_t* bj = bins + (size_t)s.feature * n;
+      const int nb = nbins[s.feature];
+      auto goes_left = [&](int r) {
+        const int b = bj[r];
+        return b < nb ? b <= s.bin : s.default_left != 0;
+      };
+      const int mid = (int)(std::stable_partition(rows.begin() + nd.begin, rows.begin() + nd.end, goes_left) -
+                            rows.begin());
+      const int li = new_node(), ri = new_node();
+      if (li < 0 || ri < 0) return -1;
+      feature[nd.id] = s.feature;
+      split_bin[nd.id] = s.bin;
+      default_left[nd.id] = (uint8_t)s.default_left;
+      left[nd.id] = li;
+      right[nd.id] = ri;
+      QNode L{nd.begin, mid, nd.depth + 1, li, s.gl, s.hl, {}, {}, {}};
+      QNode R{mid, nd.end, nd.depth + 1, ri, nd.g - s.gl, nd.h - s.hl, {}, {}, {}};
+      if (nd.depth + 1 < max_depth) {  // smaller child built, larger = parent - smaller (identical in integers)
+        QNode& small = (L.end - L.begin) <= (R.end - R.begin) ? L : R;
+        QNode& large = &small == &L ? R : L;
+        build(small);
+        large.hg = std::move(nd.hg);
+        large.hh = std::move(nd.hh);
+        large.hc = std::move(nd.hc);
+        for (int k = 0; k < hsize; ++k) {
+          large.hg[k] -= small.hg[k];
+          large.hh[k] -= small.hh[k];
+          large.hc[k] -= small.hc[k];
         }
       }
       next.push_back(std::move(L));

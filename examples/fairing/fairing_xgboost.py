@@ -1,6 +1,8 @@
 """XGBoost-style regressor trained through the fairing config (reference:
 `kubeflow-pipelines/fairing/fairing_xgboost.py`). The Ames-housing download is unavailable offline,
-so a synthetic table of the same shape (1460 rows, 36 numeric features) is used."""
+so a synthetic table of the same shape (1460 rows, 36 numeric features) is used.
+`--device gpu` trains on the device learner (csrc/gbdt_gpu.hip); the default is the host learner."""
+import argparse
 import logging
 import os
 import sys
@@ -24,9 +26,9 @@ def read_input(test_size=TEST_FRACTION_SIZE):
     return (X[:n], y[:n]), (X[n:], y[n:])
 
 
-def run_training_and_eval():
+def run_training_and_eval(device="cpu"):
     (tx, ty), (vx, vy) = read_input()
-    model = XGBRegressor(n_estimators=ESTIMATORS, learning_rate=LEARNING_RATE)
+    model = XGBRegressor(n_estimators=ESTIMATORS, learning_rate=LEARNING_RATE, device=device)
     model.fit(tx, ty, early_stopping_rounds=EARLY_STOPPING_ROUNDS, eval_set=[(vx, vy)])
     logging.info("Best RMSE on eval: %.2f with %d rounds", model.best_score, model.best_iteration + 1)
     mae = mean_absolute_error(model.predict(vx), vy)
@@ -35,6 +37,9 @@ def run_training_and_eval():
 
 
 if __name__ == "__main__":
+    ap = argparse.ArgumentParser(description=__doc__)
+    ap.add_argument("--device", default="cpu", help="cpu (default), gpu, cuda or cuda:N")
+    args = ap.parse_args()
     fairing.config.set_builder("append", base_image="rocm/pytorch:latest", registry="local", push=False)
     fairing.config.set_deployer("local")
-    print(fairing.config.fn(run_training_and_eval)())
+    print(fairing.config.fn(run_training_and_eval)(args.device))

@@ -8,7 +8,14 @@ eval set; with early stopping, training stops after `early_stopping_rounds` roun
 `predict` uses the trees up to `best_iteration` (XGBoost >= 1.4's default `iteration_range`). Defaults are
 XGBoost >= 1.0's (learning_rate 0.3, max_depth 6, reg_lambda 1, min_child_weight 1, gamma 0, 256 bins); the
 intercept is the training mean (regression) or its log-odds (classification), XGBoost 2's `base_score` estimate.
-Binary classification only (the reference has no multi-class GBDT)."""
+Binary classification only (the reference has no multi-class GBDT).
+
+`device="gpu"` (or "cuda", "cuda:N") trains on the device learner of csrc/gbdt_gpu.hip: gradients, fixed-point int64
+histograms, split search, row partition and margin updates stay resident on the GPU for the whole fit; cuts and
+binning stay on the host (exact, once). `fixed_point=True` selects the fixed-point semantics of csrc/gbdt_split.h
+(the GPU's only mode, the CPU's option): histograms are integer sums, so a model is bit-reproducible for any thread
+count AND any launch geometry, and `device="cpu", fixed_point=True` is the host twin that reproduces a GPU-trained
+model bit for bit. The default (`device=None`, double histograms on the host) is unchanged."""
 from __future__ import annotations
 
 import ctypes
@@ -37,13 +44,27 @@ def _lib():
                                    _I, _I, _U8, _I, _I, _D, _I]
     lib.mifx_gbdt_predict.argtypes = [_D, ctypes.c_long, ctypes.c_int, ctypes.c_int, _I, _I, _D, _U8, _I, _I, _D,
                                       ctypes.c_double, _D, ctypes.c_int]
-    for f in (lib.mifx_gbdt_cuts, lib.mifx_gbdt_bin, lib.mifx_gbdt_grow, lib.mifx_gbdt_predict):
+    lib.mifx_gbdt_grow_fixed.argtypes = lib.mifx_gbdt_grow.argtypes
+    lib.mifx_gbdt_quant_exp.argtypes = [ctypes.c_double, ctypes.c_long]
+    for f in (lib.mifx_gbdt_cuts, lib.mifx_gbdt_bin, lib.mifx_gbdt_grow, lib.mifx_gbdt_predict,
+              lib.mifx_gbdt_grow_fixed, lib.mifx_gbdt_quant_exp):
         f.restype = ctypes.c_int
     return lib
 
 
 def _p(a: np.ndarray, t):
     return a.ctypes.data_as(t)
+
+
+def _parse_device(device):
+    """None / "cpu" -> None; "gpu" / "cuda" / "cuda:N" -> the GPU index."""
+    if device is None or device == "cpu":
+        return None
+    if device in ("gpu", "cuda"):
+        return 0
+    if isinstance(device, str) and device.startswith("cuda:") and device[5:].isdigit():
+        return int(device[5:])
+    raise ValueError(f"device must be None, 'cpu', 'gpu', 'cuda' or 'cuda:N' (one GPU), got {device!r}")
 
 
 def _threads() -> int:
@@ -56,13 +77,23 @@ class _Base:
     def __init__(self, n_estimators: int = 100, learning_rate: float = 0.3, max_depth: int = 6,
                  min_child_weight: float = 1.0, reg_lambda: float = 1.0, gamma: float = 0.0, max_bins: int = 256,
                  base_score: float | None = None, n_jobs: int | None = None, random_state: int = 0,
-                 verbosity: int = 0):
+                 verbosity: int = 0, device: str | None = None, fixed_point: bool | None = None):
         self.n_estimators, self.learning_rate, self.max_depth = n_estimators, learning_rate, max_depth
         self.min_child_weight, self.reg_lambda, self.gamma, self.max_bins = min_child_weight, reg_lambda, gamma, max_bins
         self.base_score, self.n_jobs = base_score, n_jobs
         self.random_state, self.verbosity = random_state, verbosity  # (the learner is deterministic: no sampling)
         self.best_iteration, self.best_score, self.evals_result_ = None, None, {}
         self._trees: list[tuple] = []
+        self.device, self.fixed_point = device, fixed_point
+        if _parse_device(device) is not None and fixed_point is not None and not fixed_point:
+            raise ValueError("device='gpu' trains in fixed point only (fixed_point=False is the host's double learner)")
+
+    def _gpu_index(self):
+        return _parse_device(getattr(self, "device", None))
+
+    def _fixed(self) -> bool:
+        fp = getattr(self, "fixed_point", None)
+        return self._gpu_index() is not None if fp is None else bool(fp)
 
     # ---- loss (overridden by the classifier)
     def _base(self, y: np.ndarray) -> float:
@@ -111,11 +142,12 @@ class _Base:
         fe, sb, left, right = (np.empty(cap, np.int32) for _ in range(4))
         dl = np.empty(cap, np.uint8)
         val = np.empty(cap, np.float64)
-        cnt = _lib().mifx_gbdt_grow(_p(bins, _U16), n, bins.shape[0], _p(nbins, _I), _p(g, _F), _p(h, _F),
-                                    int(self.max_depth), float(self.min_child_weight), float(self.reg_lambda),
-                                    float(self.gamma), float(self.learning_rate), self._nthreads(), cap, _p(fe, _I),
-                                    _p(sb, _I), _p(dl, _U8), _p(left, _I), _p(right, _I), _p(val, _D),
-                                    _p(leaf_of_row, _I))
+        grow = _lib().mifx_gbdt_grow_fixed if self._fixed() else _lib().mifx_gbdt_grow
+        cnt = grow(_p(bins, _U16), n, bins.shape[0], _p(nbins, _I), _p(g, _F), _p(h, _F),
+                   int(self.max_depth), float(self.min_child_weight), float(self.reg_lambda),
+                   float(self.gamma), float(self.learning_rate), self._nthreads(), cap, _p(fe, _I),
+                   _p(sb, _I), _p(dl, _U8), _p(left, _I), _p(right, _I), _p(val, _D),
+                   _p(leaf_of_row, _I))
         if cnt < 0:
             raise RuntimeError("tree exceeded its node capacity")
         thr = np.zeros(cnt, np.float64)
@@ -130,6 +162,8 @@ class _Base:
         if X.ndim != 2 or len(X) != len(y):
             raise ValueError("X must be [n, features] with one label per row")
         self._nfeat = X.shape[1]
+        if self._gpu_index() is not None:
+            return self._fit_gpu(X, y, eval_set, early_stopping_rounds, verbose)
         bins = self._bin_matrix(X)
         nbins = (self._ncut + 1).astype(np.int32)
         self._base_margin = float(self.base_score) if self.base_score is not None else self._base(y)
@@ -166,6 +200,74 @@ class _Base:
         self.evals_result_ = {"validation_0": {self._metric_name(): hist}} if ev is not None else {}
         # XGBoost's sklearn API sets best_iteration / best_score only under early stopping; without it predict uses
         # every tree even when an eval_set was given
+        self.best_score, self.best_iteration = (best, best_it) if ev is not None and early_stopping_rounds else \
+            (None, None)
+        return self
+
+    def _fit_gpu(self, X, y, eval_set, early_stopping_rounds, verbose):
+        """The boosting loop on the device learner (mifx/ops/gbdt_gpu.py): cuts and binning on the host, once; then
+        gradients, trees and margins stay on the GPU. With an eval set its margins come back once per round for the
+        metric (the host's own numpy metric, so the scores are the host twin's bit for bit); the trees come back once
+        at the end. Leaves the attributes of the host path."""
+        import torch
+
+        from ..ops import gbdt_gpu as G
+
+        G.check_limits(len(y), int(self.max_bins), int(self.max_depth))
+        dev = G.device_for(self._gpu_index())
+        bins = self._bin_matrix(X)
+        nbins = (self._ncut + 1).astype(np.int32)
+        self._base_margin = float(self.base_score) if self.base_score is not None else self._base(y)
+        if self._objective != "reg:squarederror" and self.base_score is not None:
+            self._base_margin = float(np.log(self.base_score / (1 - self.base_score)))
+        rounds = int(self.n_estimators)
+        with torch.cuda.device(dev):
+            bst = G.Booster(bins, nbins, int(self.max_depth), dev)
+            yd = torch.from_numpy(y).to(dev)
+            margin = torch.full((len(y),), self._base_margin, dtype=torch.float64, device=dev)
+            g, h = (torch.empty(len(y), dtype=torch.float32, device=dev) for _ in range(2))
+            trees = bst.new_trees(max(1, rounds))
+            ev = None
+            if eval_set:
+                ex, ey = eval_set[-1]
+                ex = np.ascontiguousarray(np.asarray(ex, dtype=np.float64))
+                ey = self._check_y(np.asarray(ey).reshape(-1))
+                if ex.ndim != 2 or ex.shape[1] != self._nfeat or len(ex) != len(ey) or not len(ey):
+                    raise ValueError(f"the eval set must be [m, {self._nfeat}] with one label per row")
+                ebins = np.empty((self._nfeat, len(ex)), np.uint16)
+                _lib().mifx_gbdt_bin(_p(ex, _D), len(ex), self._nfeat, _p(self._cut_flat, _D), _p(self._cut_off, _I),
+                                     _p(self._ncut, _I), _p(ebins, _U16), self._nthreads())
+                ev = (G.upload_bins(ebins, dev), ey,
+                      torch.full((len(ey),), self._base_margin, dtype=torch.float64, device=dev))
+            best, best_it, since, hist, done = None, 0, 0, [], 0
+            for it in range(rounds):
+                tree = tuple(t[it] for t in trees)
+                G.grad_hess(self._objective, margin, yd, g, h)
+                bst.grow(g, h, tree, self.min_child_weight, self.reg_lambda, self.gamma, self.learning_rate, margin)
+                done = it + 1
+                if ev is not None:
+                    bst.apply(ev[0], tree, ev[2])
+                    score = self._metric(ev[2].cpu().numpy(), ev[1])  # the round's one read-back
+                    hist.append(score)
+                    if verbose:
+                        logging.info("[%d]\tvalidation_0-%s:%.5f", it, self._metric_name(), score)
+                    if best is None or score < best:
+                        best, best_it, since = score, it, 0
+                    else:
+                        since += 1
+                        if early_stopping_rounds and since >= early_stopping_rounds:
+                            break
+            fe, sb, dl, le, ri, val, cnt = (t[:done].cpu().numpy() for t in trees)
+        self._trees = []
+        for t in range(done):
+            c = int(cnt[t])
+            thr = np.zeros(c, np.float64)
+            for k in range(c):  # the split's cut value: bin <= b  <=>  x < cuts[b]
+                if fe[t, k] >= 0:
+                    thr[k] = self._cuts[fe[t, k]][sb[t, k]]
+            self._trees.append((fe[t, :c].copy(), thr, dl[t, :c].copy(), le[t, :c].copy(), ri[t, :c].copy(),
+                                val[t, :c].copy()))
+        self.evals_result_ = {"validation_0": {self._metric_name(): hist}} if ev is not None else {}
         self.best_score, self.best_iteration = (best, best_it) if ev is not None and early_stopping_rounds else \
             (None, None)
         return self
