@@ -1,0 +1,280 @@
+// Feature preparation and prediction of mifx.gbdt on the device: quantile cuts from a sorted column, binning of the
+// raw table, and forest prediction on raw features. Each is bit-identical to its host function in gbdt.cpp
+// (mifx_gbdt_cuts under ==, mifx_gbdt_bin, mifx_gbdt_predict); nothing here depends on launch geometry.
+// MIFX_HIPCC_FLAGS: -ffp-contract=off
+//
+//   cuts     The host rule is a serial state machine over the distinct values of the sorted column v[0..m). Its
+//            equivalent without serial state: with D distinct values, D <= max_bins keeps every distinct value but the
+//            first; otherwise cut k (k = 1 .. max_bins - 1) is v[p], p = upper_bound(v, v[r - 1]),
+//            r = max(1, ceil(k m / max_bins)), if p < m, repeats of one p dropped.
+//            k_cut_mark counts the positions that start a run of equal values (wave-aggregated integer atomics) and
+//            records the first kCutSlots of them, in whatever order the atomics land; k_cut_pick (one workgroup)
+//            either ranks the recorded positions (D <= max_bins: all of them were recorded, and a set has one sorted
+//            order) or runs the max_bins - 1 independent binary searches.
+//   bins     k_bin: one workgroup per (row chunk, feature tile); the tile's cut tables are staged in LDS
+//            (32 features x 255 cuts x 8 B = 65,280 B), bin = number of cuts <= x by binary search, NaN -> 0xFFFF.
+//            Output row-major [n, f] uint16, the layout the learner (gbdt_gpu.hip) reads.
+//   predict  k_predict: one row per thread; the forest is walked in tree order from packed 24-byte nodes, staged
+//            through LDS in chunks of whole consecutive trees (a tree larger than a chunk is walked from global
+//            memory). One double per row, additions only, in the host's order.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace {
+
+constexpr int kMaxBins = 256;               // cuts: max_bins <= 256, so at most 255 cuts per feature
+constexpr int kMaxCuts = kMaxBins - 1;
+constexpr int kCutSlots = kMaxBins + 1;     // run starts recorded per column: enough to tell D <= max_bins apart
+constexpr int kMaxFeatTile = 32;            // 32 * 255 * 8 B = 65,280 B of LDS
+constexpr int kMaxRowsPerWg = 1 << 20;
+constexpr int kMarkThreads = 256;
+constexpr int kBinThreads = 512;
+constexpr int kPredictThreads = 256;
+constexpr int kMaxChunkNodes = 2730;        // 2730 * 24 B = 65,520 B of LDS
+
+typedef unsigned long long u64;
+
+struct PackedNode {  // 24 bytes; built once per model (mifx/ops/gbdt_prep.py)
+  double v;          // inner node: the threshold (left iff x < v); leaf: the value
+  int feature;       // < 0: leaf
+  int left, right;   // local to the tree
+  int default_left;
+};
+
+// ---- cuts
+
+// state[0] = D, the number of run starts in v[0, m); pos[s] for s < min(D, kCutSlots): run-start positions, unordered
+__global__ __launch_bounds__(kMarkThreads) void k_cut_mark(const double* v, long n, const long long* nan_count,
+                                                           u64* state, long long* pos) {
+  const long m = n - (long)*nan_count;
+  const int lane = threadIdx.x & 63;
+  // Slots matter only while the count is below kCutSlots, and it never falls: a wave that has seen it there stops
+  // drawing slots and adds its own count once at the end (a column of distinct values would otherwise send one
+  // atomic per wave and 64 rows to a single word). Every quantity below but `start` and `i` is wave-uniform.
+  bool slots = true;
+  u64 pending = 0;
+  for (long base = (long)blockIdx.x * kMarkThreads; base < m; base += (long)gridDim.x * kMarkThreads) {
+    const long i = base + threadIdx.x;
+    const bool start = i < m && (i == 0 || v[i] != v[i - 1]);
+    const u64 mask = __ballot(start);
+    if (mask == 0) continue;
+    if (!slots) {
+      pending += __popcll(mask);
+      continue;
+    }
+    const int leader = __ffsll((long long)mask) - 1;
+    u64 first = 0;
+    if (lane == leader) first = atomicAdd(&state[0], (u64)__popcll(mask));
+    first = __shfl(first, leader);
+    const u64 slot = first + __popcll(mask & (((u64)1 << lane) - 1));
+    if (start && slot < (u64)kCutSlots) pos[slot] = i;
+    slots = first + __popcll(mask) < (u64)kCutSlots;
+  }
+  if (pending && lane == 0) atomicAdd(&state[0], pending);
+}
+
+// one workgroup of kMaxBins threads: cuts[0 .. count) and *count from the state k_cut_mark left
+__global__ __launch_bounds__(kMaxBins) void k_cut_pick(const double* v, long n, const long long* nan_count,
+                                                       int max_bins, const u64* state, const long long* pos,
+                                                       double* cuts, int* count) {
+  __shared__ long long sp[kCutSlots];
+  __shared__ int keep[kMaxBins];
+  const long m = n - (long)*nan_count;
+  const u64 D = state[0];
+  const int t = threadIdx.x;
+  if (m <= 0) {
+    if (t == 0) *count = 0;
+    return;
+  }
+  if (D <= (u64)max_bins) {  // one bin per distinct value: the run starts in ascending order, without the first
+    const int d = (int)D;
+    for (int s = t; s < d; s += kMaxBins) sp[s] = pos[s];
+    __syncthreads();
+    for (int s = t; s < d; s += kMaxBins) {
+      const long long p = sp[s];
+      int rank = 0;
+      for (int q = 0; q < d; ++q) rank += sp[q] < p;
+      if (rank > 0 && p >= 0 && p < m) cuts[rank - 1] = v[p];
+    }
+    if (t == 0) *count = d - 1;
+    return;
+  }
+  // count quantiles: thread k - 1 searches for cut k
+  const int k = t + 1;
+  long p = m;
+  if (k < max_bins) {
+    const double total = (double)m;
+    const double q = k * total / max_bins;  // the host's expression, in its operation order
+    long r = (long)ceil(q);
+    r = r < 1 ? 1 : (r > m ? m : r);
+    const double a = v[r - 1];
+    long lo = r, hi = m;  // upper_bound(v, a): the first index holding a greater value; v[r - 1] == a, so it is >= r
+    while (lo < hi) {
+      const long mid = lo + (hi - lo) / 2;
+      if (v[mid] <= a) lo = mid + 1; else hi = mid;
+    }
+    p = lo;
+  }
+  sp[t] = p;
+  __syncthreads();
+  const bool kept = k < max_bins && p < m && (t == 0 || sp[t - 1] != p);
+  keep[t] = kept;
+  __syncthreads();
+  int rank = 0;
+  for (int q = 0; q < t; ++q) rank += keep[q];
+  if (kept) cuts[rank] = v[p];
+  if (t == kMaxBins - 1) *count = rank + (kept ? 1 : 0);
+}
+
+// ---- bins
+
+template <class T>
+__global__ __launch_bounds__(kBinThreads) void k_bin(const T* X, long n, int f, const double* cut_flat,
+                                                     const int* cut_off, const int* ncut, uint16_t* bins,
+                                                     int rows_per_wg, int feat_tile) {
+  extern __shared__ double lds_cuts[];  // the tile's tables back to back
+  __shared__ int loff[kMaxFeatTile + 1];
+  const int j0 = blockIdx.y * feat_tile;
+  const int tw = min(feat_tile, f - j0);
+  if (threadIdx.x == 0) {
+    int o = 0;
+    for (int jj = 0; jj < tw; ++jj) {
+      loff[jj] = o;
+      o += min(max(ncut[j0 + jj], 0), kMaxCuts);
+    }
+    loff[tw] = o;
+  }
+  __syncthreads();
+  for (int jj = 0; jj < tw; ++jj) {
+    const double* src = cut_flat + cut_off[j0 + jj];
+    const int c = loff[jj + 1] - loff[jj];
+    for (int q = threadIdx.x; q < c; q += kBinThreads) lds_cuts[loff[jj] + q] = src[q];
+  }
+  __syncthreads();
+  const long r0 = (long)blockIdx.x * rows_per_wg;
+  const int rows = (int)min((long)rows_per_wg, n - r0);
+  const int cells = rows * tw;  // rows_per_wg <= kMaxRowsPerWg: no overflow
+  for (int e = threadIdx.x; e < cells; e += kBinThreads) {
+    const long row = r0 + e / tw;
+    const int jj = e % tw;
+    const size_t at = (size_t)row * f + j0 + jj;
+    const double a = (double)X[at];
+    const double* c = lds_cuts + loff[jj];
+    int lo = 0, hi = loff[jj + 1] - loff[jj];
+    while (lo < hi) {  // the number of cuts <= a (std::upper_bound)
+      const int mid = (lo + hi) >> 1;
+      if (c[mid] <= a) lo = mid + 1; else hi = mid;
+    }
+    bins[at] = a != a ? (uint16_t)0xFFFF : (uint16_t)lo;
+  }
+}
+
+// ---- predict
+
+template <class T>
+__device__ inline double walk(const PackedNode* nodes, int cnt, const T* xi) {
+  int k = 0;
+  PackedNode nd = nodes[0];
+  for (int step = 1; step < cnt && nd.feature >= 0; ++step) {  // children have larger indices: < cnt steps
+    const double a = (double)xi[nd.feature];
+    const bool l = a != a ? nd.default_left != 0 : a < nd.v;
+    k = l ? nd.left : nd.right;
+    if ((unsigned)k >= (unsigned)cnt) return 0.0;  // refused on the host (validate_forest); never read past the tree
+    nd = nodes[k];
+  }
+  return nd.v;
+}
+
+template <class T>
+__global__ __launch_bounds__(kPredictThreads) void k_predict(const T* X, long n, int f, const PackedNode* nodes,
+                                                             const int* tree_off, int n_trees, double base,
+                                                             int nodes_per_chunk, double* out) {
+  extern __shared__ double lds_raw[];
+  PackedNode* lds = reinterpret_cast<PackedNode*>(lds_raw);
+  const long i = (long)blockIdx.x * kPredictThreads + threadIdx.x;
+  const T* xi = X + (size_t)(i < n ? i : 0) * f;
+  double s = base;
+  int t0 = 0;
+  while (t0 < n_trees) {  // every quantity that steers this loop is uniform over the workgroup
+    const int o0 = tree_off[t0];
+    int t1 = t0;
+    while (t1 < n_trees && tree_off[t1 + 1] - o0 <= nodes_per_chunk) ++t1;
+    if (t1 == t0) {  // one tree larger than a chunk: from global memory
+      if (i < n) s += walk(nodes + o0, tree_off[t0 + 1] - o0, xi);
+      t0 += 1;
+      continue;
+    }
+    const int total = tree_off[t1] - o0;
+    __syncthreads();  // the previous chunk has been walked
+    for (int q = threadIdx.x; q < total; q += kPredictThreads) lds[q] = nodes[o0 + q];
+    __syncthreads();
+    if (i < n)
+      for (int t = t0; t < t1; ++t) s += walk(lds + (tree_off[t] - o0), tree_off[t + 1] - tree_off[t], xi);
+    t0 = t1;
+  }
+  if (i < n) out[i] = s;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mifx_gbdt_prep_max_bins() { return kMaxBins; }
+int mifx_gbdt_prep_max_feat_tile() { return kMaxFeatTile; }
+int mifx_gbdt_prep_max_chunk_nodes() { return kMaxChunkNodes; }
+int mifx_gbdt_prep_node_bytes() { return (int)sizeof(PackedNode); }
+int mifx_gbdt_prep_cut_scratch_bytes() { return (int)((1 + kCutSlots) * sizeof(long long)); }
+
+// Cuts of one column. sorted: the column's n values ascending with the NaNs last (device); nan_count: their number
+// (device, int64). Writes up to max_bins - 1 ascending cuts and their count (device). scratch: cut_scratch_bytes.
+int mifx_gbdt_prep_cuts(const double* sorted, long n, const long long* nan_count, int max_bins, double* cuts,
+                        int* count, void* scratch, int blocks, hipStream_t stream) {
+  if (n < 1 || n >= (1L << 31) || max_bins < 2 || max_bins > kMaxBins || blocks < 1 || blocks > 65535) return -1;
+  u64* state = static_cast<u64*>(scratch);
+  long long* pos = static_cast<long long*>(scratch) + 1;
+  const hipError_t e = hipMemsetAsync(state, 0, sizeof(u64), stream);
+  if (e != hipSuccess) return (int)e;
+  k_cut_mark<<<(unsigned)blocks, kMarkThreads, 0, stream>>>(sorted, n, nan_count, state, pos);
+  k_cut_pick<<<1, kMaxBins, 0, stream>>>(sorted, n, nan_count, max_bins, state, pos, cuts, count);
+  return (int)hipGetLastError();
+}
+
+// Bins of a row-major [n, f] table (is_f64: double, else float) into row-major [n, f] uint16. cut_flat / cut_off /
+// ncut on the device; every ncut[j] <= 255 and every table inside cut_flat (checked by the caller on the host).
+int mifx_gbdt_prep_bin(const void* X, int is_f64, long n, int f, const double* cut_flat, const int* cut_off,
+                       const int* ncut, uint16_t* bins, int rows_per_wg, int feat_tile, hipStream_t stream) {
+  if (n < 1 || n >= (1L << 31) || f < 1 || rows_per_wg < 1 || rows_per_wg > kMaxRowsPerWg || feat_tile < 1 ||
+      feat_tile > kMaxFeatTile)
+    return -1;
+  const long tiles = ((long)f + feat_tile - 1) / feat_tile;
+  if (tiles > 65535) return -1;
+  const dim3 grid((unsigned)((n + rows_per_wg - 1) / rows_per_wg), (unsigned)tiles);
+  const size_t lds = (size_t)feat_tile * kMaxCuts * sizeof(double);
+  if (is_f64)
+    k_bin<double><<<grid, kBinThreads, lds, stream>>>(static_cast<const double*>(X), n, f, cut_flat, cut_off, ncut,
+                                                      bins, rows_per_wg, feat_tile);
+  else
+    k_bin<float><<<grid, kBinThreads, lds, stream>>>(static_cast<const float*>(X), n, f, cut_flat, cut_off, ncut,
+                                                     bins, rows_per_wg, feat_tile);
+  return (int)hipGetLastError();
+}
+
+// out[i] = base + the first n_trees trees' outputs for row i of a row-major [n, f] table. nodes: the packed forest;
+// tree_off [trees + 1]: node offsets (both validated on the host before upload).
+int mifx_gbdt_prep_predict(const void* X, int is_f64, long n, int f, const void* nodes, const int* tree_off,
+                           int n_trees, double base, int nodes_per_chunk, double* out, hipStream_t stream) {
+  if (n < 1 || n >= (1L << 31) || f < 1 || n_trees < 0 || nodes_per_chunk < 1 || nodes_per_chunk > kMaxChunkNodes)
+    return -1;
+  const unsigned grid = (unsigned)((n + kPredictThreads - 1) / kPredictThreads);
+  const size_t lds = (size_t)nodes_per_chunk * sizeof(PackedNode);
+  const PackedNode* nd = static_cast<const PackedNode*>(nodes);
+  if (is_f64)
+    k_predict<double><<<grid, kPredictThreads, lds, stream>>>(static_cast<const double*>(X), n, f, nd, tree_off,
+                                                              n_trees, base, nodes_per_chunk, out);
+  else
+    k_predict<float><<<grid, kPredictThreads, lds, stream>>>(static_cast<const float*>(X), n, f, nd, tree_off,
+                                                             n_trees, base, nodes_per_chunk, out);
+  return (int)hipGetLastError();
+}
+
+}  // extern "C"

@@ -12,8 +12,11 @@ Binary classification only (the reference has no multi-class GBDT).
 
 `device="gpu"` (or "cuda", "cuda:N") trains on the device learner of csrc/gbdt_gpu.hip: gradients, fixed-point int64
 histograms, split search, row partition and margin updates stay resident on the GPU for the whole fit; cuts and
-binning stay on the host (exact, once). `fixed_point=True` selects the fixed-point semantics of csrc/gbdt_split.h
-(the GPU's only mode, the CPU's option): histograms are integer sums, so a model is bit-reproducible for any thread
+binning run there too (csrc/gbdt_prep.hip, equal to the host functions bit for bit), so the table goes to the device
+once -- or is there already: `fit` takes numpy arrays, CPU tensors or torch tensors on that GPU. `predict` runs where
+its input is: numpy / CPU input on the host, a device tensor through the forest kernel on that tensor's device (any
+model, also one trained on the host), returning a device tensor. `fixed_point=True` selects the fixed-point
+semantics of csrc/gbdt_split.h (the GPU's only mode, the CPU's option): histograms are integer sums, so a model is bit-reproducible for any thread
 count AND any launch geometry, and `device="cpu", fixed_point=True` is the host twin that reproduces a GPU-trained
 model bit for bit. The default (`device=None`, double histograms on the host) is unchanged."""
 from __future__ import annotations
@@ -22,6 +25,7 @@ import ctypes
 import functools
 import logging
 import os
+import sys
 
 import numpy as np
 
@@ -67,6 +71,21 @@ def _parse_device(device):
     raise ValueError(f"device must be None, 'cpu', 'gpu', 'cuda' or 'cuda:N' (one GPU), got {device!r}")
 
 
+def _is_tensor(x) -> bool:
+    """A torch tensor, without importing torch (the default path never does)."""
+    torch = sys.modules.get("torch")
+    return torch is not None and isinstance(x, getattr(torch, "Tensor", ()))
+
+
+def _on_gpu(x) -> bool:
+    return _is_tensor(x) and x.is_cuda
+
+
+def _host(x) -> np.ndarray:
+    """numpy view or copy of an array-like or of a tensor on any device."""
+    return x.detach().cpu().numpy() if _is_tensor(x) else np.asarray(x)
+
+
 def _threads() -> int:
     return max(1, min(16, int(os.environ.get("OMP_NUM_THREADS", os.cpu_count() or 1))))
 
@@ -94,6 +113,20 @@ class _Base:
     def _fixed(self) -> bool:
         fp = getattr(self, "fixed_point", None)
         return self._gpu_index() is not None if fp is None else bool(fp)
+
+    def _check_data_device(self, *arrays) -> None:
+        """Data on a GPU must be on the model's GPU (and the model must have one)."""
+        gpu = self._gpu_index()
+        for a in arrays:
+            if _on_gpu(a) and gpu is None:
+                raise ValueError('the data is on a GPU: train it there with device="gpu" (or pass host arrays)')
+            if _on_gpu(a) and a.device.index != gpu:
+                raise ValueError(f"the data is on {a.device} but device={self.device!r} is GPU {gpu}")
+
+    def __getstate__(self):
+        state = self.__dict__.copy()
+        state.pop("_dev_forest", None)  # the device copy of the trees: rebuilt on the next device predict
+        return state
 
     # ---- loss (overridden by the classifier)
     def _base(self, y: np.ndarray) -> float:
@@ -157,13 +190,21 @@ class _Base:
         return fe[:cnt].copy(), thr, dl[:cnt].copy(), left[:cnt].copy(), right[:cnt].copy(), val[:cnt].copy()
 
     def fit(self, X, y, eval_set=None, early_stopping_rounds: int | None = None, verbose: bool = False):
-        X = np.ascontiguousarray(np.asarray(X, dtype=np.float64))
-        y = self._check_y(np.asarray(y).reshape(-1))
+        """Fit the boosted trees. With `device="gpu"`, X, y and the eval set may be numpy arrays, CPU tensors or torch
+        tensors on that GPU (float32 means its exact widening to float64); the table is uploaded once if it is not
+        there already, and its float64 form (8 n f bytes), the bins (2 n f bytes) and one column's sort scratch must
+        fit on the device. Without a device, data on a GPU is refused."""
+        self._dev_forest = None
+        gpu = self._gpu_index()
+        self._check_data_device(X, y, *(eval_set[-1] if eval_set else ()))
+        y = self._check_y(_host(y).reshape(-1))
+        X = X if _is_tensor(X) else np.asarray(X)
         if X.ndim != 2 or len(X) != len(y):
             raise ValueError("X must be [n, features] with one label per row")
         self._nfeat = X.shape[1]
-        if self._gpu_index() is not None:
+        if gpu is not None:
             return self._fit_gpu(X, y, eval_set, early_stopping_rounds, verbose)
+        X = np.ascontiguousarray(np.asarray(X, dtype=np.float64))
         bins = self._bin_matrix(X)
         nbins = (self._ncut + 1).astype(np.int32)
         self._base_margin = float(self.base_score) if self.base_score is not None else self._base(y)
@@ -205,24 +246,33 @@ class _Base:
         return self
 
     def _fit_gpu(self, X, y, eval_set, early_stopping_rounds, verbose):
-        """The boosting loop on the device learner (mifx/ops/gbdt_gpu.py): cuts and binning on the host, once; then
-        gradients, trees and margins stay on the GPU. With an eval set its margins come back once per round for the
-        metric (the host's own numpy metric, so the scores are the host twin's bit for bit); the trees come back once
-        at the end. Leaves the attributes of the host path."""
+        """The boosting loop on the device learner (mifx/ops/gbdt_gpu.py). The table is uploaded once (unless it is on
+        the device already); cuts and binning run there (mifx/ops/gbdt_prep.py: the host's cuts and bins bit for bit,
+        the cuts come back once for the trees' thresholds); then gradients, trees and margins stay on the GPU. With an
+        eval set its margins come back once per round for the metric (the host's own numpy metric, so the scores are
+        the host twin's bit for bit); the trees come back once at the end. Leaves the attributes of the host path."""
         import torch
 
         from ..ops import gbdt_gpu as G
+        from ..ops import gbdt_prep as P
 
         G.check_limits(len(y), int(self.max_bins), int(self.max_depth))
+        if int(self.max_bins) < 2:
+            raise ValueError("max_bins must be in [2, 65535]")
         dev = G.device_for(self._gpu_index())
-        bins = self._bin_matrix(X)
+        with torch.cuda.device(dev):
+            Xd = P.as_device_matrix(X, dev)
+            self._cuts, self._cut_flat, self._cut_off, self._ncut = P.device_cuts(Xd, int(self.max_bins))
+            tables = P.CutTables(self._cut_flat, self._cut_off, self._ncut, dev)
+            bins = P.device_bins(Xd, tables)
+            del Xd
         nbins = (self._ncut + 1).astype(np.int32)
         self._base_margin = float(self.base_score) if self.base_score is not None else self._base(y)
         if self._objective != "reg:squarederror" and self.base_score is not None:
             self._base_margin = float(np.log(self.base_score / (1 - self.base_score)))
         rounds = int(self.n_estimators)
         with torch.cuda.device(dev):
-            bst = G.Booster(bins, nbins, int(self.max_depth), dev)
+            bst = G.Booster.from_device_bins(bins, nbins, int(self.max_depth))
             yd = torch.from_numpy(y).to(dev)
             margin = torch.full((len(y),), self._base_margin, dtype=torch.float64, device=dev)
             g, h = (torch.empty(len(y), dtype=torch.float32, device=dev) for _ in range(2))
@@ -230,14 +280,11 @@ class _Base:
             ev = None
             if eval_set:
                 ex, ey = eval_set[-1]
-                ex = np.ascontiguousarray(np.asarray(ex, dtype=np.float64))
-                ey = self._check_y(np.asarray(ey).reshape(-1))
+                ex = ex if _is_tensor(ex) else np.asarray(ex)
+                ey = self._check_y(_host(ey).reshape(-1))
                 if ex.ndim != 2 or ex.shape[1] != self._nfeat or len(ex) != len(ey) or not len(ey):
                     raise ValueError(f"the eval set must be [m, {self._nfeat}] with one label per row")
-                ebins = np.empty((self._nfeat, len(ex)), np.uint16)
-                _lib().mifx_gbdt_bin(_p(ex, _D), len(ex), self._nfeat, _p(self._cut_flat, _D), _p(self._cut_off, _I),
-                                     _p(self._ncut, _I), _p(ebins, _U16), self._nthreads())
-                ev = (G.upload_bins(ebins, dev), ey,
+                ev = (P.device_bins(P.as_device_matrix(ex, dev), tables), ey,
                       torch.full((len(ey),), self._base_margin, dtype=torch.float64, device=dev))
             best, best_it, since, hist, done = None, 0, 0, [], 0
             for it in range(rounds):
@@ -292,15 +339,32 @@ class _Base:
                                  self._nthreads())
         return out
 
-    def _margin(self, X) -> np.ndarray:
+    def _margin(self, X):
+        """Margins where the data is: a tensor on a GPU goes through the forest kernel on that GPU and gives a tensor
+        there (the host's bits); anything else takes the host path, which needs no GPU."""
         n = len(self._trees) if self.best_iteration is None else self.best_iteration + 1
-        return self._predict_trees(X, self._trees[:n], self._base_margin)
+        if _on_gpu(X):
+            return self._margin_device(X, n)
+        return self._predict_trees(_host(X) if _is_tensor(X) else X, self._trees[:n], self._base_margin)
+
+    def _margin_device(self, X, n_trees: int):
+        from ..ops import gbdt_prep as P
+
+        if X.dim() != 2 or X.shape[1] != self._nfeat:
+            raise ValueError(f"expected [n, {self._nfeat}] features")
+        cache = getattr(self, "_dev_forest", None)
+        if cache is None:
+            cache = self._dev_forest = {}
+        if X.device.index not in cache:  # the packed trees, uploaded once per model and device (fit resets them)
+            cache[X.device.index] = P.DeviceForest(self._trees, self._nfeat, X.device)
+        return P.predict(cache[X.device.index], P.as_device_matrix(X, X.device), self._base_margin, n_trees)
 
 
 class XGBRegressor(_Base):
     """Squared-error regression (objective reg:squarederror)."""
 
-    def predict(self, X) -> np.ndarray:
+    def predict(self, X):
+        """Margins: a numpy array for host input, a tensor on the input's device for a tensor on a GPU."""
         return self._margin(X)
 
 
@@ -318,7 +382,8 @@ class XGBClassifier(_Base):
 
     def fit(self, X, y, eval_set=None, early_stopping_rounds: int | None = None, verbose: bool = False):
         self._fitting = True
-        y = np.asarray(y).reshape(-1)
+        self._check_data_device(X, y, *(eval_set[-1] if eval_set else ()))
+        y = _host(y).reshape(-1)
         self._check_y(y)  # classes from the training labels
         self._fitting = False
         return super().fit(X, y, eval_set, early_stopping_rounds, verbose)
@@ -338,9 +403,17 @@ class XGBClassifier(_Base):
         p = np.clip(1.0 / (1.0 + np.exp(-margin)), 1e-15, 1 - 1e-15)
         return float(-np.mean(y * np.log(p) + (1 - y) * np.log(1 - p)))
 
-    def predict_proba(self, X) -> np.ndarray:
-        p1 = 1.0 / (1.0 + np.exp(-self._margin(X)))
+    def predict_proba(self, X):
+        """[n, 2] probabilities: numpy for host input, a tensor on the input's device for a tensor on a GPU."""
+        m = self._margin(X)
+        if _is_tensor(m):
+            torch = sys.modules["torch"]
+            p1 = 1.0 / (1.0 + torch.exp(-m))
+            return torch.stack([1 - p1, p1], 1)
+        p1 = 1.0 / (1.0 + np.exp(-m))
         return np.stack([1 - p1, p1], 1)
 
     def predict(self, X) -> np.ndarray:
-        return self.classes_[(self.predict_proba(X)[:, 1] > 0.5).astype(int)]
+        """Labels, always a numpy array (classes_ may hold strings): for a device tensor, one read-back of the class
+        index."""
+        return self.classes_[_host(self.predict_proba(X)[:, 1] > 0.5).astype(int)]

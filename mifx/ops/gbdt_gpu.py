@@ -74,6 +74,19 @@ class Booster:
 
     def __init__(self, bins: np.ndarray, nbins: np.ndarray, max_depth: int, dev: torch.device):
         f, n = bins.shape
+        self._setup(n, f, nbins, max_depth, dev, lambda: upload_bins(bins, dev))
+
+    @classmethod
+    def from_device_bins(cls, bins: torch.Tensor, nbins: np.ndarray, max_depth: int) -> "Booster":
+        """A Booster on bins that are on the device already: row-major [n, f] int16 (mifx.ops.gbdt_prep.device_bins),
+        kept as they are."""
+        if not (bins.is_cuda and bins.dim() == 2 and bins.dtype == torch.int16 and bins.is_contiguous()):
+            raise ValueError("expected a contiguous [n, f] int16 tensor on the GPU")
+        self = cls.__new__(cls)
+        self._setup(bins.shape[0], bins.shape[1], nbins, max_depth, bins.device, lambda: bins)
+        return self
+
+    def _setup(self, n: int, f: int, nbins: np.ndarray, max_depth: int, dev: torch.device, device_bins) -> None:
         nbins = np.asarray(nbins, np.int32)
         check_limits(n, int(nbins.max()), max_depth)
         if nbins.min() < 1 or len(nbins) != f:
@@ -82,7 +95,7 @@ class Booster:
         self.cap = 2 ** (self.max_depth + 1)
         hoff = np.concatenate([[0], np.cumsum(nbins + 1)]).astype(np.int32)
         self.hsize = int(hoff[-1])
-        self.bins = upload_bins(bins, dev)
+        self.bins = device_bins()
         self.nbins = torch.from_numpy(nbins).to(dev)
         self.hoff = torch.from_numpy(hoff[:-1].copy()).to(dev)
         nbytes = _fns()["ws_bytes"](n, f, self.max_depth, self.hsize)
