@@ -17,6 +17,9 @@
 //
 // mifx_gbdt_grow_fixed is the same learner on fixed-point (int64) histograms with the split rule of gbdt_split.h:
 // the host twin of the device learner in gbdt_gpu.hip (larger tables, device="gpu"), which it reproduces bit for bit.
+//
+// Stochastic boosting (the *_ex entries): a tree is grown on a list of sampled rows as if the table held only them,
+// and a [max_depth, f] mask names the features each level may split on; the draws themselves are gbdt_sample.h's.
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -24,6 +27,7 @@
 #include <thread>
 #include <vector>
 
+#include "gbdt_sample.h"
 #include "gbdt_split.h"
 
 namespace {
@@ -64,9 +68,46 @@ void parallel_for(int n, int threads, F&& fn) {
   for (auto& th : pool) th.join();
 }
 
+// the *_ex entries' row list: ascending ids inside [0, n)
+bool rows_ok(const int* rows, long n_rows, long n) {
+  if (!rows) return true;
+  if (n_rows < 0 || n_rows > n) return false;
+  for (long k = 0; k < n_rows; ++k)
+    if (rows[k] < 0 || rows[k] >= n || (k > 0 && rows[k] <= rows[k - 1])) return false;
+  return true;
+}
+
 }  // namespace
 
 extern "C" {
+
+// ---- the draws of gbdt_sample.h, for the estimators and for the tests that compare them with the numpy twin and
+// with the device. keep [n]: 1 for a sampled row; returns their count.
+long mifx_gbdt_sample_rows(uint64_t seed, uint64_t round, double subsample, long n, uint8_t* keep) {
+  const uint64_t thr = mifx_gs_row_thr(subsample);
+  if (thr >= MIFX_GS_KEEP_ALL) {
+    std::memset(keep, 1, (size_t)n);
+    return n;
+  }
+  const uint64_t key = mifx_gs_key(seed, round, MIFX_GS_SITE_ROWS);
+  long cnt = 0;
+  for (long i = 0; i < n; ++i) cnt += keep[i] = mifx_gs_keep_row(key, (uint64_t)i, thr);
+  return cnt;
+}
+
+// one feature draw at `site` among cand (null: all f); out [f]; returns k
+int mifx_gbdt_sample_features(uint64_t seed, uint64_t round, uint64_t site, double rate, const uint8_t* cand, int f,
+                              uint8_t* out) {
+  return mifx_gs_choose(mifx_gs_key(seed, round, site), rate, cand, f, out);
+}
+
+// the [max_depth, f] level mask of a round (and the tree's set [f])
+int mifx_gbdt_level_mask(uint64_t seed, uint64_t round, int f, int max_depth, double colsample_bytree,
+                         double colsample_bylevel, uint8_t* tree_set, uint8_t* mask) {
+  if (f < 1 || max_depth < 0) return -1;
+  mifx_gs_level_mask(seed, round, f, max_depth, colsample_bytree, colsample_bylevel, tree_set, mask);
+  return 0;
+}
 
 // Cut points of one feature column (n values, stride `stride` doubles apart): writes up to max_bins - 1 ascending
 // cuts into `cuts` and returns their count.
@@ -130,16 +171,25 @@ int mifx_gbdt_bin(const double* X, long n, int f, const double* cuts, const int*
 // written as parallel arrays of at most max_nodes entries: feature (-1 = leaf), split bin, default_left, left,
 // right, value (leaf output, eta applied). leaf_of_row[i] receives the leaf id of row i (for the caller's
 // prediction update). Returns the node count, or -1 if max_nodes is too small.
-int mifx_gbdt_grow(const uint16_t* bins, long n, int f, const int* nbins, const float* g, const float* h,
-                   int max_depth, double min_child_weight, double lambda, double gamma, double eta, int threads,
-                   int max_nodes, int* feature, int* split_bin, uint8_t* default_left, int* left, int* right,
-                   double* value, int* leaf_of_row) {
+//
+// sample (null = all rows): n_rows ascending row ids; the tree is grown on exactly these rows as if the table held
+// only them, leaf_of_row is -1 for the others, and an empty list gives the one-node tree of value +0.0.
+// level_mask (null = all features): [max_depth, f], a feature with level_mask[d * f + j] == 0 yields no candidate
+// at depth d, as nbins[j] == 1 does. -2: a row list that is not ascending inside [0, n).
+int mifx_gbdt_grow_ex(const uint16_t* bins, long n, int f, const int* nbins, const float* g, const float* h,
+                      int max_depth, double min_child_weight, double lambda, double gamma, double eta, int threads,
+                      int max_nodes, int* feature, int* split_bin, uint8_t* default_left, int* left, int* right,
+                      double* value, int* leaf_of_row, const int* sample, long n_rows, const uint8_t* level_mask) {
+  if (!rows_ok(sample, n_rows, n)) return -2;
   std::vector<int> off(f + 1, 0);
   for (int j = 0; j < f; ++j) off[j + 1] = off[j] + nbins[j] + 1;
   const int hsize = off[f];
-  std::vector<int> rows(n);
-  for (long i = 0; i < n; ++i) rows[i] = (int)i;
-  const int th = n * (long)f > 200000 ? threads : 1;
+  const long ns = sample ? n_rows : n;
+  std::vector<int> rows(ns);
+  for (long i = 0; i < ns; ++i) rows[i] = sample ? sample[i] : (int)i;
+  if (sample)
+    for (long i = 0; i < n; ++i) leaf_of_row[i] = -1;
+  const int th = ns * (long)f > 200000 ? threads : 1;
 
   auto build = [&](Node& nd) {
     nd.hist.assign(hsize, Hist{0.0, 0.0});
@@ -162,8 +212,8 @@ int mifx_gbdt_grow(const uint16_t* bins, long n, int f, const int* nbins, const 
     const double parent = score(nd.g, nd.h);
     parallel_for(f, th, [&](int j) {
       const Hist* hj = nd.hist.data() + off[j];
-      const int nb = nbins[j];
-      const double gm = hj[nb].g, hm = hj[nb].h;
+      const int nb = level_mask && !level_mask[(size_t)nd.depth * f + j] ? 1 : nbins[j];
+      const double gm = hj[nbins[j]].g, hm = hj[nbins[j]].h;
       Split bs;
       double gl = 0, hl = 0;
       for (int b = 0; b + 1 < nb; ++b) {  // cut after bin b
@@ -202,11 +252,12 @@ int mifx_gbdt_grow(const uint16_t* bins, long n, int f, const int* nbins, const 
     value[count] = 0.0;
     return count++;
   };
-  Node root{0, (int)n, 0, new_node(), 0.0, 0.0, {}};
+  Node root{0, (int)ns, 0, new_node(), 0.0, 0.0, {}};
   if (root.id < 0) return -1;
-  for (long i = 0; i < n; ++i) {
-    root.g += g[i];
-    root.h += h[i];
+  if (ns == 0) return count;  // nothing sampled: the root alone, value +0.0
+  for (long i = 0; i < ns; ++i) {
+    root.g += g[rows[i]];
+    root.h += h[rows[i]];
   }
   build(root);
   std::vector<Node> level;
@@ -260,6 +311,15 @@ int mifx_gbdt_grow(const uint16_t* bins, long n, int f, const int* nbins, const 
   return count;
 }
 
+int mifx_gbdt_grow(const uint16_t* bins, long n, int f, const int* nbins, const float* g, const float* h,
+                   int max_depth, double min_child_weight, double lambda, double gamma, double eta, int threads,
+                   int max_nodes, int* feature, int* split_bin, uint8_t* default_left, int* left, int* right,
+                   double* value, int* leaf_of_row) {
+  return mifx_gbdt_grow_ex(bins, n, f, nbins, g, h, max_depth, min_child_weight, lambda, gamma, eta, threads,
+                           max_nodes, feature, split_bin, default_left, left, right, value, leaf_of_row, nullptr, 0,
+                           nullptr);
+}
+
 // ---- fixed-point twin of mifx_gbdt_grow (gbdt_split.h): int64 histograms, so the tree cannot depend on the order
 // of any sum -- the host reference that the device learner (csrc/gbdt_gpu.hip) reproduces bit for bit.
 
@@ -267,10 +327,14 @@ int mifx_gbdt_quant_exp(double amax, long n) { return mifx_gb_quant_exp(amax, n)
 
 // mifx_gbdt_grow's signature and outputs; the semantics are the fixed-point ones of gbdt_split.h. On gradients that
 // quantise exactly and sum exactly in double (small dyadic rationals) it grows exactly mifx_gbdt_grow's tree.
-int mifx_gbdt_grow_fixed(const uint16_t* bins, long n, int f, const int* nbins, const float* g, const float* h,
-                         int max_depth, double min_child_weight, double lambda, double gamma, double eta, int threads,
-                         int max_nodes, int* feature, int* split_bin, uint8_t* default_left, int* left, int* right,
-                         double* value, int* leaf_of_row) {
+// sample / level_mask: as in mifx_gbdt_grow_ex; the exponents come from the sampled rows alone (their largest
+// magnitudes and their count).
+int mifx_gbdt_grow_fixed_ex(const uint16_t* bins, long n, int f, const int* nbins, const float* g, const float* h,
+                            int max_depth, double min_child_weight, double lambda, double gamma, double eta,
+                            int threads, int max_nodes, int* feature, int* split_bin, uint8_t* default_left, int* left,
+                            int* right, double* value, int* leaf_of_row, const int* sample, long n_rows,
+                            const uint8_t* level_mask) {
+  if (!rows_ok(sample, n_rows, n)) return -2;
   struct QNode {
     int begin, end, depth, id;
     long long g, h;
@@ -281,25 +345,29 @@ int mifx_gbdt_grow_fixed(const uint16_t* bins, long n, int f, const int* nbins, 
   std::vector<int> off(f + 1, 0);
   for (int j = 0; j < f; ++j) off[j + 1] = off[j] + nbins[j] + 1;
   const int hsize = off[f];
-  std::vector<int> rows(n);
-  for (long i = 0; i < n; ++i) rows[i] = (int)i;
-  const int th = n * (long)f > 200000 ? threads : 1;
+  const long ns = sample ? n_rows : n;
+  std::vector<int> rows(ns);
+  for (long i = 0; i < ns; ++i) rows[i] = sample ? sample[i] : (int)i;
+  if (sample)
+    for (long i = 0; i < n; ++i) leaf_of_row[i] = -1;
+  const int th = ns * (long)f > 200000 ? threads : 1;
 
   // quantisation: the largest magnitudes (max is order-independent), one exponent each, then the rows
   auto amax = [&](const float* v) {
     double a = 0.0;
-    for (long i = 0; i < n; ++i) {
-      const double x = std::fabs((double)v[i]);
+    for (long i = 0; i < ns; ++i) {
+      const double x = std::fabs((double)v[rows[i]]);
       if (!(x <= a)) a = x;  // a NaN sticks: the exponent is then 0
       if (std::isnan(x)) return x;
     }
     return a;
   };
-  const int eg = mifx_gb_quant_exp(amax(g), n), eh = mifx_gb_quant_exp(amax(h), n);
-  std::vector<long long> qg(n), qh(n);
-  for (long i = 0; i < n; ++i) {
-    qg[i] = mifx_gb_quantise(g[i], eg);
-    qh[i] = mifx_gb_quantise(h[i], eh);
+  const int eg = mifx_gb_quant_exp(amax(g), ns), eh = mifx_gb_quant_exp(amax(h), ns);
+  std::vector<long long> qg(n), qh(n);  // indexed by row id; rows outside the sample are never read
+  for (long i = 0; i < ns; ++i) {
+    const int r = rows[i];
+    qg[r] = mifx_gb_quantise(g[r], eg);
+    qh[r] = mifx_gb_quantise(h[r], eh);
   }
 
   auto build = [&](QNode& nd) {
@@ -324,8 +392,9 @@ int mifx_gbdt_grow_fixed(const uint16_t* bins, long n, int f, const int* nbins, 
     const double parent = mifx_gb_parent_score(nd.g, nd.h, eg, eh, prm);
     parallel_for(f, th, [&](int j) {
       MifxGbSplit bs = mifx_gb_no_split();
-      mifx_gb_scan(nd.hg.data() + off[j], nd.hh.data() + off[j], nd.hc.data() + off[j], nbins[j], 0, nbins[j], 0, 0,
-                   0, nd.g, nd.h, eg, eh, j, prm, parent, &bs);
+      if (!level_mask || level_mask[(size_t)nd.depth * f + j])
+        mifx_gb_scan(nd.hg.data() + off[j], nd.hh.data() + off[j], nd.hc.data() + off[j], nbins[j], 0, nbins[j], 0,
+                     0, 0, nd.g, nd.h, eg, eh, j, prm, parent, &bs);
       per[j] = bs;
     });
     MifxGbSplit best = mifx_gb_no_split();
@@ -344,11 +413,12 @@ int mifx_gbdt_grow_fixed(const uint16_t* bins, long n, int f, const int* nbins, 
     value[count] = 0.0;
     return count++;
   };
-  QNode root{0, (int)n, 0, new_node(), 0, 0, {}, {}, {}};
+  QNode root{0, (int)ns, 0, new_node(), 0, 0, {}, {}, {}};
   if (root.id < 0) return -1;
-  for (long i = 0; i < n; ++i) {
-    root.g += qg[i];
-    root.h += qh[i];
+  if (ns == 0) return count;  // nothing sampled: the root alone, value +0.0
+  for (long i = 0; i < ns; ++i) {
+    root.g += qg[rows[i]];
+    root.h += qh[rows[i]];
   }
   if (max_depth > 0) build(root);
   std::vector<QNode> level;
@@ -399,6 +469,15 @@ int mifx_gbdt_grow_fixed(const uint16_t* bins, long n, int f, const int* nbins, 
     level = std::move(next);
   }
   return count;
+}
+
+int mifx_gbdt_grow_fixed(const uint16_t* bins, long n, int f, const int* nbins, const float* g, const float* h,
+                         int max_depth, double min_child_weight, double lambda, double gamma, double eta, int threads,
+                         int max_nodes, int* feature, int* split_bin, uint8_t* default_left, int* left, int* right,
+                         double* value, int* leaf_of_row) {
+  return mifx_gbdt_grow_fixed_ex(bins, n, f, nbins, g, h, max_depth, min_child_weight, lambda, gamma, eta, threads,
+                                 max_nodes, feature, split_bin, default_left, left, right, value, leaf_of_row, nullptr,
+                                 0, nullptr);
 }
 
 // Sum of the first n_trees trees' outputs for each row of a row-major [n, f] matrix of raw values. Trees are

@@ -23,11 +23,22 @@
 //   k_partition per row position: a leaf's rows get leaf_of_row and margin += value; a split's rows move to their
 //               child's range through wave-aggregated atomic cursors. The order of rows INSIDE a child is therefore
 //               not deterministic; nothing downstream depends on it (integer sums, per-row writes).
+//
+// Stochastic boosting (mifx_gbdt_gpu_grow_ex; the draws are gbdt_sample.h's, the host twin is mifx_gbdt_grow_fixed_ex):
+//   rows      with subsample < 1 the quantise stage is a compaction: k_amax_s takes the maxima over the sampled rows
+//             and counts them, k_quant_s derives the exponents from that device-side count, writes the sampled rows
+//             as perm[0][0, n_s) (each workgroup counts its share, draws ONE cursor range, then places) and
+//             leaf_of_row = -1 for the others; the root is [0, n_s). The level kernels are still launched for n rows
+//             and find no node beyond n_s. Rows outside the sample get their margin from a walk of the finished tree
+//             over the training bins (k_apply_rest).
+//   features  a [max_depth, f] uint8 mask computed by the host: k_split gives no candidate for a masked (level,
+//             feature), k_hist skips a feature tile that is masked entirely.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <algorithm>
 
+#include "gbdt_sample.h"
 #include "gbdt_split.h"
 
 namespace {
@@ -69,6 +80,7 @@ struct Ws {
   MifxGbSplit* cand;
   long long *hg, *hh;
   int* hc;
+  int* nsamp;  // [2] sampled rows: their count (k_amax_s), the compaction cursor (k_quant_s)
   size_t bytes;
 };
 
@@ -114,6 +126,7 @@ Ws carve(void* base, long n, int f, int max_depth, int hsize) {
   w.hg = c.take<long long>(maxh * hsize);
   w.hh = c.take<long long>(maxh * hsize);
   w.hc = c.take<int>(maxh * hsize);
+  w.nsamp = c.take<int>(2);
   w.bytes = c.used;
   return w;
 }
@@ -121,23 +134,33 @@ Ws carve(void* base, long n, int f, int max_depth, int hsize) {
 __device__ __forceinline__ void add64(long long* p, long long v) { atomicAdd(reinterpret_cast<u64*>(p), (u64)v); }
 
 // ---- gradients: the formulas of XGBRegressor / XGBClassifier._grad_hess
-__global__ void k_grad(int objective, const double* margin, const double* y, long n, float* g, float* h) {
+// wt (nullable): instance weights; the float32 pair times the float32 weight, one IEEE multiply each
+__global__ void k_grad(int objective, const double* margin, const double* y, const float* wt, long n, float* g,
+                       float* h) {
   const long i = blockIdx.x * (long)kThreads + threadIdx.x;
   if (i >= n) return;
+  float gi, hi;
   if (objective == 0) {
-    g[i] = (float)(margin[i] - y[i]);
-    h[i] = 1.0f;
+    gi = (float)(margin[i] - y[i]);
+    hi = 1.0f;
   } else {
     const double p = 1.0 / (1.0 + exp(-margin[i]));
-    g[i] = (float)(p - y[i]);
-    h[i] = (float)fmax(p * (1.0 - p), 1e-16);
+    gi = (float)(p - y[i]);
+    hi = (float)fmax(p * (1.0 - p), 1e-16);
   }
+  if (wt) {
+    gi = gi * wt[i];
+    hi = hi * wt[i];
+  }
+  g[i] = gi;
+  h[i] = hi;
 }
 
 __global__ void k_init(Ws w) {
   if (threadIdx.x < 2) w.amax[threadIdx.x] = 0u;
   if (threadIdx.x == 2) w.lv[0].qg[0] = 0;
   if (threadIdx.x == 3) w.lv[0].qh[0] = 0;
+  if (threadIdx.x == 4 || threadIdx.x == 5) w.nsamp[threadIdx.x - 4] = 0;
 }
 
 // max |g|, max |h| as bit patterns: non-negative floats order like their bits, and a NaN sorts above infinity
@@ -188,10 +211,121 @@ __global__ void k_quant(const float* g, const float* h, long n, Ws w) {
   }
 }
 
+// ---- subsample < 1: the quantise stage over the sampled rows only. Row i is sampled iff mifx_gs_keep_row(key, i,
+// thr); both kernels hash (a few integer multiplies per row) instead of storing a mask. One atomic per workgroup and
+// word: the per-wave form of k_amax / k_quant runs at the same-address atomic rate (profiles/gbdt_gpu.md).
+constexpr int kWaves = kThreads / 64;
+
+__global__ __launch_bounds__(kThreads) void k_amax_s(const float* g, const float* h, long n, u64 key, u64 thr,
+                                                     unsigned* amax, int* nsamp) {
+  __shared__ unsigned s_g[kWaves], s_h[kWaves];
+  __shared__ int s_c[kWaves];
+  unsigned mg = 0, mh = 0;
+  int c = 0;
+  for (long i = blockIdx.x * (long)kThreads + threadIdx.x; i < n; i += (long)gridDim.x * kThreads)
+    if (mifx_gs_keep_row(key, (u64)i, thr)) {
+      mg = max(mg, __float_as_uint(fabsf(g[i])));
+      mh = max(mh, __float_as_uint(fabsf(h[i])));
+      ++c;
+    }
+  for (int o = 32; o; o >>= 1) {
+    mg = max(mg, (unsigned)__shfl_xor((int)mg, o));
+    mh = max(mh, (unsigned)__shfl_xor((int)mh, o));
+    c += __shfl_xor(c, o);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    s_g[threadIdx.x >> 6] = mg;
+    s_h[threadIdx.x >> 6] = mh;
+    s_c[threadIdx.x >> 6] = c;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  for (int v = 1; v < kWaves; ++v) {
+    mg = max(mg, s_g[v]);
+    mh = max(mh, s_h[v]);
+    c += s_c[v];
+  }
+  if (c == 0) return;
+  atomicMax(amax, mg);
+  atomicMax(amax + 1, mh);
+  atomicAdd(nsamp, c);
+}
+
+__global__ __launch_bounds__(kThreads) void k_quant_s(const float* g, const float* h, long n, u64 key, u64 thr, Ws w,
+                                                      int* leaf_of_row) {
+  __shared__ int s_c[kWaves], s_base;
+  __shared__ long long s_g[kWaves], s_h[kWaves];
+  const int ns = w.nsamp[0];
+  const int eg = mifx_gb_quant_exp((double)__uint_as_float(w.amax[0]), ns);
+  const int eh = mifx_gb_quant_exp((double)__uint_as_float(w.amax[1]), ns);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  // the workgroup's sampled rows over its grid-stride share, then ONE returning atomic for its range of perm[0]
+  int c = 0;
+  for (long i = blockIdx.x * (long)kThreads + threadIdx.x; i < n; i += (long)gridDim.x * kThreads)
+    c += mifx_gs_keep_row(key, (u64)i, thr);
+  for (int o = 32; o; o >>= 1) c += __shfl_xor(c, o);
+  if (lane == 0) s_c[wave] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int tot = 0;
+    for (int v = 0; v < kWaves; ++v) tot += s_c[v];
+    s_base = tot ? atomicAdd(&w.nsamp[1], tot) : 0;
+  }
+  __syncthreads();
+  int cur = s_base;  // uniform over the wave: where this wave's next sampled row goes
+  for (int v = 0; v < wave; ++v) cur += s_c[v];
+  long long sg = 0, sh = 0;
+  // the same rows as above, a wave at a time (the trip count is uniform over the wave: every lane reaches the ballot)
+  for (long i0 = blockIdx.x * (long)kThreads + wave * 64; i0 < n; i0 += (long)gridDim.x * kThreads) {
+    const long i = i0 + lane;
+    const bool kp = i < n && mifx_gs_keep_row(key, (u64)i, thr);
+    const u64 m = __ballot(kp);
+    if (kp) {
+      const long long a = mifx_gb_quantise(g[i], eg), b = mifx_gb_quantise(h[i], eh);
+      w.qg[i] = a;
+      w.qh[i] = b;
+      const int pos = cur + __popcll(m & (((u64)1 << lane) - 1));
+      if ((unsigned)pos < (unsigned long)n) w.perm[0][pos] = (int)i;
+      sg += a;
+      sh += b;
+    } else if (i < n) {
+      leaf_of_row[i] = -1;
+    }
+    cur += __popcll(m);
+  }
+  for (int o = 32; o; o >>= 1) {
+    sg += __shfl_xor(sg, o);
+    sh += __shfl_xor(sh, o);
+  }
+  if (lane == 0) {
+    s_g[wave] = sg;
+    s_h[wave] = sh;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int v = 1; v < kWaves; ++v) {
+      sg += s_g[v];
+      sh += s_h[v];
+    }
+    if (sg) add64(w.lv[0].qg, sg);
+    if (sh) add64(w.lv[0].qh, sh);
+    if (blockIdx.x == 0) {
+      w.exps[0] = eg;
+      w.exps[1] = eh;
+      w.lv[0].id[0] = 0;
+      w.lv[0].begin[0] = 0;
+      w.lv[0].end[0] = ns;
+      w.lcount[0] = 1;
+      *w.ncount = 1;
+    }
+  }
+}
+
 __global__ __launch_bounds__(kThreads) void k_hist(Level lv, const int* lcount, int d, const uint16_t* bins,
                                                    const int* perm, const long long* qg, const long long* qh, long n,
                                                    int f, const int* nbins, const int* hoff, int hsize, long long* hg,
-                                                   long long* hh, int* hc, int rows_per_wg, int ft) {
+                                                   long long* hh, int* hc, int rows_per_wg, int ft,
+                                                   const uint8_t* lmask) {
   extern __shared__ long long smem[];
   long long* sg = smem;
   long long* sh = smem + ft * kSlots;
@@ -199,6 +333,11 @@ __global__ __launch_bounds__(kThreads) void k_hist(Level lv, const int* lcount, 
   const int cnt = min(lcount[d], 1 << d);
   const long p0 = (long)blockIdx.x * rows_per_wg, p1 = min(n, p0 + rows_per_wg);
   const int j0 = blockIdx.y * ft, nf = min(ft, f - j0), tid = threadIdx.x;
+  if (lmask) {  // (nullable) the level's feature mask: a tile without a live feature is never searched
+    bool live = false;
+    for (int jj = 0; jj < nf; ++jj) live |= lmask[j0 + jj] != 0;
+    if (!live) return;  // uniform over the workgroup
+  }
   int lo = 0, hi = cnt;  // first node that ends after p0 (ranges ascend)
   while (lo < hi) {
     const int mid = (lo + hi) >> 1;
@@ -246,14 +385,14 @@ __global__ __launch_bounds__(kThreads) void k_hist(Level lv, const int* lcount, 
 __global__ __launch_bounds__(kThreads) void k_split(Level lv, const int* lcount, int d, int f, const int* nbins,
                                                     const int* hoff, int hsize, const long long* hg,
                                                     const long long* hh, const int* hc, const int* exps,
-                                                    MifxGbParams prm, MifxGbSplit* cand) {
+                                                    MifxGbParams prm, MifxGbSplit* cand, const uint8_t* lmask) {
   const long wave = (blockIdx.x * (long)kThreads + threadIdx.x) >> 6;
   const int lane = threadIdx.x & 63;
   const int cnt = min(lcount[d], 1 << d);
   const int k = (int)(wave / f), j = (int)(wave % f);
   if (k >= cnt) return;  // uniform over the wave
   MifxGbSplit bs = mifx_gb_no_split();
-  if (lv.end[k] - lv.begin[k] >= 2) {
+  if (lv.end[k] - lv.begin[k] >= 2 && (!lmask || lmask[j])) {  // a masked feature yields no candidate at this level
     const int nb = min(nbins[j], kMaxBins);
     const size_t o = (size_t)k * hsize + hoff[j];
     const long long *g0 = hg + o, *h0 = hh + o;
@@ -314,7 +453,10 @@ __global__ __launch_bounds__(kThreads) void k_decide(Level lv, Level nx, int* lc
     dec.cl[k] = best.cl;
     dec.gl[k] = best.gl;
     dec.hl[k] = best.hl;
-    dec.val[k] = leaf ? mifx_gb_leaf_value(lv.qg[k], lv.qh[k], exps[0], exps[1], prm) : 0.0;
+    // the root of an empty sample: +0.0, no division (no other node is ever empty: d is uniform, so levels below
+    // the root do not even load the range)
+    const bool empty = d == 0 && lv.end[k] <= lv.begin[k];
+    dec.val[k] = leaf && !empty ? mifx_gb_leaf_value(lv.qg[k], lv.qh[k], exps[0], exps[1], prm) : 0.0;
     cur[2 * k] = 0;
     cur[2 * k + 1] = 0;
   }
@@ -418,10 +560,12 @@ __global__ __launch_bounds__(kThreads) void k_partition(Level lv, const int* lco
 }
 
 // margin[i] += the new tree's output for row i of a binned matrix (the eval set): bin <= split_bin  <=>  x < cut
+// rest (nullable): leaf_of_row of a sampled tree; only its -1 rows, the rows outside the sample, are walked
 __global__ void k_apply(const uint16_t* bins, long m, int f, const int* nbins, TreeOut t, int cap, int max_depth,
-                        double* margin) {
+                        double* margin, const int* rest) {
   const long i = blockIdx.x * (long)kThreads + threadIdx.x;
   if (i >= m) return;
+  if (rest && rest[i] >= 0) return;
   int k = 0;
   for (int step = 0; step <= max_depth; ++step) {
     const int feat = t.feature[k];
@@ -457,52 +601,94 @@ long long mifx_gbdt_gpu_ws_bytes(long n, int f, int max_depth, int hsize) {
 int mifx_gbdt_gpu_grad(int objective, const double* margin, const double* y, long n, float* g, float* h,
                        hipStream_t stream) {
   if (n < 1 || objective < 0 || objective > 1) return -1;
-  k_grad<<<(unsigned)((n + kThreads - 1) / kThreads), kThreads, 0, stream>>>(objective, margin, y, n, g, h);
+  k_grad<<<(unsigned)((n + kThreads - 1) / kThreads), kThreads, 0, stream>>>(objective, margin, y, nullptr, n, g, h);
+  return (int)hipGetLastError();
+}
+
+// the same with instance weights (float32 [n], nullable): g, h = the pair above times the weight
+int mifx_gbdt_gpu_grad_w(int objective, const double* margin, const double* y, const float* weight, long n, float* g,
+                         float* h, hipStream_t stream) {
+  if (n < 1 || objective < 0 || objective > 1) return -1;
+  k_grad<<<(unsigned)((n + kThreads - 1) / kThreads), kThreads, 0, stream>>>(objective, margin, y, weight, n, g, h);
   return (int)hipGetLastError();
 }
 
 // Grow one tree. bins: row-major [n, f]; nbins [f] and hoff [f] (exclusive prefix of nbins + 1) on the device, the
 // tree arrays (cap = 2^(max_depth + 1) entries each) and node_count too. leaf_of_row [n]; margin (nullable) [n]
 // receives margin[row] += value[leaf of row]. rows_per_wg / feat_tile: launch geometry of the histogram kernel.
-int mifx_gbdt_gpu_grow(const uint16_t* bins, long n, int f, const int* nbins, const int* hoff, int hsize,
-                       const float* g, const float* h, int max_depth, double min_child_weight, double lambda,
-                       double gamma, double eta, void* ws, long long ws_bytes, int* feature, int* split_bin,
-                       uint8_t* default_left, int* left, int* right, double* value, int* node_count, int* leaf_of_row,
-                       double* margin, int rows_per_wg, int feat_tile, hipStream_t stream) {
+//
+// Sampling: thr < 2^32 grows the tree on the rows that mifx_gs_keep_row(key(seed, round, rows), i, thr) keeps, as if
+// the table held only them (leaf_of_row = -1 for the others; thr >= 2^32 keeps every row and hashes nothing).
+// level_mask (device, nullable): [max_depth, f] uint8, the features each level may split on. With sampling every
+// row's margin still receives the tree's output; margin_route 0: the partition updates the sampled rows and a walk of
+// the tree covers the others, 1: one walk over all rows. Both add the same double to the same margin.
+int mifx_gbdt_gpu_grow_ex(const uint16_t* bins, long n, int f, const int* nbins, const int* hoff, int hsize,
+                          const float* g, const float* h, int max_depth, double min_child_weight, double lambda,
+                          double gamma, double eta, void* ws, long long ws_bytes, int* feature, int* split_bin,
+                          uint8_t* default_left, int* left, int* right, double* value, int* node_count,
+                          int* leaf_of_row, double* margin, int rows_per_wg, int feat_tile, unsigned long long seed,
+                          unsigned long long round, unsigned long long thr, const uint8_t* level_mask,
+                          int margin_route, hipStream_t stream) {
   const long long need = mifx_gbdt_gpu_ws_bytes(n, f, max_depth, hsize);
   if (need < 0 || ws_bytes < need || rows_per_wg < 1 || feat_tile < 1 || feat_tile > kMaxFeatTile) return -1;
+  if (margin_route < 0 || margin_route > 1) return -1;
+  const bool sampled = thr < MIFX_GS_KEEP_ALL;
+  double* part_margin = sampled && margin_route == 1 ? nullptr : margin;
   Ws w = carve(ws, n, f, max_depth, hsize);
   const MifxGbParams prm{lambda, gamma, min_child_weight, eta};
   const TreeOut t{feature, split_bin, default_left, left, right, value};
   const int cap = 1 << (max_depth + 1);
   k_init<<<1, 64, 0, stream>>>(w);
-  k_amax<<<grid_for(n), kThreads, 0, stream>>>(g, h, n, w.amax);
-  k_quant<<<grid_for(n), kThreads, 0, stream>>>(g, h, n, w);
+  if (sampled) {
+    const u64 key = mifx_gs_key(seed, round, MIFX_GS_SITE_ROWS);
+    k_amax_s<<<grid_for(n), kThreads, 0, stream>>>(g, h, n, key, thr, w.amax, w.nsamp);
+    k_quant_s<<<grid_for(n), kThreads, 0, stream>>>(g, h, n, key, thr, w, leaf_of_row);
+  } else {
+    k_amax<<<grid_for(n), kThreads, 0, stream>>>(g, h, n, w.amax);
+    k_quant<<<grid_for(n), kThreads, 0, stream>>>(g, h, n, w);
+  }
   const unsigned row_blocks = (unsigned)((n + kThreads - 1) / kThreads);
   const dim3 hist_grid((unsigned)((n + rows_per_wg - 1) / rows_per_wg), (unsigned)((f + feat_tile - 1) / feat_tile));
   const size_t lds = (size_t)feat_tile * kSlots * (2 * sizeof(long long) + sizeof(int));
   for (int d = 0; d <= max_depth; ++d) {
     Level &lv = w.lv[d & 1], &nx = w.lv[(d + 1) & 1];
     if (d < max_depth) {
+      const uint8_t* lmask = level_mask ? level_mask + (size_t)d * f : nullptr;
       const size_t cells = ((size_t)1 << d) * hsize;
       hipError_t e = hipMemsetAsync(w.hg, 0, cells * sizeof(long long), stream);
       if (e == hipSuccess) e = hipMemsetAsync(w.hh, 0, cells * sizeof(long long), stream);
       if (e == hipSuccess) e = hipMemsetAsync(w.hc, 0, cells * sizeof(int), stream);
       if (e != hipSuccess) return (int)e;
       k_hist<<<hist_grid, kThreads, lds, stream>>>(lv, w.lcount, d, bins, w.perm[d & 1], w.qg, w.qh, n, f, nbins, hoff,
-                                                   hsize, w.hg, w.hh, w.hc, rows_per_wg, feat_tile);
+                                                   hsize, w.hg, w.hh, w.hc, rows_per_wg, feat_tile, lmask);
       const long waves = ((long)1 << d) * f;
       k_split<<<(unsigned)((waves + 3) / 4), kThreads, 0, stream>>>(lv, w.lcount, d, f, nbins, hoff, hsize, w.hg, w.hh,
-                                                                    w.hc, w.exps, prm, w.cand);
+                                                                    w.hc, w.exps, prm, w.cand, lmask);
     }
     k_decide<<<1, kThreads, 0, stream>>>(lv, nx, w.lcount, d, d == max_depth, f, w.cand, w.exps, prm, w.dec, w.cur, t,
                                          cap, w.ncount);
     k_partition<<<row_blocks, kThreads, 0, stream>>>(lv, w.lcount, d, w.dec, w.cur, bins, nbins, n, f, w.perm[d & 1],
-                                                     w.perm[(d + 1) & 1], leaf_of_row, margin);
+                                                     w.perm[(d + 1) & 1], leaf_of_row, part_margin);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+  }
+  if (sampled && margin) {  // the tree is complete: the rows that no leaf has updated
+    k_apply<<<row_blocks, kThreads, 0, stream>>>(bins, n, f, nbins, t, cap, max_depth, margin,
+                                                 margin_route == 1 ? nullptr : leaf_of_row);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
   }
   return (int)hipMemcpyAsync(node_count, w.ncount, sizeof(int), hipMemcpyDeviceToDevice, stream);
+}
+
+int mifx_gbdt_gpu_grow(const uint16_t* bins, long n, int f, const int* nbins, const int* hoff, int hsize,
+                       const float* g, const float* h, int max_depth, double min_child_weight, double lambda,
+                       double gamma, double eta, void* ws, long long ws_bytes, int* feature, int* split_bin,
+                       uint8_t* default_left, int* left, int* right, double* value, int* node_count, int* leaf_of_row,
+                       double* margin, int rows_per_wg, int feat_tile, hipStream_t stream) {
+  return mifx_gbdt_gpu_grow_ex(bins, n, f, nbins, hoff, hsize, g, h, max_depth, min_child_weight, lambda, gamma, eta,
+                               ws, ws_bytes, feature, split_bin, default_left, left, right, value, node_count,
+                               leaf_of_row, margin, rows_per_wg, feat_tile, 0, 0, MIFX_GS_KEEP_ALL, nullptr, 0, stream);
 }
 
 // margin[i] += tree(row i) for a binned row-major [m, f] matrix (the eval set's margins)
@@ -513,7 +699,8 @@ int mifx_gbdt_gpu_apply(const uint16_t* bins, long m, int f, const int* nbins, c
   const TreeOut t{const_cast<int*>(feature), const_cast<int*>(split_bin), const_cast<uint8_t*>(default_left),
                   const_cast<int*>(left), const_cast<int*>(right), const_cast<double*>(value)};
   k_apply<<<(unsigned)((m + kThreads - 1) / kThreads), kThreads, 0, stream>>>(bins, m, f, nbins, t,
-                                                                               1 << (max_depth + 1), max_depth, margin);
+                                                                               1 << (max_depth + 1), max_depth, margin,
+                                                                               nullptr);
   return (int)hipGetLastError();
 }
 

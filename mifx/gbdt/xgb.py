@@ -18,7 +18,18 @@ its input is: numpy / CPU input on the host, a device tensor through the forest 
 model, also one trained on the host), returning a device tensor. `fixed_point=True` selects the fixed-point
 semantics of csrc/gbdt_split.h (the GPU's only mode, the CPU's option): histograms are integer sums, so a model is bit-reproducible for any thread
 count AND any launch geometry, and `device="cpu", fixed_point=True` is the host twin that reproduces a GPU-trained
-model bit for bit. The default (`device=None`, double histograms on the host) is unchanged."""
+model bit for bit. The default (`device=None`, double histograms on the host) is unchanged.
+
+Stochastic boosting and instance weights, on all three learners (host double, host fixed point, device):
+`subsample`, `colsample_bytree`, `colsample_bylevel` (each in (0, 1]), `fit(..., sample_weight=)` and the classifier's
+`scale_pos_weight`. The draws are our own counter-based rule (csrc/gbdt_sample.h, numpy twin mifx/gbdt/sample.py),
+not XGBoost's random stream: a pure function of `random_state`, the round and the row or feature index, so a model is
+still a pure function of data, parameters and `random_state` -- independent of `n_jobs` and launch geometry, and the
+GPU model equals the host twin bit for bit. A round's tree is grown on exactly the sampled rows, as if the table held
+only them (quantisation exponents, the two-row leaf rule and row counts included); every row's margin then receives
+the tree's output. Weights are float32 and multiply the float32 gradient pair; the intercept is the weighted mean (or
+its log-odds). The eval metric stays unweighted (`sample_weight_eval_set` and `colsample_bynode` are not
+implemented). With the defaults nothing is drawn and no weight is applied: the models are the unsampled ones."""
 from __future__ import annotations
 
 import ctypes
@@ -50,8 +61,17 @@ def _lib():
                                       ctypes.c_double, _D, ctypes.c_int]
     lib.mifx_gbdt_grow_fixed.argtypes = lib.mifx_gbdt_grow.argtypes
     lib.mifx_gbdt_quant_exp.argtypes = [ctypes.c_double, ctypes.c_long]
+    lib.mifx_gbdt_grow_ex.argtypes = lib.mifx_gbdt_grow.argtypes + [_I, ctypes.c_long, _U8]
+    lib.mifx_gbdt_grow_fixed_ex.argtypes = lib.mifx_gbdt_grow_ex.argtypes
+    u64 = ctypes.c_uint64
+    lib.mifx_gbdt_sample_rows.argtypes = [u64, u64, ctypes.c_double, ctypes.c_long, _U8]
+    lib.mifx_gbdt_sample_rows.restype = ctypes.c_long
+    lib.mifx_gbdt_sample_features.argtypes = [u64, u64, u64, ctypes.c_double, _U8, ctypes.c_int, _U8]
+    lib.mifx_gbdt_level_mask.argtypes = [u64, u64, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, _U8,
+                                         _U8]
     for f in (lib.mifx_gbdt_cuts, lib.mifx_gbdt_bin, lib.mifx_gbdt_grow, lib.mifx_gbdt_predict,
-              lib.mifx_gbdt_grow_fixed, lib.mifx_gbdt_quant_exp):
+              lib.mifx_gbdt_grow_fixed, lib.mifx_gbdt_quant_exp, lib.mifx_gbdt_grow_ex, lib.mifx_gbdt_grow_fixed_ex,
+              lib.mifx_gbdt_sample_features, lib.mifx_gbdt_level_mask):
         f.restype = ctypes.c_int
     return lib
 
@@ -86,6 +106,24 @@ def _host(x) -> np.ndarray:
     return x.detach().cpu().numpy() if _is_tensor(x) else np.asarray(x)
 
 
+def sample_rows(seed: int, round: int, subsample: float, n: int) -> np.ndarray:
+    """Ascending int32 ids of the rows that csrc/gbdt_sample.h keeps for (seed, round)."""
+    keep = np.empty(n, np.uint8)
+    _lib().mifx_gbdt_sample_rows(int(seed) & _M64, int(round) & _M64, float(subsample), n, _p(keep, _U8))
+    return np.flatnonzero(keep).astype(np.int32)
+
+
+def level_mask(seed: int, round: int, f: int, max_depth: int, colsample_bytree: float, colsample_bylevel: float):
+    """uint8 [max_depth, f] of csrc/gbdt_sample.h: the features each level of round `round`'s tree may split on."""
+    mask, tree = np.empty((max_depth, f), np.uint8), np.empty(f, np.uint8)
+    _lib().mifx_gbdt_level_mask(int(seed) & _M64, int(round) & _M64, f, max_depth, float(colsample_bytree),
+                                float(colsample_bylevel), _p(tree, _U8), _p(mask, _U8))
+    return mask
+
+
+_M64 = (1 << 64) - 1
+
+
 def _threads() -> int:
     return max(1, min(16, int(os.environ.get("OMP_NUM_THREADS", os.cpu_count() or 1))))
 
@@ -96,16 +134,53 @@ class _Base:
     def __init__(self, n_estimators: int = 100, learning_rate: float = 0.3, max_depth: int = 6,
                  min_child_weight: float = 1.0, reg_lambda: float = 1.0, gamma: float = 0.0, max_bins: int = 256,
                  base_score: float | None = None, n_jobs: int | None = None, random_state: int = 0,
-                 verbosity: int = 0, device: str | None = None, fixed_point: bool | None = None):
+                 verbosity: int = 0, device: str | None = None, fixed_point: bool | None = None,
+                 subsample: float = 1.0, colsample_bytree: float = 1.0, colsample_bylevel: float = 1.0):
         self.n_estimators, self.learning_rate, self.max_depth = n_estimators, learning_rate, max_depth
         self.min_child_weight, self.reg_lambda, self.gamma, self.max_bins = min_child_weight, reg_lambda, gamma, max_bins
         self.base_score, self.n_jobs = base_score, n_jobs
-        self.random_state, self.verbosity = random_state, verbosity  # (the learner is deterministic: no sampling)
+        self.random_state, self.verbosity = random_state, verbosity  # random_state: the seed of every draw
+        self.subsample, self.colsample_bytree, self.colsample_bylevel = subsample, colsample_bytree, colsample_bylevel
+        self._check_rates()
         self.best_iteration, self.best_score, self.evals_result_ = None, None, {}
         self._trees: list[tuple] = []
         self.device, self.fixed_point = device, fixed_point
         if _parse_device(device) is not None and fixed_point is not None and not fixed_point:
             raise ValueError("device='gpu' trains in fixed point only (fixed_point=False is the host's double learner)")
+
+    def _rates(self):
+        """(subsample, colsample_bytree, colsample_bylevel); 1.0 for a model pickled before they existed."""
+        return tuple(float(getattr(self, k, 1.0)) for k in ("subsample", "colsample_bytree", "colsample_bylevel"))
+
+    def _check_rates(self) -> None:
+        for name, r in zip(("subsample", "colsample_bytree", "colsample_bylevel"), self._rates()):
+            if not 0.0 < r <= 1.0:  # (a NaN fails too)
+                raise ValueError(f"{name} must be in (0, 1], got {r}")
+
+    def _seed(self) -> int:
+        return int(getattr(self, "random_state", 0) or 0) & _M64
+
+    def _weights(self, sample_weight, y: np.ndarray):
+        """float32 [n] weights (None: unweighted), validated on the host before anything is launched."""
+        if sample_weight is None:
+            return None
+        w = _host(sample_weight).reshape(-1)
+        if len(w) != len(y):
+            raise ValueError(f"sample_weight must hold one weight per row ({len(y)}), got {len(w)}")
+        w = np.ascontiguousarray(w, np.float32)
+        if not np.isfinite(w).all() or (w < 0).any():
+            raise ValueError("sample_weight must be finite and non-negative")
+        if not (w > 0).any():
+            raise ValueError("sample_weight must not be all zero")
+        return w
+
+    def _round_draws(self, it: int, n: int, f: int):
+        """(rows, level_mask) of boosting round `it`: None where nothing is drawn."""
+        sub, bytree, bylevel = self._rates()
+        rows = sample_rows(self._seed(), it, sub, n) if sub < 1.0 else None
+        mask = level_mask(self._seed(), it, f, int(self.max_depth), bytree, bylevel) \
+            if (bytree < 1.0 or bylevel < 1.0) and int(self.max_depth) > 0 else None
+        return rows, mask
 
     def _gpu_index(self):
         return _parse_device(getattr(self, "device", None))
@@ -129,11 +204,16 @@ class _Base:
         return state
 
     # ---- loss (overridden by the classifier)
-    def _base(self, y: np.ndarray) -> float:
-        return float(np.mean(y))
+    def _base(self, y: np.ndarray, w: np.ndarray | None = None) -> float:
+        return float(np.mean(y)) if w is None else float(np.average(y, weights=w.astype(np.float64)))
 
     def _grad_hess(self, margin: np.ndarray, y: np.ndarray):
         return (margin - y).astype(np.float32), np.ones(len(y), np.float32)
+
+    def _weighted_grad_hess(self, margin: np.ndarray, y: np.ndarray, w: np.ndarray | None):
+        """The float32 pair times the float32 weight: one IEEE multiply each (what the device kernel does)."""
+        g, h = self._grad_hess(margin, y)
+        return (g, h) if w is None else (g * w, h * w)
 
     def _metric_name(self) -> str:
         return "rmse"
@@ -169,18 +249,25 @@ class _Base:
     def _nthreads(self) -> int:
         return self.n_jobs if self.n_jobs and self.n_jobs > 0 else _threads()
 
-    def _grow(self, bins, nbins, g, h, leaf_of_row):
+    def _grow(self, bins, nbins, g, h, leaf_of_row, rows=None, level_mask=None):
+        """One tree. rows (ascending int32 ids, None = all): the tree is grown on these rows only and leaf_of_row is
+        -1 elsewhere; level_mask (uint8 [max_depth, f], None = all): the features each level may split on."""
         n = bins.shape[1]
         cap = 2 ** (self.max_depth + 1)
         fe, sb, left, right = (np.empty(cap, np.int32) for _ in range(4))
         dl = np.empty(cap, np.uint8)
         val = np.empty(cap, np.float64)
-        grow = _lib().mifx_gbdt_grow_fixed if self._fixed() else _lib().mifx_gbdt_grow
+        grow = _lib().mifx_gbdt_grow_fixed_ex if self._fixed() else _lib().mifx_gbdt_grow_ex
+        if rows is not None:
+            rows = np.ascontiguousarray(rows, np.int32)
+        if level_mask is not None:
+            level_mask = np.ascontiguousarray(level_mask, np.uint8)
         cnt = grow(_p(bins, _U16), n, bins.shape[0], _p(nbins, _I), _p(g, _F), _p(h, _F),
                    int(self.max_depth), float(self.min_child_weight), float(self.reg_lambda),
                    float(self.gamma), float(self.learning_rate), self._nthreads(), cap, _p(fe, _I),
                    _p(sb, _I), _p(dl, _U8), _p(left, _I), _p(right, _I), _p(val, _D),
-                   _p(leaf_of_row, _I))
+                   _p(leaf_of_row, _I), None if rows is None else _p(rows, _I), 0 if rows is None else len(rows),
+                   None if level_mask is None else _p(level_mask, _U8))
         if cnt < 0:
             raise RuntimeError("tree exceeded its node capacity")
         thr = np.zeros(cnt, np.float64)
@@ -189,25 +276,29 @@ class _Base:
                 thr[k] = self._cuts[fe[k]][sb[k]]
         return fe[:cnt].copy(), thr, dl[:cnt].copy(), left[:cnt].copy(), right[:cnt].copy(), val[:cnt].copy()
 
-    def fit(self, X, y, eval_set=None, early_stopping_rounds: int | None = None, verbose: bool = False):
-        """Fit the boosted trees. With `device="gpu"`, X, y and the eval set may be numpy arrays, CPU tensors or torch
-        tensors on that GPU (float32 means its exact widening to float64); the table is uploaded once if it is not
-        there already, and its float64 form (8 n f bytes), the bins (2 n f bytes) and one column's sort scratch must
-        fit on the device. Without a device, data on a GPU is refused."""
+    def fit(self, X, y, eval_set=None, early_stopping_rounds: int | None = None, verbose: bool = False, *,
+            sample_weight=None):
+        """Fit the boosted trees. With `device="gpu"`, X, y, the weights and the eval set may be numpy arrays, CPU
+        tensors or torch tensors on that GPU (float32 means its exact widening to float64); the table is uploaded once
+        if it is not there already, and its float64 form (8 n f bytes), the bins (2 n f bytes) and one column's sort
+        scratch must fit on the device. Without a device, data on a GPU is refused. `sample_weight` (keyword only):
+        one non-negative finite weight per row, used as float32; the eval metric stays unweighted."""
         self._dev_forest = None
         gpu = self._gpu_index()
-        self._check_data_device(X, y, *(eval_set[-1] if eval_set else ()))
+        self._check_rates()
+        self._check_data_device(X, y, sample_weight, *(eval_set[-1] if eval_set else ()))
         y = self._check_y(_host(y).reshape(-1))
         X = X if _is_tensor(X) else np.asarray(X)
         if X.ndim != 2 or len(X) != len(y):
             raise ValueError("X must be [n, features] with one label per row")
+        w = self._row_weights(self._weights(sample_weight, y), y)
         self._nfeat = X.shape[1]
         if gpu is not None:
-            return self._fit_gpu(X, y, eval_set, early_stopping_rounds, verbose)
+            return self._fit_gpu(X, y, eval_set, early_stopping_rounds, verbose, w)
         X = np.ascontiguousarray(np.asarray(X, dtype=np.float64))
         bins = self._bin_matrix(X)
         nbins = (self._ncut + 1).astype(np.int32)
-        self._base_margin = float(self.base_score) if self.base_score is not None else self._base(y)
+        self._base_margin = float(self.base_score) if self.base_score is not None else self._base(y, w)
         if self._objective != "reg:squarederror" and self.base_score is not None:
             self._base_margin = float(np.log(self.base_score / (1 - self.base_score)))
         margin = np.full(len(y), self._base_margin)
@@ -222,10 +313,14 @@ class _Base:
         self._trees = []
         best, best_it, since, hist = None, 0, 0, []
         for it in range(int(self.n_estimators)):
-            g, h = self._grad_hess(margin, y)
-            tree = self._grow(bins, nbins, g, h, leaf_of_row)
+            g, h = self._weighted_grad_hess(margin, y, w)
+            rows, mask = self._round_draws(it, len(y), self._nfeat)
+            tree = self._grow(bins, nbins, g, h, leaf_of_row, rows, mask)
             self._trees.append(tree)
-            margin += tree[5][leaf_of_row]
+            if rows is None:
+                margin += tree[5][leaf_of_row]
+            else:  # rows outside the sample have no leaf_of_row: every row walks the tree (the same leaf values)
+                margin += self._predict_trees(X, [tree], 0.0)
             if ev is not None:
                 ev[2][:] += self._predict_trees(ev[0], [tree], 0.0)
                 score = self._metric(ev[2], ev[1])
@@ -245,12 +340,18 @@ class _Base:
             (None, None)
         return self
 
-    def _fit_gpu(self, X, y, eval_set, early_stopping_rounds, verbose):
+    def _row_weights(self, w, y):
+        """The weights the learner uses (the classifier folds scale_pos_weight in)."""
+        return w
+
+    def _fit_gpu(self, X, y, eval_set, early_stopping_rounds, verbose, w=None):
         """The boosting loop on the device learner (mifx/ops/gbdt_gpu.py). The table is uploaded once (unless it is on
         the device already); cuts and binning run there (mifx/ops/gbdt_prep.py: the host's cuts and bins bit for bit,
         the cuts come back once for the trees' thresholds); then gradients, trees and margins stay on the GPU. With an
         eval set its margins come back once per round for the metric (the host's own numpy metric, so the scores are
-        the host twin's bit for bit); the trees come back once at the end. Leaves the attributes of the host path."""
+        the host twin's bit for bit); the trees come back once at the end. Leaves the attributes of the host path.
+        Sampling: the rows are drawn on the device inside the grower; the feature masks of all rounds (pure functions
+        of the seed, [rounds, max_depth, f] bytes) are computed by the host and uploaded once before the first round."""
         import torch
 
         from ..ops import gbdt_gpu as G
@@ -267,13 +368,20 @@ class _Base:
             bins = P.device_bins(Xd, tables)
             del Xd
         nbins = (self._ncut + 1).astype(np.int32)
-        self._base_margin = float(self.base_score) if self.base_score is not None else self._base(y)
+        self._base_margin = float(self.base_score) if self.base_score is not None else self._base(y, w)
         if self._objective != "reg:squarederror" and self.base_score is not None:
             self._base_margin = float(np.log(self.base_score / (1 - self.base_score)))
         rounds = int(self.n_estimators)
+        sub, bytree, bylevel = self._rates()
+        masks = None
+        if (bytree < 1.0 or bylevel < 1.0) and int(self.max_depth) > 0 and rounds > 0:
+            masks = np.stack([level_mask(self._seed(), it, self._nfeat, int(self.max_depth), bytree, bylevel)
+                              for it in range(rounds)])
         with torch.cuda.device(dev):
             bst = G.Booster.from_device_bins(bins, nbins, int(self.max_depth))
             yd = torch.from_numpy(y).to(dev)
+            wd = None if w is None else torch.from_numpy(w).to(dev)
+            masks = None if masks is None else torch.from_numpy(masks).to(dev)
             margin = torch.full((len(y),), self._base_margin, dtype=torch.float64, device=dev)
             g, h = (torch.empty(len(y), dtype=torch.float32, device=dev) for _ in range(2))
             trees = bst.new_trees(max(1, rounds))
@@ -289,8 +397,10 @@ class _Base:
             best, best_it, since, hist, done = None, 0, 0, [], 0
             for it in range(rounds):
                 tree = tuple(t[it] for t in trees)
-                G.grad_hess(self._objective, margin, yd, g, h)
-                bst.grow(g, h, tree, self.min_child_weight, self.reg_lambda, self.gamma, self.learning_rate, margin)
+                G.grad_hess(self._objective, margin, yd, g, h, wd)
+                bst.grow(g, h, tree, self.min_child_weight, self.reg_lambda, self.gamma, self.learning_rate, margin,
+                         subsample=sub, seed=self._seed(), round=it,
+                         level_mask=None if masks is None else masks[it])
                 done = it + 1
                 if ev is not None:
                     bst.apply(ev[0], tree, ev[2])
@@ -372,6 +482,25 @@ class XGBClassifier(_Base):
     """Binary classification (objective binary:logistic); labels are any two values (classes_ sorted)."""
     _objective = "binary:logistic"
 
+    def __init__(self, *args, scale_pos_weight: float = 1.0, **kwargs):
+        """The parameters of XGBRegressor, and scale_pos_weight (> 0): a factor on the weights of class-1 rows."""
+        super().__init__(*args, **kwargs)
+        self.scale_pos_weight = scale_pos_weight
+        self._check_spw()
+
+    def _check_spw(self) -> float:
+        spw = float(getattr(self, "scale_pos_weight", 1.0))
+        if not spw > 0.0 or not np.isfinite(spw):
+            raise ValueError(f"scale_pos_weight must be > 0, got {spw}")
+        return spw
+
+    def _row_weights(self, w, y):
+        spw = self._check_spw()
+        if spw == 1.0:
+            return w
+        w = np.ones(len(y), np.float32) if w is None else w
+        return np.where(y == 1.0, w * np.float32(spw), w).astype(np.float32)
+
     def _check_y(self, y: np.ndarray) -> np.ndarray:
         if not hasattr(self, "classes_") or self._fitting:
             self.classes_ = np.unique(y)
@@ -380,16 +509,18 @@ class XGBClassifier(_Base):
         return (np.searchsorted(self.classes_, y) == 1).astype(np.float64) if len(self.classes_) == 2 \
             else np.zeros(len(y))
 
-    def fit(self, X, y, eval_set=None, early_stopping_rounds: int | None = None, verbose: bool = False):
+    def fit(self, X, y, eval_set=None, early_stopping_rounds: int | None = None, verbose: bool = False, *,
+            sample_weight=None):
         self._fitting = True
-        self._check_data_device(X, y, *(eval_set[-1] if eval_set else ()))
+        self._check_spw()
+        self._check_data_device(X, y, sample_weight, *(eval_set[-1] if eval_set else ()))
         y = _host(y).reshape(-1)
         self._check_y(y)  # classes from the training labels
         self._fitting = False
-        return super().fit(X, y, eval_set, early_stopping_rounds, verbose)
+        return super().fit(X, y, eval_set, early_stopping_rounds, verbose, sample_weight=sample_weight)
 
-    def _base(self, y: np.ndarray) -> float:
-        p = float(np.clip(np.mean(y), 1e-6, 1 - 1e-6))
+    def _base(self, y: np.ndarray, w: np.ndarray | None = None) -> float:
+        p = float(np.clip(super()._base(y, w), 1e-6, 1 - 1e-6))
         return float(np.log(p / (1 - p)))
 
     def _grad_hess(self, margin: np.ndarray, y: np.ndarray):

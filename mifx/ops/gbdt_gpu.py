@@ -2,7 +2,12 @@
 split rule of csrc/gbdt_split.h), the eval set's margin update. Everything stays on the device; nothing synchronises.
 
 `Booster` holds what is resident for a whole fit (binned matrix row-major [n, f], the workspace); `grow_numpy` is the
-one-tree entry the tests use (host arrays in, host arrays out)."""
+one-tree entry the tests use (host arrays in, host arrays out).
+
+Stochastic boosting: `Booster.grow(subsample=, seed=, round=, level_mask=)` grows the tree on the rows that the rule of
+csrc/gbdt_sample.h keeps for (seed, round), as if the table held only them, and lets level d split only on the
+features of `level_mask[d]` (a [max_depth, f] uint8 tensor on the device, computed by the host:
+mifx.gbdt.sample.level_mask); `grad_hess(weight=)` multiplies the float32 pair by float32 instance weights."""
 from __future__ import annotations
 
 import ctypes
@@ -16,6 +21,7 @@ from ._lib import I32, I64, VP, check, ptr, sig, stream_handle
 
 F64 = ctypes.c_double
 LONG = ctypes.c_long
+U64 = ctypes.c_uint64
 ROWS_PER_WG = 2048  # rows of one node that one workgroup accumulates in LDS before it flushes
 FEAT_TILE = 8       # features per workgroup: 8 * 257 slots * 20 B = 41 KB of LDS
 
@@ -31,6 +37,10 @@ def _fns():
         "grad": sig(lib, "mifx_gbdt_gpu_grad", [I32, VP, VP, LONG, VP, VP, VP]),
         "grow": sig(lib, "mifx_gbdt_gpu_grow", [VP, LONG, I32, VP, VP, I32, VP, VP, I32, F64, F64, F64, F64, VP, I64,
                                                  VP, VP, VP, VP, VP, VP, VP, VP, VP, I32, I32, VP]),
+        "grad_w": sig(lib, "mifx_gbdt_gpu_grad_w", [I32, VP, VP, VP, LONG, VP, VP, VP]),
+        "grow_ex": sig(lib, "mifx_gbdt_gpu_grow_ex", [VP, LONG, I32, VP, VP, I32, VP, VP, I32, F64, F64, F64, F64, VP,
+                                                       I64, VP, VP, VP, VP, VP, VP, VP, VP, VP, I32, I32, U64, U64,
+                                                       U64, VP, I32, VP]),
         "apply": sig(lib, "mifx_gbdt_gpu_apply", [VP, LONG, I32, VP, VP, VP, VP, VP, VP, VP, I32, VP, VP]),
     }
 
@@ -59,14 +69,29 @@ def upload_bins(bins: np.ndarray, dev: torch.device) -> torch.Tensor:
     return torch.from_numpy(np.ascontiguousarray(bins).view(np.int16)).to(dev).t().contiguous()
 
 
-def grad_hess(objective: str, margin: torch.Tensor, y: torch.Tensor, g: torch.Tensor, h: torch.Tensor) -> None:
-    """g, h (float32) of "reg:squarederror" or "binary:logistic" from float64 margins and labels."""
+def grad_hess(objective: str, margin: torch.Tensor, y: torch.Tensor, g: torch.Tensor, h: torch.Tensor,
+              weight: torch.Tensor | None = None) -> None:
+    """g, h (float32) of "reg:squarederror" or "binary:logistic" from float64 margins and labels; with `weight`
+    (float32 [n] on the device) each is the unweighted float32 value times the weight, one float32 multiply."""
     obj = {"reg:squarederror": 0, "binary:logistic": 1}[objective]
     assert margin.dtype == y.dtype == torch.float64 and g.dtype == h.dtype == torch.float32
     assert margin.is_contiguous() and y.is_contiguous() and g.is_contiguous() and h.is_contiguous()
     assert len(margin) == len(y) == len(g) == len(h)
-    check(_fns()["grad"](obj, ptr(margin), ptr(y), len(y), ptr(g), ptr(h), stream_handle(margin.device)),
-          "mifx_gbdt_gpu_grad")
+    if weight is None:
+        check(_fns()["grad"](obj, ptr(margin), ptr(y), len(y), ptr(g), ptr(h), stream_handle(margin.device)),
+              "mifx_gbdt_gpu_grad")
+        return
+    assert weight.dtype == torch.float32 and weight.is_contiguous() and len(weight) == len(y)
+    assert weight.device == margin.device
+    check(_fns()["grad_w"](obj, ptr(margin), ptr(y), ptr(weight), len(y), ptr(g), ptr(h),
+                           stream_handle(margin.device)), "mifx_gbdt_gpu_grad_w")
+
+
+def row_threshold(subsample: float) -> int:
+    """thr of csrc/gbdt_sample.h: (uint64)(subsample * 2^32); 2^32 keeps every row."""
+    if not 0.0 < subsample <= 1.0:
+        raise ValueError(f"subsample must be in (0, 1], got {subsample}")
+    return int(float(subsample) * 4294967296.0)
 
 
 class Booster:
@@ -112,10 +137,16 @@ class Booster:
 
     def grow(self, g: torch.Tensor, h: torch.Tensor, tree, min_child_weight: float, reg_lambda: float, gamma: float,
              eta: float, margin: torch.Tensor | None = None, _rows_per_wg: int | None = None,
-             _feat_tile: int | None = None) -> None:
+             _feat_tile: int | None = None, subsample: float = 1.0, seed: int = 0, round: int = 0,
+             level_mask: torch.Tensor | None = None, _margin_route: int = 0) -> None:
         """One tree from float32 g, h into `tree` = (feature, split_bin, default_left, left, right, value, node_count)
         rows; leaf_of_row is set and, if given, margin += value[leaf]. The private arguments are the histogram
-        kernel's launch geometry: the result does not depend on them."""
+        kernel's launch geometry: the result does not depend on them.
+
+        `subsample` < 1 grows the tree on the rows sampled for (seed, round) only (leaf_of_row = -1 for the others;
+        every row's margin still receives the tree's output); `level_mask`: [max_depth, f] uint8 on the device, the
+        features each level may split on. `_margin_route`: how the rows outside the sample get their margin (0: the
+        partition updates the sampled rows and a tree walk the others, 1: one walk over all rows); the same sums."""
         assert g.dtype == h.dtype == torch.float32 and len(g) == len(h) == self.n and g.is_contiguous()
         assert h.is_contiguous() and all(t.is_contiguous() for t in tree)
         assert margin is None or (margin.dtype == torch.float64 and len(margin) == self.n and margin.is_contiguous())
@@ -123,11 +154,28 @@ class Booster:
         if rows < 1 or not 1 <= tile <= _fns()["max_feat_tile"]():
             raise ValueError("launch geometry out of range")
         fe, sb, dl, le, ri, val, cnt = tree
-        check(_fns()["grow"](ptr(self.bins), self.n, self.f, ptr(self.nbins), ptr(self.hoff), self.hsize, ptr(g),
-                             ptr(h), self.max_depth, float(min_child_weight), float(reg_lambda), float(gamma),
-                             float(eta), ptr(self.ws), self.ws.numel(), ptr(fe), ptr(sb), ptr(dl), ptr(le), ptr(ri),
-                             ptr(val), ptr(cnt), ptr(self.leaf_of_row), ptr(margin), rows, tile,
-                             stream_handle(self.dev)), "mifx_gbdt_gpu_grow")
+        thr = row_threshold(subsample)
+        if level_mask is not None:
+            if self.max_depth == 0:
+                level_mask = None
+            elif not (level_mask.dtype == torch.uint8 and level_mask.is_contiguous() and level_mask.device == self.dev
+                      and tuple(level_mask.shape) == (self.max_depth, self.f)):
+                raise ValueError(f"level_mask must be a contiguous uint8 [{self.max_depth}, {self.f}] tensor on "
+                                 f"{self.dev}")
+        if thr == 2 ** 32 and level_mask is None:
+            check(_fns()["grow"](ptr(self.bins), self.n, self.f, ptr(self.nbins), ptr(self.hoff), self.hsize, ptr(g),
+                                 ptr(h), self.max_depth, float(min_child_weight), float(reg_lambda), float(gamma),
+                                 float(eta), ptr(self.ws), self.ws.numel(), ptr(fe), ptr(sb), ptr(dl), ptr(le),
+                                 ptr(ri), ptr(val), ptr(cnt), ptr(self.leaf_of_row), ptr(margin), rows, tile,
+                                 stream_handle(self.dev)), "mifx_gbdt_gpu_grow")
+            return
+        mask64 = 2 ** 64 - 1
+        check(_fns()["grow_ex"](ptr(self.bins), self.n, self.f, ptr(self.nbins), ptr(self.hoff), self.hsize, ptr(g),
+                                ptr(h), self.max_depth, float(min_child_weight), float(reg_lambda), float(gamma),
+                                float(eta), ptr(self.ws), self.ws.numel(), ptr(fe), ptr(sb), ptr(dl), ptr(le),
+                                ptr(ri), ptr(val), ptr(cnt), ptr(self.leaf_of_row), ptr(margin), rows, tile,
+                                int(seed) & mask64, int(round) & mask64, thr, ptr(level_mask), int(_margin_route),
+                                stream_handle(self.dev)), "mifx_gbdt_gpu_grow_ex")
 
     def apply(self, ebins: torch.Tensor, tree, emargin: torch.Tensor) -> None:
         """emargin += tree(row) for a binned row-major [m, f] matrix (upload_bins of the eval set)."""
@@ -141,9 +189,11 @@ class Booster:
 
 def grow_numpy(bins: np.ndarray, nbins: np.ndarray, g: np.ndarray, h: np.ndarray, max_depth: int,
                min_child_weight: float = 1.0, reg_lambda: float = 1.0, gamma: float = 0.0, eta: float = 0.3,
-               device: int = 0, _rows_per_wg: int | None = None, _feat_tile: int | None = None, _booster=None):
+               device: int = 0, _rows_per_wg: int | None = None, _feat_tile: int | None = None, _booster=None,
+               subsample: float = 1.0, seed: int = 0, round: int = 0, level_mask: np.ndarray | None = None):
     """One tree on the device from host arrays: (feature, split_bin, default_left, left, right, value, leaf_of_row),
-    the outputs of the host's mifx_gbdt_grow_fixed."""
+    the outputs of the host's mifx_gbdt_grow_fixed (with subsample / level_mask: of mifx_gbdt_grow_fixed_ex on the
+    rows sampled for (seed, round); level_mask is a host [max_depth, f] uint8 array)."""
     dev = device_for(device)
     with torch.cuda.device(dev):
         b = _booster or Booster(bins, nbins, max_depth, dev)
@@ -151,6 +201,9 @@ def grow_numpy(bins: np.ndarray, nbins: np.ndarray, g: np.ndarray, h: np.ndarray
         tree = tuple(t[0] for t in trees)
         gd = torch.from_numpy(np.ascontiguousarray(g, np.float32)).to(dev)
         hd = torch.from_numpy(np.ascontiguousarray(h, np.float32)).to(dev)
-        b.grow(gd, hd, tree, min_child_weight, reg_lambda, gamma, eta, None, _rows_per_wg, _feat_tile)
+        lm = None if level_mask is None or max_depth == 0 else \
+            torch.from_numpy(np.ascontiguousarray(level_mask, np.uint8).reshape(max_depth, -1)).to(dev)
+        b.grow(gd, hd, tree, min_child_weight, reg_lambda, gamma, eta, None, _rows_per_wg, _feat_tile,
+               subsample=subsample, seed=seed, round=round, level_mask=lm)
         cnt = int(tree[6].item())
         return tuple(t[:cnt].cpu().numpy() for t in tree[:6]) + (b.leaf_of_row.cpu().numpy(),)

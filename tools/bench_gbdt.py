@@ -5,8 +5,11 @@ Synthetic data: standard-normal features (32), 256 bins, depth 6, squared error.
 the training margins' update, exactly what `fit` does per round; device rounds are timed with a host clock around a
 window that ends in a device synchronise, after warm-up rounds. Cuts + binning (host, once per fit) and the upload
 (once per fit) are reported separately. The first device tree is compared with the host twin's (they must be equal).
+`--subsample` / `--colsample-bytree` time stochastic rounds (round t draws with seed 0 and round t, as `fit` does; a
+sampled round also walks the tree for the margins of the rows outside the sample); 1.0, the default, draws nothing.
 
   python tools/bench_gbdt.py --sizes 10000 100000 1000000 --out profiles/gbdt_gpu.jsonl
+  python tools/bench_gbdt.py --sizes 1000000 --subsample 0.5 --host-rounds 1 --out profiles/gbdt_sample.jsonl
 """
 from __future__ import annotations
 
@@ -21,15 +24,16 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def host_rounds(model, bins, nbins, y, rounds):
+def host_rounds(model, bins, nbins, y, rounds, X=None):
     margin = np.full(len(y), float(np.mean(y)))
     leaf = np.empty(len(y), np.int32)
     times, first = [], None
-    for _ in range(rounds):
+    for it in range(rounds):
         t0 = time.perf_counter()
         g, h = model._grad_hess(margin, y)
-        tree = model._grow(bins, nbins, g, h, leaf)
-        margin += tree[5][leaf]
+        rows, mask = model._round_draws(it, len(y), bins.shape[0])
+        tree = model._grow(bins, nbins, g, h, leaf, rows, mask)
+        margin += tree[5][leaf] if rows is None else model._predict_trees(X, [tree], 0.0)
         times.append(time.perf_counter() - t0)
         first = first or tree
     return times, first
@@ -45,6 +49,10 @@ def main(argv=None) -> int:
     ap.add_argument("--rounds", type=int, default=20, help="timed device rounds")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--host-rounds", type=int, default=3)
+    ap.add_argument("--subsample", type=float, default=1.0, help="rows sampled per round, in (0, 1]")
+    ap.add_argument("--colsample-bytree", type=float, default=1.0, help="features sampled per tree, in (0, 1]")
+    ap.add_argument("--margin-route", type=int, default=0, choices=[0, 1],
+                    help="sampled rounds: 0 = partition updates the sampled rows + a walk for the others, 1 = one walk")
     ap.add_argument("--out", default=None, help="append one JSON line per size")
     a = ap.parse_args(argv)
 
@@ -58,16 +66,27 @@ def main(argv=None) -> int:
         r = np.random.default_rng(n)
         X = r.standard_normal((n, a.features))
         y = X[:, 0] * X[:, 1] + np.abs(X[:, 2]) + 0.5 * X[:, 3] + r.normal(0, 0.1, n)
-        kw = dict(max_bins=a.max_bins, max_depth=a.max_depth, n_jobs=a.threads)
+        kw = dict(max_bins=a.max_bins, max_depth=a.max_depth, n_jobs=a.threads, subsample=a.subsample,
+                  colsample_bytree=a.colsample_bytree, random_state=0)
         host, twin = XGBRegressor(**kw), XGBRegressor(fixed_point=True, **kw)
         t0 = time.perf_counter()
         bins = host._bin_matrix(X)
         t_bin = time.perf_counter() - t0
         twin._cuts = host._cuts
         nbins = (host._ncut + 1).astype(np.int32)
+        host._nfeat = twin._nfeat = a.features
+        if a.subsample >= 1.0:
+            X = None  # only a sampled host round walks the raw table (the margins of the rows outside the sample)
+        th, _ = host_rounds(host, bins, nbins, y, a.host_rounds, X)
+        tt, first_twin = host_rounds(twin, bins, nbins, y, a.host_rounds, X)
         del X
-        th, _ = host_rounds(host, bins, nbins, y, a.host_rounds)
-        tt, first_twin = host_rounds(twin, bins, nbins, y, a.host_rounds)
+        total = a.warmup + a.rounds
+        masks = None
+        if a.colsample_bytree < 1.0 and a.max_depth > 0:
+            from mifx.gbdt import xgb
+
+            masks = np.stack([xgb.level_mask(0, it, a.features, a.max_depth, a.colsample_bytree, 1.0)
+                              for it in range(total)])
 
         with torch.cuda.device(dev):
             torch.cuda.synchronize()
@@ -78,12 +97,15 @@ def main(argv=None) -> int:
             t_up = time.perf_counter() - t0
             margin = torch.full((n,), float(np.mean(y)), dtype=torch.float64, device=dev)
             g, h = (torch.empty(n, dtype=torch.float32, device=dev) for _ in range(2))
-            trees = bst.new_trees(a.warmup + a.rounds)
+            trees = bst.new_trees(total)
+            md = None if masks is None else torch.from_numpy(masks).to(dev)
 
             def run(lo, hi):
                 for it in range(lo, hi):
                     G.grad_hess("reg:squarederror", margin, yd, g, h)
-                    bst.grow(g, h, tuple(t[it] for t in trees), 1.0, 1.0, 0.0, 0.3, margin)
+                    bst.grow(g, h, tuple(t[it] for t in trees), 1.0, 1.0, 0.0, 0.3, margin, subsample=a.subsample,
+                             seed=0, round=it, level_mask=None if md is None else md[it],
+                             _margin_route=a.margin_route)
                 torch.cuda.synchronize()
 
             run(0, a.warmup)
@@ -97,6 +119,7 @@ def main(argv=None) -> int:
             del bst, yd, margin, g, h, trees
             torch.cuda.empty_cache()
         rec = {"n": n, "features": a.features, "max_bins": a.max_bins, "max_depth": a.max_depth,
+               "subsample": a.subsample, "colsample_bytree": a.colsample_bytree, "margin_route": a.margin_route,
                "host_threads": a.threads, "bin_s": round(t_bin, 4), "upload_s": round(t_up, 4),
                "host_round_s": [round(t, 5) for t in th], "host_fixed_round_s": [round(t, 5) for t in tt],
                "gpu_round_s": round(t_gpu, 6), "gpu_rounds": a.rounds,
