@@ -33,6 +33,10 @@
 //             over the training bins (k_apply_rest).
 //   features  a [max_depth, f] uint8 mask computed by the host: k_split gives no candidate for a masked (level,
 //             feature), k_hist skips a feature tile that is masked entirely.
+//
+// Multi-class (multi:softprob, K >= 3 classes): k_grad_softmax computes all K gradient pairs of a round in one launch
+// from class-major [K, n] margins; the round then grows K trees with the grower above, tree k on row k of g, h and
+// the margins. The grower itself knows nothing about classes.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -154,6 +158,36 @@ __global__ void k_grad(int objective, const double* margin, const double* y, con
   }
   g[i] = gi;
   h[i] = hi;
+}
+
+// ---- multi:softprob: the K pairs of every row from the margins at the start of the round (XGBClassifier._grad_hess
+// for K >= 3 is the specification). margin, g, h: class-major [K, n]; y: the class index as a double. One row per
+// thread, so a wave reads and writes 64 consecutive elements of one class at a time. Everything up to the two casts is
+// double: the maximum, e_k = exp(m_k - mx), their sum in class order, p_k = e_k / s. exp is evaluated twice per element
+// (K is a run-time value: the e_k cannot wait in registers) from the same expression, so p_k comes from the e_k that
+// entered s; the second and third pass re-read margins that the first one has just brought in.
+__global__ void k_grad_softmax(const double* margin, const double* y, const float* wt, long n, int K, float* g,
+                               float* h) {
+  const long i = blockIdx.x * (long)kThreads + threadIdx.x;
+  if (i >= n) return;
+  const double* m = margin + i;
+  double mx = m[0];
+  for (int k = 1; k < K; ++k) mx = fmax(mx, m[(size_t)k * n]);
+  double s = 0.0;
+  for (int k = 0; k < K; ++k) s += exp(m[(size_t)k * n] - mx);
+  const int yi = (int)y[i];
+  const float w = wt ? wt[i] : 1.0f;
+  for (int k = 0; k < K; ++k) {
+    const double p = exp(m[(size_t)k * n] - mx) / s;
+    float gi = (float)(p - (k == yi ? 1.0 : 0.0));
+    float hi = (float)fmax(2.0 * p * (1.0 - p), 1e-16);
+    if (wt) {
+      gi = gi * w;
+      hi = hi * w;
+    }
+    g[(size_t)k * n + i] = gi;
+    h[(size_t)k * n + i] = hi;
+  }
 }
 
 __global__ void k_init(Ws w) {
@@ -610,6 +644,16 @@ int mifx_gbdt_gpu_grad_w(int objective, const double* margin, const double* y, c
                          float* h, hipStream_t stream) {
   if (n < 1 || objective < 0 || objective > 1) return -1;
   k_grad<<<(unsigned)((n + kThreads - 1) / kThreads), kThreads, 0, stream>>>(objective, margin, y, weight, n, g, h);
+  return (int)hipGetLastError();
+}
+
+// multi:softprob, one launch per round: margin [num_class, n] (class-major) and y [n] (class indices 0 .. num_class - 1
+// as doubles) to g, h [num_class, n]; weight (float32 [n], nullable) as above. num_class has no upper limit here.
+int mifx_gbdt_gpu_grad_softmax(const double* margin, const double* y, const float* weight, long n, int num_class,
+                               float* g, float* h, hipStream_t stream) {
+  if (n < 1 || n >= (1L << 31) || num_class < 1) return -1;
+  k_grad_softmax<<<(unsigned)((n + kThreads - 1) / kThreads), kThreads, 0, stream>>>(margin, y, weight, n, num_class,
+                                                                                      g, h);
   return (int)hipGetLastError();
 }
 

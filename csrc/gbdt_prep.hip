@@ -17,6 +17,8 @@
 //   predict  k_predict: one row per thread; the forest is walked in tree order from packed 24-byte nodes, staged
 //            through LDS in chunks of whole consecutive trees (a tree larger than a chunk is walked from global
 //            memory). One double per row, additions only, in the host's order.
+//            k_predict_multi: the same walk for a multi-class forest (tree t belongs to class t % K), one launch for
+//            all K classes, one double per (class, row), per class the host's order.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -215,6 +217,94 @@ __global__ __launch_bounds__(kPredictThreads) void k_predict(const T* X, long n,
   if (i < n) out[i] = s;
 }
 
+// Multi-class (multi:softprob): tree t belongs to class t % K, and class k's margin is base plus the outputs of trees
+// k, k + K, k + 2K, ... below n_trees, added in that order: per class the additions of k_predict over the class's own
+// trees, so the host's per-class mifx_gbdt_predict bit for bit. The forest is walked ONCE, with the chunk staging of
+// k_predict. out is class-major [K, n]: a wave's 64 rows are 64 consecutive doubles of one class (coalesced), and it is
+// the layout of the training margins. The class of a tree is uniform over the grid, so choosing its sum is a scalar
+// branch. KT > 0 (K <= KT): the K sums stay in registers; acc[] is indexed by unrolled constants only, and the tree
+// loop is unrolled over the classes so that tree t's output is added straight to acc[t % K]. They are stored once.
+// KT == 0 (any K): the thread accumulates into its own K elements of out, initialised to base; no other thread
+// touches them, so plain loads and stores.
+constexpr int kRegClasses = 16;
+
+// adds the outputs of trees [t0, t1) for one row, tree t to class t % K; nd: where node tree_off[t] - o0 lives
+template <class T, int KT>
+__device__ inline void add_trees(double* acc, double* out, long n, long i, const PackedNode* nd, int o0,
+                                 const int* tree_off, int t0, int t1, int K, const T* xi) {
+  int t = t0, c = t0 % K;
+  if constexpr (KT > 0) {
+    while (t < t1) {  // one pass adds up to K trees, classes ascending; the pass that starts at class c adds tree t
+#pragma unroll
+      for (int k = 0; k < KT; ++k)
+        if (c == k && t < t1) {
+          acc[k] += walk(nd + (tree_off[t] - o0), tree_off[t + 1] - tree_off[t], xi);
+          ++t;
+          c = k + 1 == K ? 0 : k + 1;
+        }
+    }
+  } else {
+    for (; t < t1; ++t) {
+      out[(size_t)c * n + i] += walk(nd + (tree_off[t] - o0), tree_off[t + 1] - tree_off[t], xi);
+      c = c + 1 == K ? 0 : c + 1;
+    }
+  }
+}
+
+template <class T, int KT>
+__global__ __launch_bounds__(kPredictThreads) void k_predict_multi(const T* X, long n, int f, const PackedNode* nodes,
+                                                                   const int* tree_off, int n_trees, int K,
+                                                                   double base, int nodes_per_chunk, double* out) {
+  extern __shared__ double lds_raw[];
+  PackedNode* lds = reinterpret_cast<PackedNode*>(lds_raw);
+  const long i = (long)blockIdx.x * kPredictThreads + threadIdx.x;
+  const bool live = i < n;  // a thread past the table only helps staging: it never touches out
+  const T* xi = X + (size_t)(live ? i : 0) * f;
+  double acc[KT > 0 ? KT : 1];
+#pragma unroll
+  for (int k = 0; k < (KT > 0 ? KT : 1); ++k) acc[k] = base;
+  if (KT == 0 && live)
+    for (int k = 0; k < K; ++k) out[(size_t)k * n + i] = base;
+  int t0 = 0;
+  while (t0 < n_trees) {  // every quantity that steers this loop is uniform over the workgroup
+    const int o0 = tree_off[t0];
+    int t1 = t0;
+    while (t1 < n_trees && tree_off[t1 + 1] - o0 <= nodes_per_chunk) ++t1;
+    if (t1 == t0) {  // one tree larger than a chunk: from global memory
+      if (live) add_trees<T, KT>(acc, out, n, i, nodes + o0, o0, tree_off, t0, t0 + 1, K, xi);
+      t0 += 1;
+      continue;
+    }
+    const int total = tree_off[t1] - o0;
+    __syncthreads();  // the previous chunk has been walked
+    for (int q = threadIdx.x; q < total; q += kPredictThreads) lds[q] = nodes[o0 + q];
+    __syncthreads();
+    if (live) add_trees<T, KT>(acc, out, n, i, lds, o0, tree_off, t0, t1, K, xi);
+    t0 = t1;
+  }
+  if (KT > 0 && live) {
+#pragma unroll
+    for (int k = 0; k < KT; ++k)
+      if (k < K) out[(size_t)k * n + i] = acc[k];
+  }
+}
+
+template <class T>
+void launch_predict_multi(const T* X, long n, int f, const PackedNode* nd, const int* tree_off, int n_trees, int K,
+                          double base, int nodes_per_chunk, double* out, int in_registers, hipStream_t stream) {
+  const unsigned grid = (unsigned)((n + kPredictThreads - 1) / kPredictThreads);
+  const size_t lds = (size_t)nodes_per_chunk * sizeof(PackedNode);
+  if (in_registers && K <= 8)
+    k_predict_multi<T, 8><<<grid, kPredictThreads, lds, stream>>>(X, n, f, nd, tree_off, n_trees, K, base,
+                                                                  nodes_per_chunk, out);
+  else if (in_registers)
+    k_predict_multi<T, kRegClasses><<<grid, kPredictThreads, lds, stream>>>(X, n, f, nd, tree_off, n_trees, K, base,
+                                                                            nodes_per_chunk, out);
+  else
+    k_predict_multi<T, 0><<<grid, kPredictThreads, lds, stream>>>(X, n, f, nd, tree_off, n_trees, K, base,
+                                                                  nodes_per_chunk, out);
+}
+
 }  // namespace
 
 extern "C" {
@@ -274,6 +364,27 @@ int mifx_gbdt_prep_predict(const void* X, int is_f64, long n, int f, const void*
   else
     k_predict<float><<<grid, kPredictThreads, lds, stream>>>(static_cast<const float*>(X), n, f, nd, tree_off,
                                                              n_trees, base, nodes_per_chunk, out);
+  return (int)hipGetLastError();
+}
+
+int mifx_gbdt_prep_reg_classes() { return kRegClasses; }
+
+// Multi-class margins in one launch: out [num_class, n] (class-major); out[k, i] = base + the outputs for row i of
+// trees k, k + num_class, ... below n_trees, in that order. in_registers: 1 keeps the class sums in registers (needs
+// num_class <= mifx_gbdt_prep_reg_classes()), 0 accumulates in out itself (any num_class). The same bits either way.
+int mifx_gbdt_prep_predict_multi(const void* X, int is_f64, long n, int f, const void* nodes, const int* tree_off,
+                                 int n_trees, int num_class, double base, int nodes_per_chunk, double* out,
+                                 int in_registers, hipStream_t stream) {
+  if (n < 1 || n >= (1L << 31) || f < 1 || n_trees < 0 || nodes_per_chunk < 1 || nodes_per_chunk > kMaxChunkNodes ||
+      num_class < 1 || in_registers < 0 || in_registers > 1 || (in_registers && num_class > kRegClasses))
+    return -1;
+  const PackedNode* nd = static_cast<const PackedNode*>(nodes);
+  if (is_f64)
+    launch_predict_multi(static_cast<const double*>(X), n, f, nd, tree_off, n_trees, num_class, base, nodes_per_chunk,
+                         out, in_registers, stream);
+  else
+    launch_predict_multi(static_cast<const float*>(X), n, f, nd, tree_off, n_trees, num_class, base, nodes_per_chunk,
+                         out, in_registers, stream);
   return (int)hipGetLastError();
 }
 

@@ -3,12 +3,21 @@ csrc/gbdt.cpp (second-order split gain, learned missing-value directions, depth-
 
 Reference usage: `kubeflow-pipelines/fairing/fairing_xgboost.py:69-87` (XGBRegressor(n_estimators, learning_rate),
 fit with `early_stopping_rounds` and `eval_set`, then `best_score`, `best_iteration`, `predict`). Semantics follow
-XGBoost's scikit-learn API: the eval metric is RMSE (regression) or logloss (binary classification) on the LAST
+XGBoost's scikit-learn API: the eval metric is RMSE (regression), logloss (two classes) or mlogloss (more) on the LAST
 eval set; with early stopping, training stops after `early_stopping_rounds` rounds without improvement and
 `predict` uses the trees up to `best_iteration` (XGBoost >= 1.4's default `iteration_range`). Defaults are
 XGBoost >= 1.0's (learning_rate 0.3, max_depth 6, reg_lambda 1, min_child_weight 1, gamma 0, 256 bins); the
 intercept is the training mean (regression) or its log-odds (classification), XGBoost 2's `base_score` estimate.
-Binary classification only (the reference has no multi-class GBDT).
+
+Classification: two classes train `binary:logistic`; K >= 3 classes train XGBoost's `multi:softprob` on all three
+learners. A boosting round then grows K trees, one per class: `_trees` is round-major and class-minor (tree t belongs
+to class t % K, XGBoost's layout), `n_trees_` counts trees, `n_estimators`, `best_iteration` and
+`early_stopping_rounds` count rounds. Margins are float64 [K, n], class-major, every class starting from the same
+intercept (`base_score` if given, else 0.5). All K gradient pairs come from the margins at the START of the round
+(`XGBClassifier._softmax`, in double: p_k = exp(m_k - max) / sum in class order; g = p_k - [y = k],
+h = max(2 p_k (1 - p_k), 1e-16), both float32), and the tree index t = round * K + k takes the round's place in every
+draw, so each tree has its own sample. `predict_proba` is [n, K] in `classes_` order, `predict` the class of the largest
+margin (ties to the lowest class); the eval metric is the unweighted mlogloss. `scale_pos_weight` is binary only.
 
 `device="gpu"` (or "cuda", "cuda:N") trains on the device learner of csrc/gbdt_gpu.hip: gradients, fixed-point int64
 histograms, split search, row partition and margin updates stay resident on the GPU for the whole fit; cuts and
@@ -207,6 +216,18 @@ class _Base:
     def _base(self, y: np.ndarray, w: np.ndarray | None = None) -> float:
         return float(np.mean(y)) if w is None else float(np.average(y, weights=w.astype(np.float64)))
 
+    def _intercept(self, y: np.ndarray, w: np.ndarray | None) -> float:
+        """The margin every row starts from: base_score (as a margin) if given, else the objective's estimate."""
+        if self.base_score is None:
+            return self._base(y, w)
+        if self._objective != "reg:squarederror":
+            return float(np.log(self.base_score / (1 - self.base_score)))
+        return float(self.base_score)
+
+    def _num_class(self) -> int:
+        """Margin rows per data row (= trees per boosting round): 1 but for the multi-class classifier."""
+        return 1
+
     def _grad_hess(self, margin: np.ndarray, y: np.ndarray):
         return (margin - y).astype(np.float32), np.ones(len(y), np.float32)
 
@@ -298,32 +319,37 @@ class _Base:
         X = np.ascontiguousarray(np.asarray(X, dtype=np.float64))
         bins = self._bin_matrix(X)
         nbins = (self._ncut + 1).astype(np.int32)
-        self._base_margin = float(self.base_score) if self.base_score is not None else self._base(y, w)
-        if self._objective != "reg:squarederror" and self.base_score is not None:
-            self._base_margin = float(np.log(self.base_score / (1 - self.base_score)))
-        margin = np.full(len(y), self._base_margin)
+        self._base_margin = self._intercept(y, w)
+        # K margin rows, class-major: one for the regressor and the binary classifier, one per class for multi:softprob.
+        # A round computes every row's gradients first, then grows tree `it * K + k` on row k; that tree index takes
+        # the round's place in the draws (it IS the round for K = 1).
+        K = self._num_class()
+        margin = np.full((K, len(y)), self._base_margin)
         leaf_of_row = np.empty(len(y), np.int32)
         ev = None
         if eval_set:
             ex, ey = eval_set[-1]
             ex = np.ascontiguousarray(np.asarray(ex, dtype=np.float64))
             ey = self._check_y(np.asarray(ey).reshape(-1))
-            ev_margin = np.full(len(ey), self._base_margin)
+            ev_margin = np.full((K, len(ey)), self._base_margin)
             ev = (ex, ey, ev_margin)
         self._trees = []
         best, best_it, since, hist = None, 0, 0, []
         for it in range(int(self.n_estimators)):
-            g, h = self._weighted_grad_hess(margin, y, w)
-            rows, mask = self._round_draws(it, len(y), self._nfeat)
-            tree = self._grow(bins, nbins, g, h, leaf_of_row, rows, mask)
-            self._trees.append(tree)
-            if rows is None:
-                margin += tree[5][leaf_of_row]
-            else:  # rows outside the sample have no leaf_of_row: every row walks the tree (the same leaf values)
-                margin += self._predict_trees(X, [tree], 0.0)
+            g, h = self._weighted_grad_hess(margin if K > 1 else margin[0], y, w)
+            g, h = g.reshape(K, -1), h.reshape(K, -1)
+            for k in range(K):
+                rows, mask = self._round_draws(it * K + k, len(y), self._nfeat)
+                tree = self._grow(bins, nbins, g[k], h[k], leaf_of_row, rows, mask)
+                self._trees.append(tree)
+                if rows is None:
+                    margin[k] += tree[5][leaf_of_row]
+                else:  # rows outside the sample have no leaf_of_row: every row walks the tree (the same leaf values)
+                    margin[k] += self._predict_trees(X, [tree], 0.0)
+                if ev is not None:
+                    ev[2][k] += self._predict_trees(ev[0], [tree], 0.0)
             if ev is not None:
-                ev[2][:] += self._predict_trees(ev[0], [tree], 0.0)
-                score = self._metric(ev[2], ev[1])
+                score = self._metric(ev[2] if K > 1 else ev[2][0], ev[1])
                 hist.append(score)
                 if verbose:
                     logging.info("[%d]\tvalidation_0-%s:%.5f", it, self._metric_name(), score)
@@ -350,8 +376,10 @@ class _Base:
         the cuts come back once for the trees' thresholds); then gradients, trees and margins stay on the GPU. With an
         eval set its margins come back once per round for the metric (the host's own numpy metric, so the scores are
         the host twin's bit for bit); the trees come back once at the end. Leaves the attributes of the host path.
-        Sampling: the rows are drawn on the device inside the grower; the feature masks of all rounds (pure functions
-        of the seed, [rounds, max_depth, f] bytes) are computed by the host and uploaded once before the first round."""
+        Sampling: the rows are drawn on the device inside the grower; the feature masks of all trees (pure functions
+        of the seed, [trees, max_depth, f] bytes) are computed by the host and uploaded once before the first round.
+        Multi-class: margins, g and h are [K, n] on the device; a round is one softmax gradient launch and K calls of
+        the grower (and of the eval update), each on one class's row."""
         import torch
 
         from ..ops import gbdt_gpu as G
@@ -368,23 +396,21 @@ class _Base:
             bins = P.device_bins(Xd, tables)
             del Xd
         nbins = (self._ncut + 1).astype(np.int32)
-        self._base_margin = float(self.base_score) if self.base_score is not None else self._base(y, w)
-        if self._objective != "reg:squarederror" and self.base_score is not None:
-            self._base_margin = float(np.log(self.base_score / (1 - self.base_score)))
-        rounds = int(self.n_estimators)
+        self._base_margin = self._intercept(y, w)
+        rounds, K = int(self.n_estimators), self._num_class()  # K trees per round, tree it * K + k on margin row k
         sub, bytree, bylevel = self._rates()
         masks = None
         if (bytree < 1.0 or bylevel < 1.0) and int(self.max_depth) > 0 and rounds > 0:
-            masks = np.stack([level_mask(self._seed(), it, self._nfeat, int(self.max_depth), bytree, bylevel)
-                              for it in range(rounds)])
+            masks = np.stack([level_mask(self._seed(), t, self._nfeat, int(self.max_depth), bytree, bylevel)
+                              for t in range(rounds * K)])
         with torch.cuda.device(dev):
             bst = G.Booster.from_device_bins(bins, nbins, int(self.max_depth))
             yd = torch.from_numpy(y).to(dev)
             wd = None if w is None else torch.from_numpy(w).to(dev)
             masks = None if masks is None else torch.from_numpy(masks).to(dev)
-            margin = torch.full((len(y),), self._base_margin, dtype=torch.float64, device=dev)
-            g, h = (torch.empty(len(y), dtype=torch.float32, device=dev) for _ in range(2))
-            trees = bst.new_trees(max(1, rounds))
+            margin = torch.full((K, len(y)), self._base_margin, dtype=torch.float64, device=dev)
+            g, h = (torch.empty((K, len(y)), dtype=torch.float32, device=dev) for _ in range(2))
+            trees = bst.new_trees(max(1, rounds * K))
             ev = None
             if eval_set:
                 ex, ey = eval_set[-1]
@@ -393,18 +419,24 @@ class _Base:
                 if ex.ndim != 2 or ex.shape[1] != self._nfeat or len(ex) != len(ey) or not len(ey):
                     raise ValueError(f"the eval set must be [m, {self._nfeat}] with one label per row")
                 ev = (P.device_bins(P.as_device_matrix(ex, dev), tables), ey,
-                      torch.full((len(ey),), self._base_margin, dtype=torch.float64, device=dev))
+                      torch.full((K, len(ey)), self._base_margin, dtype=torch.float64, device=dev))
             best, best_it, since, hist, done = None, 0, 0, [], 0
             for it in range(rounds):
-                tree = tuple(t[it] for t in trees)
-                G.grad_hess(self._objective, margin, yd, g, h, wd)
-                bst.grow(g, h, tree, self.min_child_weight, self.reg_lambda, self.gamma, self.learning_rate, margin,
-                         subsample=sub, seed=self._seed(), round=it,
-                         level_mask=None if masks is None else masks[it])
-                done = it + 1
+                if K > 1:  # every class's pair from the margins at the start of the round, one launch
+                    G.grad_hess_softmax(margin, yd, g, h, wd)
+                else:
+                    G.grad_hess(self._objective, margin[0], yd, g[0], h[0], wd)
+                for k in range(K):
+                    tree = tuple(t[it * K + k] for t in trees)
+                    bst.grow(g[k], h[k], tree, self.min_child_weight, self.reg_lambda, self.gamma, self.learning_rate,
+                             margin[k], subsample=sub, seed=self._seed(), round=it * K + k,
+                             level_mask=None if masks is None else masks[it * K + k])
+                    if ev is not None:
+                        bst.apply(ev[0], tree, ev[2][k])
+                done = (it + 1) * K
                 if ev is not None:
-                    bst.apply(ev[0], tree, ev[2])
-                    score = self._metric(ev[2].cpu().numpy(), ev[1])  # the round's one read-back
+                    em = ev[2].cpu().numpy()  # the round's one read-back
+                    score = self._metric(em if K > 1 else em[0], ev[1])
                     hist.append(score)
                     if verbose:
                         logging.info("[%d]\tvalidation_0-%s:%.5f", it, self._metric_name(), score)
@@ -452,12 +484,17 @@ class _Base:
     def _margin(self, X):
         """Margins where the data is: a tensor on a GPU goes through the forest kernel on that GPU and gives a tensor
         there (the host's bits); anything else takes the host path, which needs no GPU."""
-        n = len(self._trees) if self.best_iteration is None else self.best_iteration + 1
+        n = self._tree_limit()
         if _on_gpu(X):
             return self._margin_device(X, n)
         return self._predict_trees(_host(X) if _is_tensor(X) else X, self._trees[:n], self._base_margin)
 
-    def _margin_device(self, X, n_trees: int):
+    def _tree_limit(self) -> int:
+        """Trees that predict uses: best_iteration counts rounds, a round holds _num_class() trees."""
+        return len(self._trees) if self.best_iteration is None else (self.best_iteration + 1) * self._num_class()
+
+    def _margin_device(self, X, n_trees: int, num_class: int = 1):
+        """num_class > 1: the [num_class, n] margins of a multi-class forest, one walk for all classes."""
         from ..ops import gbdt_prep as P
 
         if X.dim() != 2 or X.shape[1] != self._nfeat:
@@ -467,7 +504,10 @@ class _Base:
             cache = self._dev_forest = {}
         if X.device.index not in cache:  # the packed trees, uploaded once per model and device (fit resets them)
             cache[X.device.index] = P.DeviceForest(self._trees, self._nfeat, X.device)
-        return P.predict(cache[X.device.index], P.as_device_matrix(X, X.device), self._base_margin, n_trees)
+        Xd = P.as_device_matrix(X, X.device)
+        if num_class > 1:
+            return P.predict_multi(cache[X.device.index], Xd, self._base_margin, num_class, n_trees)
+        return P.predict(cache[X.device.index], Xd, self._base_margin, n_trees)
 
 
 class XGBRegressor(_Base):
@@ -479,7 +519,8 @@ class XGBRegressor(_Base):
 
 
 class XGBClassifier(_Base):
-    """Binary classification (objective binary:logistic); labels are any two values (classes_ sorted)."""
+    """Classification: two classes train binary:logistic, K >= 3 classes multi:softprob (K trees per boosting round,
+    tree t for class t % K). Labels are any sortable values (classes_ sorted)."""
     _objective = "binary:logistic"
 
     def __init__(self, *args, scale_pos_weight: float = 1.0, **kwargs):
@@ -494,18 +535,31 @@ class XGBClassifier(_Base):
             raise ValueError(f"scale_pos_weight must be > 0, got {spw}")
         return spw
 
+    def _num_class(self) -> int:
+        """K for K >= 3 classes (multi:softprob: K margin rows, K trees per round); 1 for binary:logistic, which is
+        also what a model pickled before multi-class existed is."""
+        k = len(getattr(self, "classes_", ()))
+        return k if k >= 3 else 1
+
     def _row_weights(self, w, y):
         spw = self._check_spw()
         if spw == 1.0:
             return w
+        if self._num_class() > 1:
+            raise ValueError(f"scale_pos_weight is a binary parameter: with {self._num_class()} classes it must be 1, "
+                             f"got {spw} (use sample_weight)")
         w = np.ones(len(y), np.float32) if w is None else w
         return np.where(y == 1.0, w * np.float32(spw), w).astype(np.float32)
 
     def _check_y(self, y: np.ndarray) -> np.ndarray:
+        """Labels to what the loss reads: 0.0 / 1.0 (binary), the class index as a double (multi-class)."""
         if not hasattr(self, "classes_") or self._fitting:
             self.classes_ = np.unique(y)
-            if len(self.classes_) > 2:
-                raise ValueError("XGBClassifier here is binary (binary:logistic)")
+        if len(self.classes_) >= 3:
+            idx = np.minimum(np.searchsorted(self.classes_, y), len(self.classes_) - 1)
+            if not (self.classes_[idx] == y).all():
+                raise ValueError("the eval set holds labels that are not among the training labels (classes_)")
+            return idx.astype(np.float64)
         return (np.searchsorted(self.classes_, y) == 1).astype(np.float64) if len(self.classes_) == 2 \
             else np.zeros(len(y))
 
@@ -523,19 +577,63 @@ class XGBClassifier(_Base):
         p = float(np.clip(super()._base(y, w), 1e-6, 1 - 1e-6))
         return float(np.log(p / (1 - p)))
 
+    def _intercept(self, y: np.ndarray, w: np.ndarray | None) -> float:
+        if self._num_class() == 1:
+            return super()._intercept(y, w)
+        # multi:softprob: one raw margin for every class (softmax is shift invariant: only raw margins see it)
+        return float(self.base_score) if self.base_score is not None else 0.5
+
+    @staticmethod
+    def _softmax(margin: np.ndarray) -> np.ndarray:
+        """p [K, n] from margins [K, n], in double: e_k = exp(m_k - max_k m_k), s = e_0 + e_1 + ... in this order,
+        p_k = e_k / s. The one definition: gradients, mlogloss and predict_proba use it, and the device kernel
+        k_grad_softmax (csrc/gbdt_gpu.hip) follows it operation for operation."""
+        e = np.exp(margin - margin.max(0))
+        s = e[0].copy()
+        for k in range(1, len(e)):
+            s += e[k]
+        return e / s
+
     def _grad_hess(self, margin: np.ndarray, y: np.ndarray):
+        if margin.ndim == 2:  # multi:softprob, margins [K, n], y the class index: XGBoost's softmax pair
+            p = self._softmax(margin)
+            onehot = (y == np.arange(len(margin), dtype=np.float64)[:, None]).astype(np.float64)
+            return (p - onehot).astype(np.float32), np.maximum(2.0 * p * (1.0 - p), 1e-16).astype(np.float32)
         p = 1.0 / (1.0 + np.exp(-margin))
         return (p - y).astype(np.float32), np.maximum(p * (1 - p), 1e-16).astype(np.float32)
 
     def _metric_name(self) -> str:
-        return "logloss"
+        return "mlogloss" if self._num_class() > 1 else "logloss"
 
     def _metric(self, margin: np.ndarray, y: np.ndarray) -> float:
+        if margin.ndim == 2:  # mlogloss from [K, m] margins
+            p = self._softmax(margin)[y.astype(np.int64), np.arange(len(y))]
+            return float(-np.mean(np.log(np.clip(p, 1e-15, 1 - 1e-15))))
         p = np.clip(1.0 / (1.0 + np.exp(-margin)), 1e-15, 1 - 1e-15)
         return float(-np.mean(y * np.log(p) + (1 - y) * np.log(1 - p)))
 
+    def _margins(self, X):
+        """Multi-class margins [K, n], class k from trees k, k + K, ... below the tree limit: numpy for host input
+        (the per-class host walk), a device tensor for a tensor on a GPU (one walk of the forest kernel)."""
+        K, limit = self._num_class(), self._tree_limit()
+        if _on_gpu(X):
+            return self._margin_device(X, limit, K)
+        X = _host(X) if _is_tensor(X) else X
+        return np.stack([self._predict_trees(X, self._trees[k:limit:K], self._base_margin) for k in range(K)])
+
     def predict_proba(self, X):
-        """[n, 2] probabilities: numpy for host input, a tensor on the input's device for a tensor on a GPU."""
+        """[n, K] probabilities, columns in classes_ order (K = 2 for binary:logistic): numpy for host input, a tensor
+        on the input's device for a tensor on a GPU."""
+        if self._num_class() > 1:
+            m = self._margins(X)
+            if not _is_tensor(m):
+                return np.ascontiguousarray(self._softmax(m).T)
+            torch = sys.modules["torch"]
+            e = torch.exp(m - m.max(0).values)
+            s = e[0].clone()
+            for k in range(1, len(e)):
+                s += e[k]
+            return (e / s).t().contiguous()
         m = self._margin(X)
         if _is_tensor(m):
             torch = sys.modules["torch"]
@@ -546,5 +644,13 @@ class XGBClassifier(_Base):
 
     def predict(self, X) -> np.ndarray:
         """Labels, always a numpy array (classes_ may hold strings): for a device tensor, one read-back of the class
-        index."""
+        index. Multi-class: the class of the largest margin (softmax is monotone, so it is the most probable class),
+        ties to the lowest class."""
+        if self._num_class() > 1:
+            m = self._margins(X)
+            if not _is_tensor(m):
+                return self.classes_[np.argmax(m, 0)]
+            torch = sys.modules["torch"]
+            k = torch.arange(len(m), device=m.device)[:, None]  # the lowest class among the largest margins
+            return self.classes_[_host(torch.where(m == m.max(0).values, k, len(m)).min(0).values)]
         return self.classes_[_host(self.predict_proba(X)[:, 1] > 0.5).astype(int)]

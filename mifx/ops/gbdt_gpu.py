@@ -7,7 +7,11 @@ one-tree entry the tests use (host arrays in, host arrays out).
 Stochastic boosting: `Booster.grow(subsample=, seed=, round=, level_mask=)` grows the tree on the rows that the rule of
 csrc/gbdt_sample.h keeps for (seed, round), as if the table held only them, and lets level d split only on the
 features of `level_mask[d]` (a [max_depth, f] uint8 tensor on the device, computed by the host:
-mifx.gbdt.sample.level_mask); `grad_hess(weight=)` multiplies the float32 pair by float32 instance weights."""
+mifx.gbdt.sample.level_mask); `grad_hess(weight=)` multiplies the float32 pair by float32 instance weights.
+
+Multi-class (multi:softprob): `grad_hess_softmax` computes the pairs of all K classes from class-major [K, n] margins
+in one launch; the round then calls `Booster.grow` (and `Booster.apply`) once per class on row k of g, h and the
+margins, with the tree index round * K + k as `round`."""
 from __future__ import annotations
 
 import ctypes
@@ -42,6 +46,7 @@ def _fns():
                                                        I64, VP, VP, VP, VP, VP, VP, VP, VP, VP, I32, I32, U64, U64,
                                                        U64, VP, I32, VP]),
         "apply": sig(lib, "mifx_gbdt_gpu_apply", [VP, LONG, I32, VP, VP, VP, VP, VP, VP, VP, I32, VP, VP]),
+        "grad_softmax": sig(lib, "mifx_gbdt_gpu_grad_softmax", [VP, VP, VP, LONG, I32, VP, VP, VP]),
     }
 
 
@@ -85,6 +90,23 @@ def grad_hess(objective: str, margin: torch.Tensor, y: torch.Tensor, g: torch.Te
     assert weight.device == margin.device
     check(_fns()["grad_w"](obj, ptr(margin), ptr(y), ptr(weight), len(y), ptr(g), ptr(h),
                            stream_handle(margin.device)), "mifx_gbdt_gpu_grad_w")
+
+
+def grad_hess_softmax(margin: torch.Tensor, y: torch.Tensor, g: torch.Tensor, h: torch.Tensor,
+                      weight: torch.Tensor | None = None) -> None:
+    """g, h (float32 [K, n]) of "multi:softprob" from float64 margins [K, n] (class-major) and float64 class indices
+    y [n], all K classes in one launch: XGBClassifier._grad_hess for K >= 3 is the specification (softmax in double,
+    the sum in class order, h = max(2 p (1 - p), 1e-16)). `weight` as in grad_hess. K is margin.shape[0]: any K >= 1."""
+    assert margin.dim() == 2 and margin.shape == g.shape == h.shape and y.shape == (margin.shape[1],)
+    assert margin.dtype == y.dtype == torch.float64 and g.dtype == h.dtype == torch.float32
+    assert margin.is_contiguous() and y.is_contiguous() and g.is_contiguous() and h.is_contiguous()
+    assert y.device == g.device == h.device == margin.device
+    if weight is not None:
+        assert weight.dtype == torch.float32 and weight.is_contiguous() and weight.shape == y.shape
+        assert weight.device == margin.device
+    K, n = margin.shape
+    check(_fns()["grad_softmax"](ptr(margin), ptr(y), ptr(weight), n, K, ptr(g), ptr(h),
+                                 stream_handle(margin.device)), "mifx_gbdt_gpu_grad_softmax")
 
 
 def row_threshold(subsample: float) -> int:

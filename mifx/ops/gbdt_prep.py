@@ -38,6 +38,9 @@ def _fns():
         "cuts": sig(lib, "mifx_gbdt_prep_cuts", [VP, LONG, VP, I32, VP, VP, VP, I32, VP]),
         "bin": sig(lib, "mifx_gbdt_prep_bin", [VP, I32, LONG, I32, VP, VP, VP, VP, I32, I32, VP]),
         "predict": sig(lib, "mifx_gbdt_prep_predict", [VP, I32, LONG, I32, VP, VP, I32, F64, I32, VP, VP]),
+        "reg_classes": sig(lib, "mifx_gbdt_prep_reg_classes", []),
+        "predict_multi": sig(lib, "mifx_gbdt_prep_predict_multi", [VP, I32, LONG, I32, VP, VP, I32, I32, F64, I32, VP,
+                                                                   I32, VP]),
     }
     assert fns["node_bytes"]() == NODE_DTYPE.itemsize
     return fns
@@ -189,4 +192,67 @@ def predict(forest: DeviceForest, Xd: torch.Tensor, base: float, n_trees: int | 
         check(_fns()["predict"](ptr(Xd), int(Xd.dtype == torch.float64), n, f, ptr(forest.nodes),
                                 ptr(forest.tree_off), n_trees, float(base), chunk, ptr(out),
                                 stream_handle(Xd.device)), "mifx_gbdt_prep_predict")
+    return out
+
+
+def _class_major(forest: DeviceForest, num_class: int):
+    """The forest's nodes regrouped by class (class k's trees k, k + num_class, ... side by side), their offsets and
+    the position of every class's first tree: what k_predict needs to walk one class. Built on the device from the
+    packed forest, once per forest and num_class."""
+    cache = forest.__dict__.setdefault("_by_class", {})
+    if num_class not in cache:
+        off = forest.tree_off.cpu().numpy().astype(np.int64)
+        per_class = [np.arange(k, forest.n_trees, num_class) for k in range(num_class)]
+        order = np.concatenate(per_class)
+        new_off = np.concatenate([[0], np.cumsum((off[1:] - off[:-1])[order])])
+        idx = np.concatenate([np.arange(off[t], off[t + 1]) for t in order] + [np.zeros(0, np.int64)])
+        nodes = forest.nodes.view(-1, NODE_DTYPE.itemsize)[torch.from_numpy(idx).to(forest.dev)].contiguous()
+        first = np.concatenate([[0], np.cumsum([len(c) for c in per_class])])
+        cache[num_class] = (nodes, torch.from_numpy(new_off.astype(np.int32)).to(forest.dev), first)
+    return cache[num_class]
+
+
+def predict_multi(forest: DeviceForest, Xd: torch.Tensor, base: float, num_class: int, n_trees: int | None = None,
+                  _nodes_per_chunk: int | None = None, _route: str | None = None) -> torch.Tensor:
+    """Multi-class margins of a device table: float64 [num_class, n] on the device, row k = base + the outputs of
+    trees k, k + num_class, ... below n_trees (all by default), added in that order -- the bits of the host's
+    mifx_gbdt_predict over the class's own trees. Class-major, because a wave's 64 rows are then 64 consecutive doubles
+    of one class (coalesced stores) and because it is the layout of the training margins.
+
+    `_route` (the result does not depend on it; the default is the faster one measured, profiles/gbdt_multiclass.md):
+      "registers"  ONE walk of the forest, the class sums in registers: num_class <= 16, the default there
+      "launches"   one launch of the single-output kernel per class over a class-major copy of the forest (made once
+                   per forest): the default for more classes
+      "output"     one walk, every thread accumulating in its own elements of the output: any num_class"""
+    _check_matrix(Xd)
+    n, f = Xd.shape
+    if f != forest.nfeat or Xd.device != forest.dev:
+        raise ValueError(f"expected [n, {forest.nfeat}] features on {forest.dev}")
+    n_trees = forest.n_trees if n_trees is None else int(n_trees)
+    num_class, chunk = int(num_class), int(_nodes_per_chunk or NODES_PER_CHUNK)
+    if num_class < 1:
+        raise ValueError(f"num_class must be >= 1, got {num_class}")
+    if not 0 <= n_trees <= forest.n_trees:
+        raise ValueError(f"n_trees must be in [0, {forest.n_trees}]")
+    if not 1 <= chunk <= _fns()["max_chunk_nodes"]():
+        raise ValueError("launch geometry out of range")
+    fits = num_class <= _fns()["reg_classes"]()
+    route = ("registers" if fits else "launches") if _route is None else _route
+    if route not in ("registers", "launches", "output"):
+        raise ValueError(f"unknown route {route!r}")
+    if route == "registers" and not fits:
+        raise ValueError(f"the register route holds at most {_fns()['reg_classes']()} classes")
+    is64, stream = int(Xd.dtype == torch.float64), stream_handle(Xd.device)
+    with torch.cuda.device(Xd.device):
+        out = torch.empty((num_class, n), dtype=torch.float64, device=Xd.device)
+        if route == "launches":
+            nodes, tree_off, first = _class_major(forest, num_class)
+            for k in range(num_class):  # class k's trees below n_trees are a prefix of its block
+                check(_fns()["predict"](ptr(Xd), is64, n, f, ptr(nodes), VP(tree_off.data_ptr() + 4 * int(first[k])),
+                                        len(range(k, n_trees, num_class)), float(base), chunk,
+                                        VP(out.data_ptr() + 8 * k * n), stream), "mifx_gbdt_prep_predict")
+            return out
+        check(_fns()["predict_multi"](ptr(Xd), is64, n, f, ptr(forest.nodes), ptr(forest.tree_off), n_trees, num_class,
+                                      float(base), chunk, ptr(out), int(route == "registers"), stream),
+              "mifx_gbdt_prep_predict_multi")
     return out
