@@ -20,6 +20,11 @@
 //
 // Stochastic boosting (the *_ex entries): a tree is grown on a list of sampled rows as if the table held only them,
 // and a [max_depth, f] mask names the features each level may split on; the draws themselves are gbdt_sample.h's.
+//
+// Node statistics (the *_stats entries): every grower can also record each node's gain and cover (hessian sum), which
+// feature importances and feature contributions need. mifx_gbdt_paths_build turns a forest with covers into the path
+// table of gbdt_shap.h and mifx_gbdt_contribs evaluates path-dependent TreeSHAP from it (the device twin is k_contribs
+// in gbdt_prep.hip).
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -28,6 +33,7 @@
 #include <vector>
 
 #include "gbdt_sample.h"
+#include "gbdt_shap.h"
 #include "gbdt_split.h"
 
 namespace {
@@ -176,10 +182,15 @@ int mifx_gbdt_bin(const double* X, long n, int f, const double* cuts, const int*
 // only them, leaf_of_row is -1 for the others, and an empty list gives the one-node tree of value +0.0.
 // level_mask (null = all features): [max_depth, f], a feature with level_mask[d * f + j] == 0 yields no candidate
 // at depth d, as nbins[j] == 1 does. -2: a row list that is not ascending inside [0, n).
-int mifx_gbdt_grow_ex(const uint16_t* bins, long n, int f, const int* nbins, const float* g, const float* h,
-                      int max_depth, double min_child_weight, double lambda, double gamma, double eta, int threads,
-                      int max_nodes, int* feature, int* split_bin, uint8_t* default_left, int* left, int* right,
-                      double* value, int* leaf_of_row, const int* sample, long n_rows, const uint8_t* level_mask) {
+//
+// node_gain / node_cover (nullable, max_nodes doubles each): per node the gain the learner maximised,
+// 0.5 * (score_L + score_R - score_parent) - gamma (0.0 at a leaf), and the node's hessian sum over the rows the tree
+// was grown on. The tree does not depend on whether they are asked for.
+int mifx_gbdt_grow_stats(const uint16_t* bins, long n, int f, const int* nbins, const float* g, const float* h,
+                         int max_depth, double min_child_weight, double lambda, double gamma, double eta, int threads,
+                         int max_nodes, int* feature, int* split_bin, uint8_t* default_left, int* left, int* right,
+                         double* value, int* leaf_of_row, const int* sample, long n_rows, const uint8_t* level_mask,
+                         double* node_gain, double* node_cover) {
   if (!rows_ok(sample, n_rows, n)) return -2;
   std::vector<int> off(f + 1, 0);
   for (int j = 0; j < f; ++j) off[j + 1] = off[j] + nbins[j] + 1;
@@ -250,6 +261,8 @@ int mifx_gbdt_grow_ex(const uint16_t* bins, long n, int f, const int* nbins, con
     default_left[count] = 0;
     left[count] = right[count] = -1;
     value[count] = 0.0;
+    if (node_gain) node_gain[count] = 0.0;
+    if (node_cover) node_cover[count] = 0.0;
     return count++;
   };
   Node root{0, (int)ns, 0, new_node(), 0.0, 0.0, {}};
@@ -271,10 +284,12 @@ int mifx_gbdt_grow_ex(const uint16_t* bins, long n, int f, const int* nbins, con
     for (Node& nd : level) {
       Split s;
       if (nd.depth < max_depth && nd.end - nd.begin >= 2) s = best_split(nd);
+      if (node_cover) node_cover[nd.id] = nd.h;
       if (s.feature < 0 || s.gain <= 1e-6) {
         make_leaf(nd);
         continue;
       }
+      if (node_gain) node_gain[nd.id] = s.gain;
       // partition rows: left = bin <= s.bin (or missing with default_left)
       const uint16_t* bj = bins + (size_t)s.feature * n;
       auto goes_left = [&](int r) {
@@ -311,6 +326,15 @@ int mifx_gbdt_grow_ex(const uint16_t* bins, long n, int f, const int* nbins, con
   return count;
 }
 
+int mifx_gbdt_grow_ex(const uint16_t* bins, long n, int f, const int* nbins, const float* g, const float* h,
+                      int max_depth, double min_child_weight, double lambda, double gamma, double eta, int threads,
+                      int max_nodes, int* feature, int* split_bin, uint8_t* default_left, int* left, int* right,
+                      double* value, int* leaf_of_row, const int* sample, long n_rows, const uint8_t* level_mask) {
+  return mifx_gbdt_grow_stats(bins, n, f, nbins, g, h, max_depth, min_child_weight, lambda, gamma, eta, threads,
+                              max_nodes, feature, split_bin, default_left, left, right, value, leaf_of_row, sample,
+                              n_rows, level_mask, nullptr, nullptr);
+}
+
 int mifx_gbdt_grow(const uint16_t* bins, long n, int f, const int* nbins, const float* g, const float* h,
                    int max_depth, double min_child_weight, double lambda, double gamma, double eta, int threads,
                    int max_nodes, int* feature, int* split_bin, uint8_t* default_left, int* left, int* right,
@@ -329,11 +353,12 @@ int mifx_gbdt_quant_exp(double amax, long n) { return mifx_gb_quant_exp(amax, n)
 // quantise exactly and sum exactly in double (small dyadic rationals) it grows exactly mifx_gbdt_grow's tree.
 // sample / level_mask: as in mifx_gbdt_grow_ex; the exponents come from the sampled rows alone (their largest
 // magnitudes and their count).
-int mifx_gbdt_grow_fixed_ex(const uint16_t* bins, long n, int f, const int* nbins, const float* g, const float* h,
-                            int max_depth, double min_child_weight, double lambda, double gamma, double eta,
-                            int threads, int max_nodes, int* feature, int* split_bin, uint8_t* default_left, int* left,
-                            int* right, double* value, int* leaf_of_row, const int* sample, long n_rows,
-                            const uint8_t* level_mask) {
+// node_gain / node_cover: as in mifx_gbdt_grow_stats; the gain is MifxGbSplit::gain, the cover mifx_gb_dequant(Qh, eh).
+int mifx_gbdt_grow_fixed_stats(const uint16_t* bins, long n, int f, const int* nbins, const float* g, const float* h,
+                               int max_depth, double min_child_weight, double lambda, double gamma, double eta,
+                               int threads, int max_nodes, int* feature, int* split_bin, uint8_t* default_left,
+                               int* left, int* right, double* value, int* leaf_of_row, const int* sample, long n_rows,
+                               const uint8_t* level_mask, double* node_gain, double* node_cover) {
   if (!rows_ok(sample, n_rows, n)) return -2;
   struct QNode {
     int begin, end, depth, id;
@@ -411,6 +436,8 @@ int mifx_gbdt_grow_fixed_ex(const uint16_t* bins, long n, int f, const int* nbin
     default_left[count] = 0;
     left[count] = right[count] = -1;
     value[count] = 0.0;
+    if (node_gain) node_gain[count] = 0.0;
+    if (node_cover) node_cover[count] = 0.0;
     return count++;
   };
   QNode root{0, (int)ns, 0, new_node(), 0, 0, {}, {}, {}};
@@ -428,6 +455,7 @@ int mifx_gbdt_grow_fixed_ex(const uint16_t* bins, long n, int f, const int* nbin
     for (QNode& nd : level) {
       MifxGbSplit s = mifx_gb_no_split();
       if (nd.depth < max_depth && nd.end - nd.begin >= 2) s = best_split(nd);
+      if (node_cover) node_cover[nd.id] = mifx_gb_dequant(nd.h, eh);
       if (mifx_gb_is_leaf(s)) {
         value[nd.id] = mifx_gb_leaf_value(nd.g, nd.h, eg, eh, prm);
         for (int k = nd.begin; k < nd.end; ++k) leaf_of_row[rows[k]] = nd.id;
@@ -443,6 +471,7 @@ int mifx_gbdt_grow_fixed_ex(const uint16_t* bins, long n, int f, const int* nbin
                             rows.begin());
       const int li = new_node(), ri = new_node();
       if (li < 0 || ri < 0) return -1;
+      if (node_gain) node_gain[nd.id] = s.gain;
       feature[nd.id] = s.feature;
       split_bin[nd.id] = s.bin;
       default_left[nd.id] = (uint8_t)s.default_left;
@@ -469,6 +498,16 @@ int mifx_gbdt_grow_fixed_ex(const uint16_t* bins, long n, int f, const int* nbin
     level = std::move(next);
   }
   return count;
+}
+
+int mifx_gbdt_grow_fixed_ex(const uint16_t* bins, long n, int f, const int* nbins, const float* g, const float* h,
+                            int max_depth, double min_child_weight, double lambda, double gamma, double eta,
+                            int threads, int max_nodes, int* feature, int* split_bin, uint8_t* default_left, int* left,
+                            int* right, double* value, int* leaf_of_row, const int* sample, long n_rows,
+                            const uint8_t* level_mask) {
+  return mifx_gbdt_grow_fixed_stats(bins, n, f, nbins, g, h, max_depth, min_child_weight, lambda, gamma, eta, threads,
+                                    max_nodes, feature, split_bin, default_left, left, right, value, leaf_of_row,
+                                    sample, n_rows, level_mask, nullptr, nullptr);
 }
 
 int mifx_gbdt_grow_fixed(const uint16_t* bins, long n, int f, const int* nbins, const float* g, const float* h,
@@ -503,6 +542,132 @@ int mifx_gbdt_predict(const double* X, long n, int f, int n_trees, const int* tr
         s += value[o + k];
       }
       out[i] = s;
+    }
+  });
+  return 0;
+}
+
+// ---- feature contributions (path-dependent TreeSHAP in path form, gbdt_shap.h)
+
+// The path table of a forest (trees concatenated as for mifx_gbdt_predict, tree_off [n_trees + 1]; cover: the nodes'
+// hessian sums). recs == null counts only. info [3] receives the records, the leaves and, on an error, the tree.
+// leaf_off [leaves + 1]: record offset of every leaf's header; tree_leaf [n_trees + 1]: first leaf of every tree.
+// Everything the walkers trust is checked here: -1 a tree that is not one (an empty tree, a child outside
+// (node, count), a node with two parents or none), -2 a feature outside [0, nfeat), -3 an inner node or a child of
+// one whose cover is not finite and > 0 (UNWIND divides by the ratios), -4 a path with more than MIFX_SHAP_MAX_PATH
+// distinct features, -5 an output too small or 2^31 records, -6 a NaN threshold.
+int mifx_gbdt_paths_build(int n_trees, const int* tree_off, const int* feature, const double* thr,
+                          const uint8_t* default_left, const int* left, const int* right, const double* value,
+                          const double* cover, int nfeat, MifxShapRec* recs, long rec_cap, int* leaf_off, long leaf_cap,
+                          int* tree_leaf, long* info) {
+  long n_recs = 0, n_leaves = 0;
+  info[0] = info[1] = 0;
+  info[2] = -1;
+  if (n_trees < 0 || nfeat < 1) return -1;
+  std::vector<int> parent, path;
+  auto good = [](double c) { return c > 0.0 && c <= 1.7976931348623157e308; };
+  for (int t = 0; t < n_trees; ++t) {
+    info[2] = t;
+    const int o = tree_off[t], c = tree_off[t + 1] - o;
+    if (o < 0 || c < 1) return -1;
+    const int *fe = feature + o, *le = left + o, *ri = right + o;
+    const double *th = thr + o, *cv = cover + o, *val = value + o;
+    const uint8_t* dl = default_left + o;
+    parent.assign(c, -1);
+    for (int k = 0; k < c; ++k) {
+      if (fe[k] < 0) continue;
+      if (fe[k] >= nfeat) return -2;
+      const int l = le[k], r = ri[k];
+      if (l <= k || l >= c || r <= k || r >= c || l == r || parent[l] >= 0 || parent[r] >= 0) return -1;
+      if (th[k] != th[k]) return -6;
+      if (!good(cv[k]) || !good(cv[l]) || !good(cv[r])) return -3;
+      parent[l] = parent[r] = k;
+    }
+    for (int k = 1; k < c; ++k)
+      if (parent[k] < 0) return -1;
+    if (recs) tree_leaf[t] = (int)n_leaves;
+    for (int k = 0; k < c; ++k) {
+      if (fe[k] >= 0) continue;
+      path.clear();
+      for (int a = k; a >= 0; a = parent[a]) path.push_back(a);  // parents have smaller indices: it ends at the root
+      MifxShapRec el[MIFX_SHAP_MAX_PATH];
+      int m = 0;
+      for (size_t s = path.size() - 1; s > 0; --s) {
+        const int p = path[s], ch = path[s - 1];
+        int e = 0;
+        while (e < m && el[e].i != fe[p]) ++e;
+        if (e == m) {
+          if (m == MIFX_SHAP_MAX_PATH) return -4;
+          el[m++] = MifxShapRec{1.0, -INFINITY, 0.0, fe[p], MIFX_SHAP_NAN_OK};
+        }
+        el[e].a = el[e].a * (cv[ch] / cv[p]);
+        if (ch == le[p]) {
+          el[e].c = (el[e].j & MIFX_SHAP_HAS_HI) && el[e].c < th[p] ? el[e].c : th[p];
+          el[e].j |= MIFX_SHAP_HAS_HI;
+          if (!dl[p]) el[e].j &= ~MIFX_SHAP_NAN_OK;
+        } else {
+          if (th[p] > el[e].b) el[e].b = th[p];
+          if (dl[p]) el[e].j &= ~MIFX_SHAP_NAN_OK;
+        }
+      }
+      if (n_recs + 1 + m >= (1L << 31)) return -5;
+      if (recs) {
+        if (n_recs + 1 + m > rec_cap || n_leaves + 1 > leaf_cap) return -5;
+        double pz = 1.0;
+        for (int e = 0; e < m; ++e) pz = pz * el[e].a;
+        leaf_off[n_leaves] = (int)n_recs;
+        recs[n_recs] = MifxShapRec{val[k], m ? val[k] * pz : val[k], 0.0, m, 0};
+        for (int e = 0; e < m; ++e) recs[n_recs + 1 + e] = el[e];
+      }
+      n_recs += 1 + m;
+      n_leaves += 1;
+    }
+  }
+  if (recs) {
+    tree_leaf[n_trees] = (int)n_leaves;
+    leaf_off[n_leaves] = (int)n_recs;
+  }
+  info[0] = n_recs;
+  info[1] = n_leaves;
+  info[2] = -1;
+  return 0;
+}
+
+// Contributions of the leaves in recs[0, n_recs) (a prefix of a path table that ends at a leaf boundary) for every
+// row of a row-major [n, f] table: out[i * stride + j] for j < f is feature j's contribution, out[i * stride + f]
+// the bias, base plus every leaf's share. One accumulator row per data row, the table walked in order, so the result
+// does not depend on the thread count. -1: a table that is not one for f features (checked before any row).
+int mifx_gbdt_contribs(const double* X, long n, int f, const MifxShapRec* recs, long n_recs, double base, double* out,
+                       long stride, int threads) {
+  if (n < 0 || f < 1 || n_recs < 0 || stride < f + 1) return -1;
+  for (long pos = 0; pos < n_recs;) {
+    const int m = recs[pos].i;
+    if (m < 0 || m > MIFX_SHAP_MAX_PATH || pos + 1 + m > n_recs) return -1;
+    for (int e = 0; e < m; ++e)
+      if (recs[pos + 1 + e].i < 0 || recs[pos + 1 + e].i >= f) return -1;
+    pos += 1 + m;
+  }
+  const int chunks = n > 64 ? (int)std::min<long>(std::max(1, threads), n) : 1;
+  parallel_for(chunks, chunks, [&](int c) {
+    const long lo = n * c / chunks, hi = n * (c + 1) / chunks;
+    for (long i = lo; i < hi; ++i) {
+      const double* xi = X + (size_t)i * f;
+      double* phi = out + (size_t)i * stride;
+      for (int j = 0; j < f; ++j) phi[j] = 0.0;
+      double bias = base;
+      for (long pos = 0; pos < n_recs;) {
+        const MifxShapRec& hd = recs[pos];
+        const int m = hd.i;
+        bias += hd.b;
+        if (m > 0) {
+          const MifxShapRec* e = recs + pos + 1;
+          unsigned obits = 0;
+          for (int k = 0; k < m; ++k) obits |= (unsigned)mifx_shap_passes(e[k], xi[e[k].i]) << k;
+          mifx_shap_leaf_m(m, e, obits, hd.a, [&](int j, double x) { phi[j] += x; });
+        }
+        pos += 1 + m;
+      }
+      phi[f] = bias;
     }
   });
   return 0;

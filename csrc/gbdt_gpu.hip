@@ -18,7 +18,8 @@
 //               (int64 g, int64 h, int32 rows) by LDS atomics, non-empty slots flushed with 64-bit global atomics
 //   k_split     one wave per (node, feature): lanes own runs of 4 bins, integer prefix scan across the wave,
 //               mifx_gb_scan per lane, lanes merged with ties to the lowest (bin, direction)
-//   k_decide    one workgroup: per node the features in order (1e-12 rule), leaf test, leaf value; then one thread
+//   k_decide    one workgroup: per node the features in order (1e-12 rule), leaf test, leaf value (and, when asked
+//               for, the node's gain and cover: mifx_gbdt_gpu_grow_stats); then one thread
 //               numbers the children in the host learner's order (breadth first, in the order of their parents)
 //   k_partition per row position: a leaf's rows get leaf_of_row and margin += value; a split's rows move to their
 //               child's range through wave-aggregated atomic cursors. The order of rows INSIDE a child is therefore
@@ -71,6 +72,7 @@ struct TreeOut {
   uint8_t* default_left;
   int *left, *right;
   double* value;
+  double *gain, *cover;  // (nullable) node statistics: the split's gain (0.0 at a leaf), the node's hessian sum
 };
 
 struct Ws {
@@ -491,6 +493,11 @@ __global__ __launch_bounds__(kThreads) void k_decide(Level lv, Level nx, int* lc
     // the root do not even load the range)
     const bool empty = d == 0 && lv.end[k] <= lv.begin[k];
     dec.val[k] = leaf && !empty ? mifx_gb_leaf_value(lv.qg[k], lv.qh[k], exps[0], exps[1], prm) : 0.0;
+    const int nid = lv.id[k];
+    if (t.gain && nid >= 0 && nid < cap) {  // what the host twin records (mifx_gbdt_grow_fixed_stats)
+      t.gain[nid] = leaf ? 0.0 : best.gain;
+      t.cover[nid] = mifx_gb_dequant(lv.qh[k], exps[1]);
+    }
     cur[2 * k] = 0;
     cur[2 * k + 1] = 0;
   }
@@ -504,6 +511,7 @@ __global__ __launch_bounds__(kThreads) void k_decide(Level lv, Level nx, int* lc
     if (dec.feat[k] >= 0 && base + 2 * s + 1 >= cap) {  // cannot happen with cap = 2^(max_depth + 1)
       dec.feat[k] = -1;
       dec.val[k] = mifx_gb_leaf_value(lv.qg[k], lv.qh[k], exps[0], exps[1], prm);
+      if (t.gain) t.gain[id] = 0.0;
     }
     const bool leaf = dec.feat[k] < 0;
     const int li = leaf ? -1 : base + 2 * s, ri = leaf ? -1 : li + 1;
@@ -666,13 +674,16 @@ int mifx_gbdt_gpu_grad_softmax(const double* margin, const double* y, const floa
 // level_mask (device, nullable): [max_depth, f] uint8, the features each level may split on. With sampling every
 // row's margin still receives the tree's output; margin_route 0: the partition updates the sampled rows and a walk of
 // the tree covers the others, 1: one walk over all rows. Both add the same double to the same margin.
-int mifx_gbdt_gpu_grow_ex(const uint16_t* bins, long n, int f, const int* nbins, const int* hoff, int hsize,
-                          const float* g, const float* h, int max_depth, double min_child_weight, double lambda,
-                          double gamma, double eta, void* ws, long long ws_bytes, int* feature, int* split_bin,
-                          uint8_t* default_left, int* left, int* right, double* value, int* node_count,
-                          int* leaf_of_row, double* margin, int rows_per_wg, int feat_tile, unsigned long long seed,
-                          unsigned long long round, unsigned long long thr, const uint8_t* level_mask,
-                          int margin_route, hipStream_t stream) {
+// node_gain / node_cover (device, cap doubles each, both or neither): per node the gain of its split (0.0 at a leaf)
+// and its hessian sum over the rows the tree was grown on, the values of the host's mifx_gbdt_grow_fixed_stats.
+int mifx_gbdt_gpu_grow_stats(const uint16_t* bins, long n, int f, const int* nbins, const int* hoff, int hsize,
+                             const float* g, const float* h, int max_depth, double min_child_weight, double lambda,
+                             double gamma, double eta, void* ws, long long ws_bytes, int* feature, int* split_bin,
+                             uint8_t* default_left, int* left, int* right, double* value, int* node_count,
+                             int* leaf_of_row, double* margin, int rows_per_wg, int feat_tile, unsigned long long seed,
+                             unsigned long long round, unsigned long long thr, const uint8_t* level_mask,
+                             int margin_route, double* node_gain, double* node_cover, hipStream_t stream) {
+  if ((node_gain == nullptr) != (node_cover == nullptr)) return -1;
   const long long need = mifx_gbdt_gpu_ws_bytes(n, f, max_depth, hsize);
   if (need < 0 || ws_bytes < need || rows_per_wg < 1 || feat_tile < 1 || feat_tile > kMaxFeatTile) return -1;
   if (margin_route < 0 || margin_route > 1) return -1;
@@ -680,7 +691,7 @@ int mifx_gbdt_gpu_grow_ex(const uint16_t* bins, long n, int f, const int* nbins,
   double* part_margin = sampled && margin_route == 1 ? nullptr : margin;
   Ws w = carve(ws, n, f, max_depth, hsize);
   const MifxGbParams prm{lambda, gamma, min_child_weight, eta};
-  const TreeOut t{feature, split_bin, default_left, left, right, value};
+  const TreeOut t{feature, split_bin, default_left, left, right, value, node_gain, node_cover};
   const int cap = 1 << (max_depth + 1);
   k_init<<<1, 64, 0, stream>>>(w);
   if (sampled) {
@@ -725,6 +736,19 @@ int mifx_gbdt_gpu_grow_ex(const uint16_t* bins, long n, int f, const int* nbins,
   return (int)hipMemcpyAsync(node_count, w.ncount, sizeof(int), hipMemcpyDeviceToDevice, stream);
 }
 
+int mifx_gbdt_gpu_grow_ex(const uint16_t* bins, long n, int f, const int* nbins, const int* hoff, int hsize,
+                          const float* g, const float* h, int max_depth, double min_child_weight, double lambda,
+                          double gamma, double eta, void* ws, long long ws_bytes, int* feature, int* split_bin,
+                          uint8_t* default_left, int* left, int* right, double* value, int* node_count,
+                          int* leaf_of_row, double* margin, int rows_per_wg, int feat_tile, unsigned long long seed,
+                          unsigned long long round, unsigned long long thr, const uint8_t* level_mask,
+                          int margin_route, hipStream_t stream) {
+  return mifx_gbdt_gpu_grow_stats(bins, n, f, nbins, hoff, hsize, g, h, max_depth, min_child_weight, lambda, gamma, eta,
+                                  ws, ws_bytes, feature, split_bin, default_left, left, right, value, node_count,
+                                  leaf_of_row, margin, rows_per_wg, feat_tile, seed, round, thr, level_mask,
+                                  margin_route, nullptr, nullptr, stream);
+}
+
 int mifx_gbdt_gpu_grow(const uint16_t* bins, long n, int f, const int* nbins, const int* hoff, int hsize,
                        const float* g, const float* h, int max_depth, double min_child_weight, double lambda,
                        double gamma, double eta, void* ws, long long ws_bytes, int* feature, int* split_bin,
@@ -741,7 +765,7 @@ int mifx_gbdt_gpu_apply(const uint16_t* bins, long m, int f, const int* nbins, c
                         const double* value, int max_depth, double* margin, hipStream_t stream) {
   if (m < 1 || f < 1 || max_depth < 0 || max_depth > kMaxDepth) return -1;
   const TreeOut t{const_cast<int*>(feature), const_cast<int*>(split_bin), const_cast<uint8_t*>(default_left),
-                  const_cast<int*>(left), const_cast<int*>(right), const_cast<double*>(value)};
+                  const_cast<int*>(left), const_cast<int*>(right), const_cast<double*>(value), nullptr, nullptr};
   k_apply<<<(unsigned)((m + kThreads - 1) / kThreads), kThreads, 0, stream>>>(bins, m, f, nbins, t,
                                                                                1 << (max_depth + 1), max_depth, margin,
                                                                                nullptr);

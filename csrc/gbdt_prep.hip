@@ -19,8 +19,12 @@
 //            memory). One double per row, additions only, in the host's order.
 //            k_predict_multi: the same walk for a multi-class forest (tree t belongs to class t % K), one launch for
 //            all K classes, one double per (class, row), per class the host's order.
+//   contribs k_contribs: per-row feature contributions (path-dependent TreeSHAP) from the path table of gbdt_shap.h,
+//            one row per thread, the table staged through LDS in chunks of whole leaves; mifx_gbdt_contribs bit for bit.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "gbdt_shap.h"
 
 namespace {
 
@@ -305,9 +309,121 @@ void launch_predict_multi(const T* X, long n, int f, const PackedNode* nd, const
                                                                   nodes_per_chunk, out);
 }
 
+// ---- contributions (path-dependent TreeSHAP in path form; gbdt_shap.h holds the one copy of the arithmetic)
+//
+// One row per thread. The path table is staged through LDS in chunks of whole leaves (a leaf is at most
+// 1 + MIFX_SHAP_MAX_PATH records, so any chunk of that many records makes progress); every lane of the workgroup is at
+// the same leaf at the same time, so m, every z and every feature index are uniform (LDS broadcasts, scalar branch on
+// m) and only the o bits and the permutation weights differ per lane. The weights are registers: mifx_shap_leaf<M>
+// indexes them by constants only. A row's f contributions accumulate in the thread's own slots, in the table's order:
+//   ACC_LDS   slot j of thread t is lds[j * blockDim.x + t] (consecutive lanes, consecutive words); stored once. The
+//             workgroup is 256, 128 or 64 threads, the largest whose f sums per thread fit beside the chunk
+//   otherwise the thread's own output row (plain loads and stores: no other thread touches it)
+// The same thread adds the same doubles in the same order either way, and in the order of the host's
+// mifx_gbdt_contribs: the three agree bit for bit whatever the chunk size or the grid. The bias is one register.
+constexpr int kContribThreads = 256;
+constexpr int kMinContribChunk = 1 + MIFX_SHAP_MAX_PATH;
+constexpr int kMaxContribLds = 65536;  // chunk records and, on the LDS route, the accumulators
+
+template <class T, bool ACC_LDS>
+__global__ __launch_bounds__(kContribThreads) void k_contribs(const T* X, long n, int f, const MifxShapRec* recs,
+                                                              const int* leaf_off, int n_leaves, double base,
+                                                              int chunk, double* out, long stride) {
+  extern __shared__ double lds_raw[];
+  MifxShapRec* lds = reinterpret_cast<MifxShapRec*>(lds_raw);
+  double* acc = lds_raw + (size_t)chunk * (sizeof(MifxShapRec) / sizeof(double)) + threadIdx.x;
+  const int nt = blockDim.x;
+  const long i = (long)blockIdx.x * nt + threadIdx.x;
+  const bool live = i < n;  // a thread past the table only helps staging: it never touches out
+  const T* xi = X + (size_t)(live ? i : 0) * f;
+  double* phi = out + (size_t)(live ? i : 0) * stride;
+  if (ACC_LDS) {
+    for (int j = 0; j < f; ++j) acc[(size_t)j * nt] = 0.0;
+  } else if (live) {
+    for (int j = 0; j < f; ++j) phi[j] = 0.0;
+  }
+  double bias = base;
+  int l0 = 0;
+  while (l0 < n_leaves) {  // every quantity that steers this loop is uniform over the workgroup
+    const int o0 = leaf_off[l0];
+    int lo = l0 + 1, hi = n_leaves;  // the last leaf boundary within a chunk of o0; l0 + 1 always is (validated)
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (leaf_off[mid] - o0 <= chunk) lo = mid; else hi = mid - 1;
+    }
+    const int total = min(leaf_off[lo] - o0, chunk);
+    __syncthreads();  // the previous chunk has been walked
+    for (int q = threadIdx.x; q < total; q += nt) lds[q] = recs[o0 + q];
+    __syncthreads();
+    if (live) {
+      int pos = 0;
+      while (pos < total) {
+        const int m = lds[pos].i;
+        if (m < 0 || m > MIFX_SHAP_MAX_PATH || pos + 1 + m > total) break;  // refused on the host; never read past
+        bias += lds[pos].b;
+        if (m > 0) {
+          const MifxShapRec* e = lds + pos + 1;
+          unsigned obits = 0;
+          for (int k = 0; k < m; ++k) {
+            const int j = min(max(e[k].i, 0), f - 1);
+            obits |= (unsigned)mifx_shap_passes(e[k], (double)xi[j]) << k;
+          }
+          const double v = lds[pos].a;
+          if (ACC_LDS)
+            mifx_shap_leaf_m(m, e, obits, v, [&](int j, double x) {
+              if ((unsigned)j < (unsigned)f) acc[(size_t)j * nt] += x;
+            });
+          else
+            mifx_shap_leaf_m(m, e, obits, v, [&](int j, double x) {
+              if ((unsigned)j < (unsigned)f) phi[j] += x;
+            });
+        }
+        pos += 1 + m;
+      }
+    }
+    l0 = lo;
+  }
+  if (!live) return;
+  if (ACC_LDS)
+    for (int j = 0; j < f; ++j) phi[j] = acc[(size_t)j * nt];
+  phi[f] = bias;
+}
+
 }  // namespace
 
 extern "C" {
+
+int mifx_gbdt_prep_contrib_rec_bytes() { return (int)sizeof(MifxShapRec); }
+int mifx_gbdt_prep_contrib_min_chunk() { return kMinContribChunk; }
+int mifx_gbdt_prep_contrib_max_lds() { return kMaxContribLds; }
+int mifx_gbdt_prep_contrib_threads() { return kContribThreads; }
+
+// Contributions of the first n_leaves leaves of a path table (mifx_gbdt_paths_build, validated on the host) for a
+// row-major [n, f] table: out[i * stride + j], j < f, is feature j's contribution and out[i * stride + f] the bias
+// (base plus every leaf's share), the bits of the host's mifx_gbdt_contribs. leaf_off [>= n_leaves + 1] on the device.
+// chunk: records staged in LDS at a time; threads: 64, 128 or 256 per workgroup; acc_lds: 1 accumulates in LDS (needs
+// chunk * 32 + f * threads * 8 bytes <= mifx_gbdt_prep_contrib_max_lds()), 0 in the output rows. None of the three
+// changes a bit of the result.
+int mifx_gbdt_prep_contribs(const void* X, int is_f64, long n, int f, const void* recs, const int* leaf_off,
+                            int n_leaves, double base, int chunk, int threads, int acc_lds, double* out, long stride,
+                            hipStream_t stream) {
+  if (n < 1 || n >= (1L << 31) || f < 1 || n_leaves < 0 || chunk < kMinContribChunk || stride < f + 1 ||
+      acc_lds < 0 || acc_lds > 1 || (threads != 64 && threads != 128 && threads != kContribThreads))
+    return -1;
+  const size_t lds = (size_t)chunk * sizeof(MifxShapRec) + (acc_lds ? (size_t)f * threads * sizeof(double) : 0);
+  if (lds > (size_t)kMaxContribLds) return -1;
+  const unsigned grid = (unsigned)((n + threads - 1) / threads);
+  const MifxShapRec* r = static_cast<const MifxShapRec*>(recs);
+#define MIFX_CONTRIBS(T, A) \
+  k_contribs<T, A><<<grid, threads, lds, stream>>>(static_cast<const T*>(X), n, f, r, leaf_off, n_leaves, \
+                                                           base, chunk, out, stride)
+  if (is_f64 && acc_lds) MIFX_CONTRIBS(double, true);
+  else if (is_f64) MIFX_CONTRIBS(double, false);
+  else if (acc_lds) MIFX_CONTRIBS(float, true);
+  else MIFX_CONTRIBS(float, false);
+#undef MIFX_CONTRIBS
+  return (int)hipGetLastError();
+}
 
 int mifx_gbdt_prep_max_bins() { return kMaxBins; }
 int mifx_gbdt_prep_max_feat_tile() { return kMaxFeatTile; }

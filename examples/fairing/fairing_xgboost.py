@@ -36,6 +36,13 @@ def run_training_and_eval(device="cpu", subsample=1.0, colsample_bytree=1.0, col
     logging.info("Best RMSE on eval: %.2f with %d rounds", model.best_score, model.best_iteration + 1)
     mae = mean_absolute_error(model.predict(vx), vy)
     print(f"mean_absolute_error={mae:.2f}")
+    # which columns drive the price: the model's importances, and why the first eval row got its prediction
+    top = np.argsort(-model.feature_importances_)[:5]
+    print("top importances (gain): " + ", ".join(f"f{j}={model.feature_importances_[j]:.3f}" for j in top))
+    contribs = model.predict_contribs(vx[:1])[0]  # [features + 1]: one contribution per column, then the bias
+    lead = np.argsort(-np.abs(contribs[:-1]))[:5]
+    print(f"row 0: prediction {contribs.sum():.0f} = bias {contribs[-1]:.0f} " +
+          " ".join(f"{contribs[j]:+.0f}[f{j}]" for j in lead) + " + the other columns")
     return mae
 
 

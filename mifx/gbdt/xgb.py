@@ -38,7 +38,16 @@ GPU model equals the host twin bit for bit. A round's tree is grown on exactly t
 only them (quantisation exponents, the two-row leaf rule and row counts included); every row's margin then receives
 the tree's output. Weights are float32 and multiply the float32 gradient pair; the intercept is the weighted mean (or
 its log-odds). The eval metric stays unweighted (`sample_weight_eval_set` and `colsample_bynode` are not
-implemented). With the defaults nothing is drawn and no weight is applied: the models are the unsampled ones."""
+implemented). With the defaults nothing is drawn and no weight is applied: the models are the unsampled ones.
+
+What the model used: every learner records each node's `gain` (the double it maximised,
+0.5 * (score_L + score_R - score_parent) - gamma, 0.0 at a leaf) and `cover` (the node's hessian sum, over the sampled
+rows under `subsample`), kept beside the 6-tuples of `_trees` as `_node_stats[t] = (gain, cover)` and equal bit for bit
+between the device and its host twin. XGBoost's `loss_chg` is 2 * (gain + gamma) of ours, so at gamma = 0 the normalised
+importances are the same quantity. `get_score(importance_type)` and `feature_importances_` (constructor argument
+`importance_type`, default "gain") are XGBoost's; `predict_contribs(X)` is its `pred_contribs`: exact path-dependent
+TreeSHAP in margin space, on the host (csrc/gbdt.cpp) for host input and on the GPU (csrc/gbdt_prep.hip) for a device
+tensor, the same bits. `pred_interactions` and approximate (Saabas) contributions are not implemented."""
 from __future__ import annotations
 
 import ctypes
@@ -72,6 +81,8 @@ def _lib():
     lib.mifx_gbdt_quant_exp.argtypes = [ctypes.c_double, ctypes.c_long]
     lib.mifx_gbdt_grow_ex.argtypes = lib.mifx_gbdt_grow.argtypes + [_I, ctypes.c_long, _U8]
     lib.mifx_gbdt_grow_fixed_ex.argtypes = lib.mifx_gbdt_grow_ex.argtypes
+    lib.mifx_gbdt_grow_stats.argtypes = lib.mifx_gbdt_grow_ex.argtypes + [_D, _D]
+    lib.mifx_gbdt_grow_fixed_stats.argtypes = lib.mifx_gbdt_grow_stats.argtypes
     u64 = ctypes.c_uint64
     lib.mifx_gbdt_sample_rows.argtypes = [u64, u64, ctypes.c_double, ctypes.c_long, _U8]
     lib.mifx_gbdt_sample_rows.restype = ctypes.c_long
@@ -80,7 +91,8 @@ def _lib():
                                          _U8]
     for f in (lib.mifx_gbdt_cuts, lib.mifx_gbdt_bin, lib.mifx_gbdt_grow, lib.mifx_gbdt_predict,
               lib.mifx_gbdt_grow_fixed, lib.mifx_gbdt_quant_exp, lib.mifx_gbdt_grow_ex, lib.mifx_gbdt_grow_fixed_ex,
-              lib.mifx_gbdt_sample_features, lib.mifx_gbdt_level_mask):
+              lib.mifx_gbdt_sample_features, lib.mifx_gbdt_level_mask, lib.mifx_gbdt_grow_stats,
+              lib.mifx_gbdt_grow_fixed_stats):
         f.restype = ctypes.c_int
     return lib
 
@@ -144,7 +156,8 @@ class _Base:
                  min_child_weight: float = 1.0, reg_lambda: float = 1.0, gamma: float = 0.0, max_bins: int = 256,
                  base_score: float | None = None, n_jobs: int | None = None, random_state: int = 0,
                  verbosity: int = 0, device: str | None = None, fixed_point: bool | None = None,
-                 subsample: float = 1.0, colsample_bytree: float = 1.0, colsample_bylevel: float = 1.0):
+                 subsample: float = 1.0, colsample_bytree: float = 1.0, colsample_bylevel: float = 1.0,
+                 importance_type: str = "gain"):
         self.n_estimators, self.learning_rate, self.max_depth = n_estimators, learning_rate, max_depth
         self.min_child_weight, self.reg_lambda, self.gamma, self.max_bins = min_child_weight, reg_lambda, gamma, max_bins
         self.base_score, self.n_jobs = base_score, n_jobs
@@ -153,6 +166,8 @@ class _Base:
         self._check_rates()
         self.best_iteration, self.best_score, self.evals_result_ = None, None, {}
         self._trees: list[tuple] = []
+        self._node_stats: list[tuple] = []  # per tree (gain, cover), parallel to _trees
+        self.importance_type = importance_type
         self.device, self.fixed_point = device, fixed_point
         if _parse_device(device) is not None and fixed_point is not None and not fixed_point:
             raise ValueError("device='gpu' trains in fixed point only (fixed_point=False is the host's double learner)")
@@ -210,6 +225,8 @@ class _Base:
     def __getstate__(self):
         state = self.__dict__.copy()
         state.pop("_dev_forest", None)  # the device copy of the trees: rebuilt on the next device predict
+        state.pop("_paths", None)       # the path tables of predict_contribs and their device copies: rebuilt too
+        state.pop("_dev_paths", None)
         return state
 
     # ---- loss (overridden by the classifier)
@@ -273,12 +290,17 @@ class _Base:
     def _grow(self, bins, nbins, g, h, leaf_of_row, rows=None, level_mask=None):
         """One tree. rows (ascending int32 ids, None = all): the tree is grown on these rows only and leaf_of_row is
         -1 elsewhere; level_mask (uint8 [max_depth, f], None = all): the features each level may split on."""
+        return self._grow_stats(bins, nbins, g, h, leaf_of_row, rows, level_mask)[0]
+
+    def _grow_stats(self, bins, nbins, g, h, leaf_of_row, rows=None, level_mask=None):
+        """(_grow's tree, (gain, cover)): the tree and its nodes' statistics (float64 [nodes] each)."""
         n = bins.shape[1]
         cap = 2 ** (self.max_depth + 1)
         fe, sb, left, right = (np.empty(cap, np.int32) for _ in range(4))
         dl = np.empty(cap, np.uint8)
         val = np.empty(cap, np.float64)
-        grow = _lib().mifx_gbdt_grow_fixed_ex if self._fixed() else _lib().mifx_gbdt_grow_ex
+        gain, cover = np.empty(cap, np.float64), np.empty(cap, np.float64)
+        grow = _lib().mifx_gbdt_grow_fixed_stats if self._fixed() else _lib().mifx_gbdt_grow_stats
         if rows is not None:
             rows = np.ascontiguousarray(rows, np.int32)
         if level_mask is not None:
@@ -288,14 +310,15 @@ class _Base:
                    float(self.gamma), float(self.learning_rate), self._nthreads(), cap, _p(fe, _I),
                    _p(sb, _I), _p(dl, _U8), _p(left, _I), _p(right, _I), _p(val, _D),
                    _p(leaf_of_row, _I), None if rows is None else _p(rows, _I), 0 if rows is None else len(rows),
-                   None if level_mask is None else _p(level_mask, _U8))
+                   None if level_mask is None else _p(level_mask, _U8), _p(gain, _D), _p(cover, _D))
         if cnt < 0:
             raise RuntimeError("tree exceeded its node capacity")
         thr = np.zeros(cnt, np.float64)
         for k in range(cnt):  # the split's cut value: bin <= b  <=>  x < cuts[b]
             if fe[k] >= 0:
                 thr[k] = self._cuts[fe[k]][sb[k]]
-        return fe[:cnt].copy(), thr, dl[:cnt].copy(), left[:cnt].copy(), right[:cnt].copy(), val[:cnt].copy()
+        return ((fe[:cnt].copy(), thr, dl[:cnt].copy(), left[:cnt].copy(), right[:cnt].copy(), val[:cnt].copy()),
+                (gain[:cnt].copy(), cover[:cnt].copy()))
 
     def fit(self, X, y, eval_set=None, early_stopping_rounds: int | None = None, verbose: bool = False, *,
             sample_weight=None):
@@ -304,7 +327,7 @@ class _Base:
         if it is not there already, and its float64 form (8 n f bytes), the bins (2 n f bytes) and one column's sort
         scratch must fit on the device. Without a device, data on a GPU is refused. `sample_weight` (keyword only):
         one non-negative finite weight per row, used as float32; the eval metric stays unweighted."""
-        self._dev_forest = None
+        self._dev_forest = self._paths = self._dev_paths = None
         gpu = self._gpu_index()
         self._check_rates()
         self._check_data_device(X, y, sample_weight, *(eval_set[-1] if eval_set else ()))
@@ -333,15 +356,16 @@ class _Base:
             ey = self._check_y(np.asarray(ey).reshape(-1))
             ev_margin = np.full((K, len(ey)), self._base_margin)
             ev = (ex, ey, ev_margin)
-        self._trees = []
+        self._trees, self._node_stats = [], []
         best, best_it, since, hist = None, 0, 0, []
         for it in range(int(self.n_estimators)):
             g, h = self._weighted_grad_hess(margin if K > 1 else margin[0], y, w)
             g, h = g.reshape(K, -1), h.reshape(K, -1)
             for k in range(K):
                 rows, mask = self._round_draws(it * K + k, len(y), self._nfeat)
-                tree = self._grow(bins, nbins, g[k], h[k], leaf_of_row, rows, mask)
+                tree, stats = self._grow_stats(bins, nbins, g[k], h[k], leaf_of_row, rows, mask)
                 self._trees.append(tree)
+                self._node_stats.append(stats)
                 if rows is None:
                     margin[k] += tree[5][leaf_of_row]
                 else:  # rows outside the sample have no leaf_of_row: every row walks the tree (the same leaf values)
@@ -411,6 +435,7 @@ class _Base:
             margin = torch.full((K, len(y)), self._base_margin, dtype=torch.float64, device=dev)
             g, h = (torch.empty((K, len(y)), dtype=torch.float32, device=dev) for _ in range(2))
             trees = bst.new_trees(max(1, rounds * K))
+            stats = bst.new_stats(max(1, rounds * K))
             ev = None
             if eval_set:
                 ex, ey = eval_set[-1]
@@ -430,7 +455,8 @@ class _Base:
                     tree = tuple(t[it * K + k] for t in trees)
                     bst.grow(g[k], h[k], tree, self.min_child_weight, self.reg_lambda, self.gamma, self.learning_rate,
                              margin[k], subsample=sub, seed=self._seed(), round=it * K + k,
-                             level_mask=None if masks is None else masks[it * K + k])
+                             level_mask=None if masks is None else masks[it * K + k],
+                             stats=tuple(s[it * K + k] for s in stats))
                     if ev is not None:
                         bst.apply(ev[0], tree, ev[2][k])
                 done = (it + 1) * K
@@ -447,7 +473,8 @@ class _Base:
                         if early_stopping_rounds and since >= early_stopping_rounds:
                             break
             fe, sb, dl, le, ri, val, cnt = (t[:done].cpu().numpy() for t in trees)
-        self._trees = []
+            gain, cover = (s[:done].cpu().numpy() for s in stats)
+        self._trees, self._node_stats = [], []
         for t in range(done):
             c = int(cnt[t])
             thr = np.zeros(c, np.float64)
@@ -456,6 +483,7 @@ class _Base:
                     thr[k] = self._cuts[fe[t, k]][sb[t, k]]
             self._trees.append((fe[t, :c].copy(), thr, dl[t, :c].copy(), le[t, :c].copy(), ri[t, :c].copy(),
                                 val[t, :c].copy()))
+            self._node_stats.append((gain[t, :c].copy(), cover[t, :c].copy()))
         self.evals_result_ = {"validation_0": {self._metric_name(): hist}} if ev is not None else {}
         self.best_score, self.best_iteration = (best, best_it) if ev is not None and early_stopping_rounds else \
             (None, None)
@@ -508,6 +536,105 @@ class _Base:
         if num_class > 1:
             return P.predict_multi(cache[X.device.index], Xd, self._base_margin, num_class, n_trees)
         return P.predict(cache[X.device.index], Xd, self._base_margin, n_trees)
+
+    # ---- what the model used: importances and per-row contributions
+    _IMPORTANCE_TYPES = ("weight", "gain", "cover", "total_gain", "total_cover")
+
+    def _stats(self):
+        """_node_stats, checked against _trees; a model without them (pickled before they were recorded, or with
+        hand-assigned trees) still predicts and is refused here only."""
+        stats = getattr(self, "_node_stats", None)
+        if stats is None or len(stats) != len(self._trees) or \
+                any(len(g) != len(t[0]) or len(c) != len(t[0]) for t, (g, c) in zip(self._trees, stats)):
+            raise ValueError("this model holds no node statistics (gain and cover) for its trees: it was fitted before "
+                             "they were recorded, or its trees were assigned by hand; refit it")
+        return stats
+
+    def _importance(self, importance_type: str) -> np.ndarray:
+        """float64 [n_features] of one importance type over all trees (all classes' trees pooled); 0 where a feature
+        never splits."""
+        if importance_type not in self._IMPORTANCE_TYPES:
+            raise ValueError(f"importance_type must be one of {self._IMPORTANCE_TYPES}, got {importance_type!r}")
+        stats = self._stats()
+        weight, gain, cover = (np.zeros(self._nfeat, np.float64) for _ in range(3))
+        for (fe, *_), (g, c) in zip(self._trees, stats):
+            inner = np.flatnonzero(np.asarray(fe) >= 0)
+            np.add.at(weight, fe[inner], 1.0)
+            np.add.at(gain, fe[inner], g[inner])
+            np.add.at(cover, fe[inner], c[inner])
+        if importance_type == "weight":
+            return weight
+        total = gain if importance_type.endswith("gain") else cover
+        return total if importance_type.startswith("total_") else total / np.maximum(weight, 1.0)
+
+    def get_score(self, importance_type: str = "weight") -> dict:
+        """{"f<j>": value} for the features that split at least once, as XGBoost's Booster.get_score: "weight" the
+        number of splits, "gain" / "cover" the average gain / cover of the feature's splits, "total_gain" /
+        "total_cover" their sums. Our gain is the quantity the learner maximised, so XGBoost's loss_chg is
+        2 * (gain + gamma) of it: with gamma = 0 the normalised importances are the same quantity."""
+        score = self._importance(importance_type)
+        used = self._importance("weight") > 0
+        return {f"f{j}": float(score[j]) for j in np.flatnonzero(used)}
+
+    @property
+    def feature_importances_(self) -> np.ndarray:
+        """float32 [n_features]: get_score(self.importance_type) normalised to sum 1 (all zero if no tree splits)."""
+        score = self._importance(getattr(self, "importance_type", "gain"))
+        total = score.sum()
+        return (score / total if total > 0 else np.zeros_like(score)).astype(np.float32)
+
+    def _path_tables(self, limit: int):
+        """One path table (mifx/gbdt/shap.py) per margin row over the trees that predict uses, built once per model
+        and tree limit. Raises ValueError for trees that contributions cannot be computed for (a zero-cover child)."""
+        from . import shap
+
+        cache = getattr(self, "_paths", None)
+        if cache is None or cache[0] != limit:
+            stats, K = self._stats(), self._num_class()
+            cache = self._paths = (limit, [shap.PathTable(self._trees[k:limit:K], [s[1] for s in stats[k:limit:K]],
+                                                           self._nfeat) for k in range(K)])
+            self._dev_paths = None
+        return cache[1]
+
+    def predict_contribs(self, X, _recs_per_chunk: int | None = None, _route: str | None = None):
+        """Per-row feature contributions in margin space (XGBoost's pred_contribs: path-dependent TreeSHAP):
+        [n, f + 1], or [n, K, f + 1] for a K-class model; column j < f is feature j's Shapley value in the game whose
+        value for a feature set S follows the row at nodes that split on S and averages both children by their cover
+        elsewhere, column f the bias (the intercept plus every used tree's cover-weighted mean leaf); a row sums to
+        its margin. The trees are predict's (best_iteration under early stopping; class k's are k, k + K, ...).
+
+        numpy or CPU input gives a numpy array from the host function (threads: n_jobs, the same bits for any count);
+        a tensor on a GPU gives a tensor there from the device kernel with the same bits, for any model. float32
+        tables are widened exactly. The private arguments are the kernel's launch geometry. Raises ValueError for a
+        model without node statistics and for a used tree with a zero-cover child (min_child_weight = 0 allows one)."""
+        from . import shap
+
+        K, limit, f = self._num_class(), self._tree_limit(), self._nfeat
+        X = X if _is_tensor(X) else np.asarray(X)
+        if X.ndim != 2 or X.shape[1] != f:
+            raise ValueError(f"expected [n, {f}] features")
+        tables = self._path_tables(limit)
+        counts = [len(range(k, limit, K)) for k in range(K)]
+        if _on_gpu(X):
+            from ..ops import gbdt_prep as P
+
+            torch = sys.modules["torch"]
+            cache = getattr(self, "_dev_paths", None)
+            if cache is None:
+                cache = self._dev_paths = {}
+            if X.device.index not in cache:  # the tables, uploaded once per model and device (fit resets them)
+                cache[X.device.index] = [P.DevicePaths(t, X.device) for t in tables]
+            Xd = P.as_device_matrix(X, X.device)
+            out = torch.empty((len(Xd), K, f + 1), dtype=torch.float64, device=X.device)
+            for k in range(K if len(Xd) else 0):  # one launch per class over the class's own table
+                P.contribs(cache[X.device.index][k], Xd, self._base_margin, out[:, k, :], counts[k],
+                           _recs_per_chunk, _route)
+            return out[:, 0, :] if K == 1 else out
+        X = np.ascontiguousarray(_host(X), dtype=np.float64)
+        out = np.empty((len(X), K, f + 1), np.float64)
+        for k in range(K):
+            shap.contribs(tables[k], X, counts[k], self._base_margin, out[:, k, :], self._nthreads())
+        return out[:, 0, :] if K == 1 else out
 
 
 class XGBRegressor(_Base):

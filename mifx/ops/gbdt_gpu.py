@@ -45,6 +45,9 @@ def _fns():
         "grow_ex": sig(lib, "mifx_gbdt_gpu_grow_ex", [VP, LONG, I32, VP, VP, I32, VP, VP, I32, F64, F64, F64, F64, VP,
                                                        I64, VP, VP, VP, VP, VP, VP, VP, VP, VP, I32, I32, U64, U64,
                                                        U64, VP, I32, VP]),
+        "grow_stats": sig(lib, "mifx_gbdt_gpu_grow_stats", [VP, LONG, I32, VP, VP, I32, VP, VP, I32, F64, F64, F64, F64,
+                                                             VP, I64, VP, VP, VP, VP, VP, VP, VP, VP, VP, I32, I32, U64,
+                                                             U64, U64, VP, I32, VP, VP, VP]),
         "apply": sig(lib, "mifx_gbdt_gpu_apply", [VP, LONG, I32, VP, VP, VP, VP, VP, VP, VP, I32, VP, VP]),
         "grad_softmax": sig(lib, "mifx_gbdt_gpu_grad_softmax", [VP, VP, VP, LONG, I32, VP, VP, VP]),
     }
@@ -157,10 +160,14 @@ class Booster:
         return (z(torch.int32), z(torch.int32), z(torch.uint8), z(torch.int32), z(torch.int32), z(torch.float64),
                 torch.zeros(count, dtype=torch.int32, device=self.dev))
 
+    def new_stats(self, count: int):
+        """Node statistics for `count` trees: (gain, cover), float64 [count, cap] each (Booster.grow's `stats=`)."""
+        return tuple(torch.zeros((count, self.cap), dtype=torch.float64, device=self.dev) for _ in range(2))
+
     def grow(self, g: torch.Tensor, h: torch.Tensor, tree, min_child_weight: float, reg_lambda: float, gamma: float,
              eta: float, margin: torch.Tensor | None = None, _rows_per_wg: int | None = None,
              _feat_tile: int | None = None, subsample: float = 1.0, seed: int = 0, round: int = 0,
-             level_mask: torch.Tensor | None = None, _margin_route: int = 0) -> None:
+             level_mask: torch.Tensor | None = None, _margin_route: int = 0, stats=None) -> None:
         """One tree from float32 g, h into `tree` = (feature, split_bin, default_left, left, right, value, node_count)
         rows; leaf_of_row is set and, if given, margin += value[leaf]. The private arguments are the histogram
         kernel's launch geometry: the result does not depend on them.
@@ -168,7 +175,10 @@ class Booster:
         `subsample` < 1 grows the tree on the rows sampled for (seed, round) only (leaf_of_row = -1 for the others;
         every row's margin still receives the tree's output); `level_mask`: [max_depth, f] uint8 on the device, the
         features each level may split on. `_margin_route`: how the rows outside the sample get their margin (0: the
-        partition updates the sampled rows and a tree walk the others, 1: one walk over all rows); the same sums."""
+        partition updates the sampled rows and a tree walk the others, 1: one walk over all rows); the same sums.
+
+        `stats` = (gain, cover): one tree's rows of `new_stats`; node k receives the gain of its split (0.0 at a leaf)
+        and its hessian sum over the rows the tree was grown on. The tree is the same with and without them."""
         assert g.dtype == h.dtype == torch.float32 and len(g) == len(h) == self.n and g.is_contiguous()
         assert h.is_contiguous() and all(t.is_contiguous() for t in tree)
         assert margin is None or (margin.dtype == torch.float64 and len(margin) == self.n and margin.is_contiguous())
@@ -184,6 +194,18 @@ class Booster:
                       and tuple(level_mask.shape) == (self.max_depth, self.f)):
                 raise ValueError(f"level_mask must be a contiguous uint8 [{self.max_depth}, {self.f}] tensor on "
                                  f"{self.dev}")
+        if stats is not None:
+            gain, cover = stats
+            for s in (gain, cover):
+                assert s.dtype == torch.float64 and s.is_contiguous() and s.numel() == self.cap and s.device == self.dev
+            check(_fns()["grow_stats"](ptr(self.bins), self.n, self.f, ptr(self.nbins), ptr(self.hoff), self.hsize,
+                                       ptr(g), ptr(h), self.max_depth, float(min_child_weight), float(reg_lambda),
+                                       float(gamma), float(eta), ptr(self.ws), self.ws.numel(), ptr(fe), ptr(sb),
+                                       ptr(dl), ptr(le), ptr(ri), ptr(val), ptr(cnt), ptr(self.leaf_of_row),
+                                       ptr(margin), rows, tile, int(seed) & (2 ** 64 - 1), int(round) & (2 ** 64 - 1),
+                                       thr, ptr(level_mask), int(_margin_route), ptr(gain), ptr(cover),
+                                       stream_handle(self.dev)), "mifx_gbdt_gpu_grow_stats")
+            return
         if thr == 2 ** 32 and level_mask is None:
             check(_fns()["grow"](ptr(self.bins), self.n, self.f, ptr(self.nbins), ptr(self.hoff), self.hsize, ptr(g),
                                  ptr(h), self.max_depth, float(min_child_weight), float(reg_lambda), float(gamma),
@@ -212,20 +234,24 @@ class Booster:
 def grow_numpy(bins: np.ndarray, nbins: np.ndarray, g: np.ndarray, h: np.ndarray, max_depth: int,
                min_child_weight: float = 1.0, reg_lambda: float = 1.0, gamma: float = 0.0, eta: float = 0.3,
                device: int = 0, _rows_per_wg: int | None = None, _feat_tile: int | None = None, _booster=None,
-               subsample: float = 1.0, seed: int = 0, round: int = 0, level_mask: np.ndarray | None = None):
+               subsample: float = 1.0, seed: int = 0, round: int = 0, level_mask: np.ndarray | None = None,
+               stats: bool = False):
     """One tree on the device from host arrays: (feature, split_bin, default_left, left, right, value, leaf_of_row),
     the outputs of the host's mifx_gbdt_grow_fixed (with subsample / level_mask: of mifx_gbdt_grow_fixed_ex on the
-    rows sampled for (seed, round); level_mask is a host [max_depth, f] uint8 array)."""
+    rows sampled for (seed, round); level_mask is a host [max_depth, f] uint8 array). `stats`: the nodes' (gain, cover)
+    of mifx_gbdt_grow_fixed_stats follow as an eighth and ninth array."""
     dev = device_for(device)
     with torch.cuda.device(dev):
         b = _booster or Booster(bins, nbins, max_depth, dev)
         trees = b.new_trees(1)
         tree = tuple(t[0] for t in trees)
+        st = tuple(s[0] for s in b.new_stats(1)) if stats else None
         gd = torch.from_numpy(np.ascontiguousarray(g, np.float32)).to(dev)
         hd = torch.from_numpy(np.ascontiguousarray(h, np.float32)).to(dev)
         lm = None if level_mask is None or max_depth == 0 else \
             torch.from_numpy(np.ascontiguousarray(level_mask, np.uint8).reshape(max_depth, -1)).to(dev)
         b.grow(gd, hd, tree, min_child_weight, reg_lambda, gamma, eta, None, _rows_per_wg, _feat_tile,
-               subsample=subsample, seed=seed, round=round, level_mask=lm)
+               subsample=subsample, seed=seed, round=round, level_mask=lm, stats=st)
         cnt = int(tree[6].item())
-        return tuple(t[:cnt].cpu().numpy() for t in tree[:6]) + (b.leaf_of_row.cpu().numpy(),)
+        out = tuple(t[:cnt].cpu().numpy() for t in tree[:6]) + (b.leaf_of_row.cpu().numpy(),)
+        return out if st is None else out + tuple(s[:cnt].cpu().numpy() for s in st)

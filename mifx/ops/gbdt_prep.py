@@ -2,6 +2,9 @@
 columns, binning of the raw table into the learner's row-major [n, f] uint16 layout, and forest prediction on raw
 features. Each equals its host function in csrc/gbdt.cpp exactly (mifx_gbdt_cuts, mifx_gbdt_bin, mifx_gbdt_predict).
 
+Feature contributions (`DevicePaths`, `contribs`): path-dependent TreeSHAP from the path table that the host builds
+(mifx/gbdt/shap.py), equal to the host's mifx_gbdt_contribs bit for bit.
+
 The column sort is torch.sort on the device, one column at a time; everything else is the kernels of gbdt_prep.hip.
 The private `_...` arguments are launch geometry: no result depends on them."""
 from __future__ import annotations
@@ -41,6 +44,12 @@ def _fns():
         "reg_classes": sig(lib, "mifx_gbdt_prep_reg_classes", []),
         "predict_multi": sig(lib, "mifx_gbdt_prep_predict_multi", [VP, I32, LONG, I32, VP, VP, I32, I32, F64, I32, VP,
                                                                    I32, VP]),
+        "contrib_rec_bytes": sig(lib, "mifx_gbdt_prep_contrib_rec_bytes", []),
+        "contrib_min_chunk": sig(lib, "mifx_gbdt_prep_contrib_min_chunk", []),
+        "contrib_max_lds": sig(lib, "mifx_gbdt_prep_contrib_max_lds", []),
+        "contrib_threads": sig(lib, "mifx_gbdt_prep_contrib_threads", []),
+        "contribs": sig(lib, "mifx_gbdt_prep_contribs", [VP, I32, LONG, I32, VP, VP, I32, F64, I32, I32, I32, VP, LONG,
+                                                             VP]),
     }
     assert fns["node_bytes"]() == NODE_DTYPE.itemsize
     return fns
@@ -256,3 +265,63 @@ def predict_multi(forest: DeviceForest, Xd: torch.Tensor, base: float, num_class
                                       float(base), chunk, ptr(out), int(route == "registers"), stream),
               "mifx_gbdt_prep_predict_multi")
     return out
+
+
+RECS_PER_CHUNK = 256      # path records staged in LDS at a time: 256 * 32 B = 8 KB (profiles/gbdt_contribs.md)
+
+
+class DevicePaths:
+    """A host path table (mifx.gbdt.shap.PathTable: built and validated on the host) on one device."""
+
+    def __init__(self, table, dev: torch.device):
+        fns = _fns()
+        assert fns["contrib_rec_bytes"]() == table.recs.dtype.itemsize
+        self.table, self.nfeat, self.n_trees, self.dev = table, table.nfeat, table.n_trees, dev
+        self.recs = torch.from_numpy(table.recs.view(np.uint8).reshape(-1)).to(dev)
+        self.leaf_off = torch.from_numpy(table.leaf_off).to(dev)
+
+
+def contrib_lds_threads(f: int, chunk: int | None = None) -> int:
+    """The largest workgroup (256, 128 or 64 threads) whose f sums per thread fit in LDS beside a chunk of the table;
+    0 if none does."""
+    fns = _fns()
+    room = fns["contrib_max_lds"]() - int(chunk or RECS_PER_CHUNK) * fns["contrib_rec_bytes"]()
+    return next((t for t in (fns["contrib_threads"](), 128, 64) if f * t * 8 <= room), 0)
+
+
+def contribs(paths: DevicePaths, Xd: torch.Tensor, base: float, out: torch.Tensor, n_trees: int | None = None,
+             _recs_per_chunk: int | None = None, _route: str | None = None, _threads: int | None = None) -> None:
+    """Feature contributions (path-dependent TreeSHAP) of the first n_trees trees of `paths` per row of a device
+    table, written into `out` [n, f + 1] (float64 on the device; a view with any row stride and unit column stride,
+    so a class's slice of [n, K, f + 1] works): columns 0 .. f - 1 the features, column f the bias. The bits of the
+    host's mifx_gbdt_contribs.
+
+    `_recs_per_chunk` (records of the path table staged in LDS at a time, at least 13) and `_route` ("lds": a row's
+    sums live in LDS and are stored once, the default when they fit; "output": they live in the output row) and
+    `_threads` (64, 128 or 256 per workgroup; by default the most that fit) are launch geometry: the result does not
+    depend on them."""
+    _check_matrix(Xd)
+    n, f = Xd.shape
+    if f != paths.nfeat or Xd.device != paths.dev:
+        raise ValueError(f"expected [n, {paths.nfeat}] features on {paths.dev}")
+    if not (out.dtype == torch.float64 and out.device == Xd.device and tuple(out.shape) == (n, f + 1)
+            and out.stride(1) == 1 and out.stride(0) >= f + 1):
+        raise ValueError(f"out must be a float64 [n, {f + 1}] tensor on {Xd.device} with unit column stride")
+    fns = _fns()
+    n_trees = paths.n_trees if n_trees is None else int(n_trees)
+    chunk = int(_recs_per_chunk or RECS_PER_CHUNK)
+    if not 0 <= n_trees <= paths.n_trees:
+        raise ValueError(f"n_trees must be in [0, {paths.n_trees}]")
+    if chunk < fns["contrib_min_chunk"]() or chunk * fns["contrib_rec_bytes"]() > fns["contrib_max_lds"]():
+        raise ValueError("launch geometry out of range")
+    fits = contrib_lds_threads(f, chunk)
+    route = ("lds" if fits else "output") if _route is None else _route
+    if route not in ("lds", "output"):
+        raise ValueError(f"unknown route {route!r}")
+    threads = int(_threads or (fits if route == "lds" else fns["contrib_threads"]()))
+    if threads not in (64, 128, fns["contrib_threads"]()) or (route == "lds" and threads > fits):
+        raise ValueError(f"{f} sums per row of {threads} threads do not fit in LDS beside a chunk of {chunk} records")
+    with torch.cuda.device(Xd.device):
+        check(fns["contribs"](ptr(Xd), int(Xd.dtype == torch.float64), n, f, ptr(paths.recs), ptr(paths.leaf_off),
+                              int(paths.table.tree_leaf[n_trees]), float(base), chunk, threads, int(route == "lds"), ptr(out),
+                              out.stride(0), stream_handle(Xd.device)), "mifx_gbdt_prep_contribs")

@@ -11,6 +11,7 @@ sampled round also walks the tree for the margins of the rows outside the sample
 per round), K >= 3 multi:softprob (one softmax gradient launch + K trees per round; the yardstick is K binary rounds).
 The softmax gradient kernel is also timed alone, against the 16 K n bytes it must move at least (the float64 margins
 in, float32 g and h out). The default, 0, is the squared-error round.
+`--stats 0` grows the trees without recording the nodes' gain and cover (1, the default, is what `fit` does).
 
   python tools/bench_gbdt.py --sizes 10000 100000 1000000 --out profiles/gbdt_gpu.jsonl
   python tools/bench_gbdt.py --sizes 1000000 --subsample 0.5 --host-rounds 1 --out profiles/gbdt_sample.jsonl
@@ -63,6 +64,8 @@ def main(argv=None) -> int:
                     help="sampled rounds: 0 = partition updates the sampled rows + a walk for the others, 1 = one walk")
     ap.add_argument("--num-class", type=int, default=0,
                     help="0: squared error (default); 2: binary:logistic; K >= 3: multi:softprob, K trees per round")
+    ap.add_argument("--stats", type=int, default=1, choices=[0, 1],
+                    help="1 (default): the grower records every node's gain and cover, as fit does; 0: it does not")
     ap.add_argument("--out", default=None, help="append one JSON line per size")
     a = ap.parse_args(argv)
 
@@ -118,6 +121,7 @@ def main(argv=None) -> int:
             margin = torch.full((K, n), base, dtype=torch.float64, device=dev)
             g, h = (torch.empty((K, n), dtype=torch.float32, device=dev) for _ in range(2))
             trees = bst.new_trees(total * K)
+            stats = bst.new_stats(total * K) if a.stats else None
             md = None if masks is None else torch.from_numpy(masks).to(dev)
             objective = "binary:logistic" if a.num_class else "reg:squarederror"
 
@@ -134,7 +138,8 @@ def main(argv=None) -> int:
                         t = it * K + k
                         bst.grow(g[k], h[k], tuple(x[t] for x in trees), 1.0, 1.0, 0.0, 0.3, margin[k],
                                  subsample=a.subsample, seed=0, round=t, level_mask=None if md is None else md[t],
-                                 _margin_route=a.margin_route)
+                                 _margin_route=a.margin_route,
+                                 stats=None if stats is None else tuple(x[t] for x in stats))
                 torch.cuda.synchronize()
 
             run(0, a.warmup)
@@ -155,13 +160,13 @@ def main(argv=None) -> int:
             same = all(np.array_equal(trees[k][0, :cnt].cpu().numpy(), w) for k, w in
                        ((0, first_twin[0]), (2, first_twin[2]), (3, first_twin[3]), (4, first_twin[4]),
                         (5, first_twin[5])))
-            del bst, yd, margin, g, h, trees
+            del bst, yd, margin, g, h, trees, stats
             torch.cuda.empty_cache()
         rec = {"n": n, "features": a.features, "max_bins": a.max_bins, "max_depth": a.max_depth,
                "subsample": a.subsample, "colsample_bytree": a.colsample_bytree, "margin_route": a.margin_route,
                "host_threads": a.threads, "bin_s": round(t_bin, 4), "upload_s": round(t_up, 4),
                "host_round_s": [round(t, 5) for t in th], "host_fixed_round_s": [round(t, 5) for t in tt],
-               "num_class": a.num_class, "trees_per_round": K,
+               "num_class": a.num_class, "trees_per_round": K, "node_stats": a.stats,
                "gpu_round_s": round(t_gpu, 6), "gpu_rounds": a.rounds, "gpu_grad_s": round(t_grad, 8),
                "gpu_grad_reps": reps, "grad_min_bytes": 16 * K * n, "grad_GBps": round(16e-9 * K * n / t_grad, 1),
                "host_over_gpu": round(min(th) / t_gpu, 2), "first_tree_equals_host_twin": bool(same)}
