@@ -52,6 +52,7 @@ typedef __bf16 v2bf __attribute__((ext_vector_type(2)));
 typedef short v4s __attribute__((ext_vector_type(4)));
 typedef short v8s __attribute__((ext_vector_type(8)));
 typedef float v4f __attribute__((ext_vector_type(4)));
+typedef unsigned int v4u __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) v4s lds_v4s;
 
 #include "wd_opt.h"
@@ -66,6 +67,11 @@ typedef __attribute__((address_space(3))) v4s lds_v4s;
 constexpr int T = WDC_T;
 static_assert(T == 128 || T == 64 || T == 256, "T");
 constexpr bool ONE_ITER = T == 256 || T == 64;  // see the iteration loop of wdc_fused
+// The prologue that issues each stage's loads at once (args_landed, one feed evaluation per lane, records_landed in
+// wdc_fused): in the T = 256 and T = 64 builds, where it shortens the step (profiles/wd_load_issue.md: 26.4 -> 25.5 us
+// at B = 65536, 12.5 -> 12.1 at B = 40). The T = 128 build keeps the earlier order: with it B = 8192 measured 0.4 us
+// SLOWER (same note), for a reason not found.
+constexpr bool LAND = ONE_ITER;
 constexpr int MAXW = 8;  // waves per workgroup: T / (16 TBN), TBN = 16-example column blocks per wave (1 or 2)
 // Row padding (elements): WPAD for the weight images, PAD for the staging images; with the row permutations below
 // (wperm, sperm16) every LDS access site is conflict-free in the bank model (tools/lds_banks.py). (XOR swizzles
@@ -689,14 +695,35 @@ __global__ __launch_bounds__(64 * (T / (16 * TBN)), 1) void wdc_fused(const uint
       return;
     }
   }
-  // the XCD this workgroup's slab row is written from (its L2 holds the row for the XCD-local reduction,
-  // csrc/wide_deep.hip wd_reduce_xcd)
   if constexpr (TAIL) TSTAMP(0);
-  if (TRAIN && xcd_of != nullptr && tid == 0) {
-    if (TAIL)  // read by workgroups on every XCD after the first barrier: write-through
-      __hip_atomic_store(xcd_of + blockIdx.x, mifx_xcc_id(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    else
-      xcd_of[blockIdx.x] = mifx_xcc_id();
+  // the XCD this workgroup's slab row is written from (its L2 holds the row for the XCD-local reduction,
+  // csrc/wide_deep.hip wd_reduce_xcd). First read by the next kernel (TAIL: by the other workgroups after the first
+  // grid-wide barrier). LAND: stored behind args_landed below, which has the pointer; otherwise here, behind a wait
+  // for that argument.
+  auto store_xcd = [&]() {
+    if (TRAIN && xcd_of != nullptr && tid == 0) {
+      if (TAIL)  // read by workgroups on every XCD: write-through
+        __hip_atomic_store(xcd_of + blockIdx.x, mifx_xcc_id(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      else
+        xcd_of[blockIdx.x] = mifx_xcc_id();
+    }
+  };
+  if constexpr (!LAND) store_xcd();
+  // ---- entry (LAND): one round trip for everything the prologue needs that is not a preloaded argument dword. The step
+  // counter and the wide bias are read through preloaded pointers, and nothing in front of the image loads below uses
+  // an argument that is not preloaded, so no wait on a scalar load stands before the first of them. The arguments the
+  // record chain needs (the feed, and with it grad_scale, tmap, stride, xcd_of and, where the iteration count depends
+  // on it, the grid size) are consumed at one point, args_landed below, after the image loads and the zero loop have
+  // been issued: one wait for them and the step counter together.
+#ifndef WDC_DIAG_NOSTEP
+#define WDC_DIAG_NOSTEP 0
+#endif
+  // WDC_DIAG_NOSTEP (stamp builds only, wrong record order): step 0's records, no step-counter load ahead of them
+  long long step0 = 0;
+  float wbias0 = 0.f;  // needed by the loss phase; constant for the launch
+  if constexpr (LAND) {
+    step0 = (step_ctr && !WDC_DIAG_NOSTEP) ? step_ctr[0] : 0;
+    wbias0 = PERSIST ? 0.f : wide[WIDE_BIAS];
   }
 
 #ifndef WDC_REG_STAGE
@@ -734,7 +761,8 @@ __global__ __launch_bounds__(64 * (T / (16 * TBN)), 1) void wdc_fused(const uint
       for (int i = 0; i < PER_STAGE; ++i) wst[i] = wimg[min(i * NTHR + tid, NCH_STAGE - 1)];
     }
     // (one launch = one step: the wait for the image and the block barrier come after the first iteration's
-    // record fetch below, so the step-counter -> records latency chain runs under the staging instead of after it)
+    // record fetch below, so the chain step counter + arguments -> feed arithmetic -> records -- two round trips, see
+    // args_landed and fetch -- runs under the staging instead of after it)
     if constexpr (PERSIST) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   }
   float* wlds = red + 64;  // PERSIST: the fp32 wide weights [WIDE_PAD], resident for the launch
@@ -745,17 +773,33 @@ __global__ __launch_bounds__(64 * (T / (16 * TBN)), 1) void wdc_fused(const uint
     __syncthreads();
   }
 
-#ifndef WDC_DIAG_NOSTEP
-#define WDC_DIAG_NOSTEP 0
-#endif
-  // WDC_DIAG_NOSTEP (stamp builds only, wrong record order): step 0's records, no step-counter load ahead of them
-  const long long step0 = (step_ctr && !WDC_DIAG_NOSTEP) ? step_ctr[0] : 0;
+  // PERSIST (grid 1, batch <= T): exactly one iteration, known at compile time, so the dW accumulators die at
+  // their layer's emission instead of living across a loop back-edge
+  // ONE_ITER (T = 256: the host launches grid >= ceil(batch / T)): every workgroup runs exactly its own iteration,
+  // also known at compile time -- the dW accumulators live only through their layer's phase, and no prefetch
+  constexpr bool SINGLE = PERSIST || ONE_ITER;
+  // args_landed: the step counter, the wide bias and the non-preloaded arguments of the prologue, waited for once.
+  // (The empty asm reads and "writes" them, so their loads can neither be sunk past this point nor be waited for one
+  // by one in front of it.)
+  MifxFeed feed_l = feed;
+  unsigned int grid_l = SINGLE ? 1u : gridDim.x;
+  if constexpr (LAND) {
+    asm volatile(""
+                 : "+s"(step0), "+s"(wbias0), "+s"(feed_l.gstride), "+s"(feed_l.goff), "+s"(feed_l.key),
+                   "+s"(grad_scale), "+s"(stride), "+s"(grid_l)
+                 : "s"(tmap), "s"(xcd_of));  // (pointers as inputs only: they keep their global address space)
+    // the store is acknowledged under the feed arithmetic and the record fetch, long before the prologue's wait on
+    // vector memory
+    store_xcd();
+  } else {
+    step0 = (step_ctr && !WDC_DIAG_NOSTEP) ? step_ctr[0] : 0;
+  }
   constexpr bool kPersist = PERSIST;
   const int nsteps = kPersist ? ta.nsteps : 1;
   for (int ps = 0; ps < nsteps; ++ps) {
   // record feed (csrc/feed.h): the step's place in the (optionally shuffled) global record stream; a fixed start
   // (eval / predict) reads records start_fixed.. in stored order
-  MifxFeed fd = feed;
+  MifxFeed fd = feed_l;
   MifxFeedStep fs;
   if (step_ctr) {
     fs = mifx_feed_step(fd, step0 + ps, n_data);
@@ -766,7 +810,9 @@ __global__ __launch_bounds__(64 * (T / (16 * TBN)), 1) void wdc_fused(const uint
     fs.h = 1;
   }
   const int niters = (int)((batch + T - 1) / T);
-  const int my_iters = (niters - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;
+  // (one iteration per workgroup: no grid size, no division)
+  const int my_iters = SINGLE ? ((int)blockIdx.x < niters ? 1 : 0)
+                              : (niters - (int)blockIdx.x + (int)grid_l - 1) / (int)grid_l;
   const float qbound = fmaxf(fabsf(grad_scale) * (float)(max(my_iters, 1) * T), 1e-30f);
   const float qscale = exp2f(fminf(floorf(log2f(1073741824.f / qbound)), 100.f));
   const float qinv = 1.f / qscale;
@@ -815,14 +861,48 @@ __global__ __launch_bounds__(64 * (T / (16 * TBN)), 1) void wdc_fused(const uint
   // the column block whose wide part / loss this lane computes (lanes h < TBN own one each)
   const int mtb = TBN == 2 ? (h & 1) : 0;
 
+  // Every lane loads the records of row r of all the wave's column blocks (lanes h == 0 use the dense inputs of
+  // every block and block 0's ids, lanes h == 1 block 1's ids and label). LAND: a lane evaluates the feed -- the Feistel
+  // permutation -- for ONE block, h & 1, and takes the other block's record index from lane ^ 16, which evaluated it
+  // for the same row: one permutation pass in front of the loads instead of TBN in a row, the same addresses, and
+  // all the loads issued back to back.
   auto fetch = [&](int it, uint4 (&u)[TBN][2]) {
+    long long dib[TBN];
+    if constexpr (!LAND) {  // every lane evaluates the feed for each of its blocks in turn
+#pragma unroll
+      for (int tb = 0; tb < TBN; ++tb) {
+        const long long row = min((long long)it * T + EPW * w + 16 * tb + r, batch - 1);
+        dib[tb] = mifx_feed_record(fd, fs, row, n_data);  // host guarantees batch <= n_data
+      }
+    }
+    const int ftb = TBN == 2 ? (h & 1) : 0;
+    const long long row = min((long long)it * T + EPW * w + 16 * ftb + r, batch - 1);
+    const long long di = LAND ? mifx_feed_record(fd, fs, row, n_data) : 0;
+    if constexpr (LAND) dib[0] = di;
+    if constexpr (TBN == 2 && LAND) {
+      constexpr int kXor16 = (0x10 << 10) | 0x1f;  // ds_swizzle bit mode: lane ^ 16 inside each half wave
+      const unsigned int olo = (unsigned int)__builtin_amdgcn_ds_swizzle((int)(unsigned int)di, kXor16);
+      const unsigned int ohi = (unsigned int)__builtin_amdgcn_ds_swizzle((int)(unsigned int)((unsigned long long)di >> 32), kXor16);
+      const long long dj = (long long)(((unsigned long long)ohi << 32) | olo);
+      dib[0] = ftb ? dj : di;
+      dib[1] = ftb ? di : dj;
+    }
 #pragma unroll
     for (int tb = 0; tb < TBN; ++tb) {
-      const long long row = min((long long)it * T + EPW * w + 16 * tb + r, batch - 1);
-      const long long di = mifx_feed_record(fd, fs, row, n_data);  // host guarantees batch <= n_data
-      u[tb][0] = data[2 * di];
-      u[tb][1] = data[2 * di + 1];
+      u[tb][0] = data[2 * dib[tb]];
+      u[tb][1] = data[2 * dib[tb] + 1];
     }
+  };
+  // the records are consumed whole at this point: no part of a record load can be issued behind it
+  auto records_landed = [&](uint4 (&u)[TBN][2]) {
+#pragma unroll
+    for (int tb = 0; tb < TBN; ++tb)
+#pragma unroll
+      for (int k = 0; k < 2; ++k) {
+        v4u t = {u[tb][k].x, u[tb][k].y, u[tb][k].z, u[tb][k].w};
+        asm volatile("" : "+v"(t));
+        u[tb][k] = make_uint4(t[0], t[1], t[2], t[3]);
+      }
   };
   uint4 nu[TBN][2];
   fetch(blockIdx.x, nu);
@@ -832,25 +912,28 @@ __global__ __launch_bounds__(64 * (T / (16 * TBN)), 1) void wdc_fused(const uint
       if (i * NTHR + tid < NCH_STAGE) *(uint4*)(lds + img_lds((i * NTHR + tid) * 8)) = wst[i];
   }
   if constexpr (!PERSIST) {  // weight image (LDS-DMA) and the first records landed; wgrad zeroed
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    // the one wait of the prologue on vector memory, and its last vector-memory instruction: vmcnt(0) as the builtin
+    // the compiler's own wait insertion sees (it adds none for the records consumed right behind it)
+    if constexpr (LAND) {
+      __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0) only
+      records_landed(nu);
+      asm volatile("" ::: "memory");
+    } else {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
     __syncthreads();
   }
 
   STAMP(1);
   BSTAMP(1);
-  // PERSIST (grid 1, batch <= T): exactly one iteration, known at compile time, so the dW accumulators die at
-  // their layer's emission instead of living across a loop back-edge
-  // ONE_ITER (T = 256: the host launches grid >= ceil(batch / T)): every workgroup runs exactly its own iteration,
-  // also known at compile time -- the dW accumulators live only through their layer's phase, and no prefetch
-  constexpr bool SINGLE = PERSIST || ONE_ITER;
-  const int it_end = SINGLE ? 1 : niters, it_inc = SINGLE ? 1 : (int)gridDim.x;
+  const int it_end = SINGLE ? 1 : niters, it_inc = SINGLE ? 1 : (int)grid_l;
   for (int itv = SINGLE ? 0 : (int)blockIdx.x; itv < it_end; itv += it_inc) {
     const int it = ONE_ITER ? (int)blockIdx.x : itv;
 #ifdef WDC_STAMPS
     stamp_on = niters > (int)gridDim.x ? it == (int)(blockIdx.x + gridDim.x) : it == (int)blockIdx.x;
 #endif
     STAMP(2);
-    const bool last = SINGLE || it + (int)gridDim.x >= niters;  // this workgroup's final iteration: dW final
+    const bool last = SINGLE || it + (int)grid_l >= niters;  // this workgroup's final iteration: dW final
     float* my_slab = TRAIN ? slab + (size_t)blockIdx.x * stride : nullptr;
     const long long pstep = step0 + ps + 1;  // PERSIST: the optimizer step (Adam bias correction)
     const bool plast = ps + 1 == nsteps;
@@ -864,7 +947,7 @@ __global__ __launch_bounds__(64 * (T / (16 * TBN)), 1) void wdc_fused(const uint
       u[tb][0] = nu[tb][0];
       u[tb][1] = nu[tb][1];
     }
-    if constexpr (!SINGLE) fetch(it + gridDim.x, nu);  // next iteration's records
+    if constexpr (!SINGLE) fetch(it + (int)grid_l, nu);  // next iteration's records
 
     // wide gather for the lane's column block (issued before the forward: its latency hides under MFMAs)
     const uint4 m0 = mtb ? u[TBN - 1][0] : u[0][0], m1 = mtb ? u[TBN - 1][1] : u[0][1];
@@ -878,7 +961,7 @@ __global__ __launch_bounds__(64 * (T / (16 * TBN)), 1) void wdc_fused(const uint
       ids[f] = kWideOff[f] + id;
       wv[f] = PERSIST ? wlds[ids[f]] : wide[ids[f]];
     }
-    const float wbias = PERSIST ? wlds[WIDE_BIAS] : wide[WIDE_BIAS];
+    const float wbias = PERSIST ? wlds[WIDE_BIAS] : LAND ? wbias0 : wide[WIDE_BIAS];  // (LAND: requested at kernel entry)
 
     // ---- forward, in registers
     v8bf a0[TBN][1];

@@ -54,17 +54,35 @@ struct ScState {
   int w;           // wsc entry
   float p, a0, a1;
 };
+// The four loads are unconditional, at the column clamped into [0, stride): straight-line code with no branch per
+// load, so they are issued back to back with whatever the caller loads next to them. A thread past the last column
+// gets w = -1 (padding) and stores nothing.
 __device__ __forceinline__ ScState sc_load(int gi, int stride, const int* __restrict__ wsc, const float* __restrict__ param,
                                            const float* __restrict__ s0, const float* __restrict__ s1) {
-  ScState st{-1, 0.f, 0.f, 0.f};
-  if (gi < stride) {
-    st.w = wsc[gi];
-    st.p = param[gi];
-    st.a0 = s0[gi];
-    st.a1 = s1[gi];
-  }
+  const int gc = min(gi, stride - 1);
+  ScState st{wsc[gc], param[gc], s0[gc], s1[gc]};
+  if (gi >= stride) st.w = -1;
   return st;
 }
+// The one point where a column's loads are consumed, placed by the kernel after everything it needs has been issued:
+// the state, the step slot, and wt_out and both hyper-parameter structs (kernel arguments past the preloaded dwords) must be in
+// registers here, so the compiler can neither sink the state loads into the branch of sc_update that uses them nor
+// start the hyper-parameter load only there -- one wait for one round trip, then the update runs from registers.
+// NG: the gradient words the kernel loaded beside the state (1 slab entry, 8 partials), landed at the same point.
+template <int NG>
+__device__ __forceinline__ void sc_landed(ScState& st, float (&g)[NG], long long& step, const uint16_t* wt_out, OptHyper& hd,
+                                          OptHyper& hw) {
+  static_assert(NG == 1 || NG == 8, "gradient words per column");
+  asm volatile(""
+               : "+v"(st.w), "+v"(st.p), "+v"(st.a0), "+v"(st.a1), "+s"(step), "+s"(hd.kind), "+s"(hd.lr),
+                 "+s"(hd.beta1), "+s"(hd.beta2), "+s"(hd.eps), "+s"(hd.l1), "+s"(hd.l2), "+s"(hd.lr_power),
+                 "+s"(hw.kind), "+s"(hw.lr), "+s"(hw.beta1), "+s"(hw.beta2), "+s"(hw.eps), "+s"(hw.l1), "+s"(hw.l2),
+                 "+s"(hw.lr_power), "+v"(g[0])
+               : "s"(wt_out));  // (an input only: the pointer keeps its global address space)
+  if constexpr (NG == 8)
+    asm volatile("" : "+v"(g[1]), "+v"(g[2]), "+v"(g[3]), "+v"(g[4]), "+v"(g[5]), "+v"(g[6]), "+v"(g[7]));
+}
+// wsc == -1 (padding) decides the update and its stores only; sc_load's loads never depend on it
 __device__ __forceinline__ void sc_update(int gi, ScState st, float g, const OptHyper& hd, const OptHyper& hw,
                                           long long step, float* __restrict__ param, float* __restrict__ s0,
                                           float* __restrict__ s1, uint16_t* __restrict__ wt_out) {

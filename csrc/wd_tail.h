@@ -189,9 +189,13 @@ __global__ __launch_bounds__(256) void wd_reduce_opt(
 
 // Slab-column-order optimizer state (the register-chained trainer): param / s0 / s1 are indexed by slab column and
 // wsc[col] says what the column is (-1 padding, -2 wide weight, >= 0 DNN weight with that bf16 weight-image offset).
-// No indirection: a thread's state is loaded before the slab reduction starts and is in registers when the summed
-// gradient arrives (the canonical-order kernel above must wait for the gradient's inv[] entry, then for param/s0/s1
-// at that index, then for wmap).
+// No indirection: a thread's state needs no other load's result for its address (the canonical-order kernel above must
+// wait for the gradient's inv[] entry, then for param/s0/s1 at that index, then for wmap). sc_load issues its four
+// loads unconditionally; what keeps them in front of the gradient's arrival differs by kernel: in wd_reduce_opt_sc the
+// reduction's loop and barriers stand between the loads and their use, so they stay where the source has them; in the
+// straight-line kernels (wd_opt1_sc, wd_res_opt_sc) nothing does -- the compiler used to sink them into the branch of
+// sc_update that uses them, behind the wait for the gradient -- so those consume everything at one point, sc_landed
+// (csrc/wd_opt.h), placed behind the last load.
 __global__ __launch_bounds__(256) void wd_reduce_opt_sc(const float4* __restrict__ slab, int G, int stride,
                                                         const int* __restrict__ wsc, float* __restrict__ param,
                                                         float* __restrict__ s0, float* __restrict__ s1,
@@ -218,18 +222,23 @@ __global__ __launch_bounds__(256) void wd_reduce_opt_sc(const float4* __restrict
 // to reduce, so one thread per column and a quarter of wd_reduce_opt_sc's workgroups (93 vs 370). Bit-identical:
 // the general kernel's column sum of one row adds only zeros to it. Each workgroup owns step slot blockIdx.x, as
 // there; a trainer always takes the same path (its slab height is fixed), so the slots it reads stay in step.
+// Argument order: everything the first loads need (slab .. s1, step_ctr) is within the 14 preloaded argument dwords
+// (csrc/wide_deep.hip), wt_out and the hyper-parameters come by a load issued beside the data loads. The slab entry,
+// the state and the step slot are all issued before sc_landed's single wait.
 __global__ __launch_bounds__(256) void wd_opt1_sc(const float* __restrict__ slab, int stride,
                                                   const int* __restrict__ wsc, float* __restrict__ param,
                                                   float* __restrict__ s0, float* __restrict__ s1,
-                                                  uint16_t* __restrict__ wt_out, long long* __restrict__ step_ctr,
+                                                  long long* __restrict__ step_ctr, uint16_t* __restrict__ wt_out,
                                                   OptHyper hd, OptHyper hw) {
   __shared__ long long s_step;
-  if (threadIdx.x == 0) s_step = step_ctr[blockIdx.x] + 1;
   const int gi = blockIdx.x * 256 + threadIdx.x;
-  const ScState st = sc_load(gi, stride, wsc, param, s0, s1);
-  const float g = gi < stride ? slab[gi] : 0.f;
+  ScState st = sc_load(gi, stride, wsc, param, s0, s1);
+  float g[1] = {slab[min(gi, stride - 1)]};
+  long long slot = step_ctr[blockIdx.x];  // wave-uniform (a scalar load); thread 0's copy is the one that counts
+  sc_landed(st, g, slot, wt_out, hd, hw);
+  if (threadIdx.x == 0) s_step = slot + 1;
   __syncthreads();
-  if (gi < stride) sc_update(gi, st, g, hd, hw, s_step, param, s0, s1, wt_out);
+  if (gi < stride) sc_update(gi, st, g[0], hd, hw, s_step, param, s0, s1, wt_out);
   if (threadIdx.x == 0) step_ctr[blockIdx.x] = s_step;
 }
 
@@ -409,11 +418,16 @@ __global__ __launch_bounds__(256) void wd_reduce_res(const float4* __restrict__ 
 
 // Level 2 for column gi: part[0][gi] + ... + part[7][gi] in residue order. load(p) reads one partial: a plain load
 // after a kernel boundary, an agent-scope load inside wd_reduce_res_fused.
+// The loads are unconditional at the column clamped into [0, stride) (straight-line code, issued back to back; a
+// thread past the last column stores nothing), and separate from the fold so that a kernel can issue its other
+// loads between the two.
 template <class Load>
-__device__ __forceinline__ float res_partial_sum(Load load, const float* part, int gi, int stride) {
-  float pv[8];
+__device__ __forceinline__ void res_partial_load(Load load, const float* part, int gi, int stride, float (&pv)[8]) {
+  const int gc = min(gi, stride - 1);
 #pragma unroll
-  for (int x = 0; x < 8; ++x) pv[x] = gi < stride ? load(part + (size_t)x * stride + gi) : 0.f;
+  for (int x = 0; x < 8; ++x) pv[x] = load(part + (size_t)x * stride + gc);
+}
+__device__ __forceinline__ float res_partial_fold(const float (&pv)[8]) {
   float g = pv[0];
 #pragma unroll
   for (int x = 1; x < 8; ++x) g += pv[x];
@@ -424,12 +438,18 @@ __device__ __forceinline__ float res_partial_sum(Load load, const float* part, i
 __global__ __launch_bounds__(256) void wd_res_opt_sc(const float* __restrict__ part, int stride,
                                                      const int* __restrict__ wsc, float* __restrict__ param,
                                                      float* __restrict__ s0, float* __restrict__ s1,
-                                                     uint16_t* __restrict__ wt_out, long long* __restrict__ step_ctr,
+                                                     long long* __restrict__ step_ctr, uint16_t* __restrict__ wt_out,
                                                      OptHyper hd, OptHyper hw) {
+  // One round trip: part .. s1 and step_ctr are preloaded argument dwords (wt_out and the hyper-parameters are loaded
+  // beside the data), and the 8 partials, the state and the step slot are all issued before sc_landed's wait.
   const int t = threadIdx.x, gi = blockIdx.x * 256 + t;
-  const long long step = step_ctr[blockIdx.x] + 1;
-  const float g = res_partial_sum([](const float* p) { return *p; }, part, gi, stride);
-  const ScState st = sc_load(gi, stride, wsc, param, s0, s1);
+  long long slot = step_ctr[blockIdx.x];
+  float pv[8];
+  res_partial_load([](const float* p) { return *p; }, part, gi, stride, pv);
+  ScState st = sc_load(gi, stride, wsc, param, s0, s1);
+  sc_landed(st, pv, slot, wt_out, hd, hw);
+  const long long step = slot + 1;
+  const float g = res_partial_fold(pv);
   if (gi < stride) sc_update(gi, st, g, hd, hw, step, param, s0, s1, wt_out);
   if (t == 0) step_ctr[blockIdx.x] = step;
   if (blockIdx.x == 0) fan_out_slots<256>(step_ctr, gridDim.x, step);
@@ -474,8 +494,10 @@ __global__ __launch_bounds__(256) void wd_reduce_res_fused(const float4* __restr
   const int gi = c * 256 + t;
   const long long step = step_ctr[c] + 1;
   const auto ld_agent = [](const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
-  const float g = res_partial_sum(ld_agent, part, gi, stride);
+  float pv[8];
+  res_partial_load(ld_agent, part, gi, stride, pv);
   const ScState st = sc_load(gi, stride, wsc, param, s0, s1);
+  const float g = res_partial_fold(pv);
   if (gi < stride) sc_update(gi, st, g, hd, hw, step, param, s0, s1, wt_out);
   if (t == 0) {
     step_ctr[c] = step;

@@ -782,7 +782,7 @@ int mifx_wd_reduce_opt_sc(const float* slab, int G, int stride, const int* wsc, 
   const OptHyper hd = opt_hyper(hyper_dnn), hw = opt_hyper(hyper_wide);
   if (G == 1)
     hipLaunchKernelGGL(wd_opt1_sc, dim3((stride + 255) / 256), dim3(256), 0, stream, slab, stride, wsc, param, s0, s1,
-                       (uint16_t*)wt_out, step_ctr, hd, hw);
+                       step_ctr, (uint16_t*)wt_out, hd, hw);
   else
     hipLaunchKernelGGL(wd_reduce_opt_sc, grid, dim3(256), 0, stream, (const float4*)slab, G, stride, wsc, param, s0,
                        s1, (uint16_t*)wt_out, step_ctr, hd, hw);
@@ -826,8 +826,8 @@ int mifx_wd_reduce_res_opt(const float* slab, int G, int stride, float* part, co
   if ((int)g2.x > STEP_SLOTS) return -1;
   hipLaunchKernelGGL(wd_reduce_res, dim3(8 * mifx_wd_xcd_chunks(stride)), dim3(256), 0, stream, (const float4*)slab, G,
                      stride, (float4*)part);
-  hipLaunchKernelGGL(wd_res_opt_sc, g2, dim3(256), 0, stream, part, stride, wsc, param, s0, s1, (uint16_t*)wt_out,
-                     step_ctr, opt_hyper(hyper_dnn), opt_hyper(hyper_wide));
+  hipLaunchKernelGGL(wd_res_opt_sc, g2, dim3(256), 0, stream, part, stride, wsc, param, s0, s1, step_ctr,
+                     (uint16_t*)wt_out, opt_hyper(hyper_dnn), opt_hyper(hyper_wide));
   return (int)hipGetLastError();
 }
 
