@@ -91,7 +91,8 @@ __global__ __launch_bounds__(256) void col_moments_p2(const Mom* __restrict__ pa
   }
 }
 
-// bucket index = number of boundaries <= x  (tf.raw_ops.Bucketize / tft.apply_buckets)
+// bucket index = number of boundaries <= x  (tf.raw_ops.Bucketize / tft.apply_buckets); NaN -> nb, as
+// np.searchsorted(side="right") and the host path place a missing value
 __global__ __launch_bounds__(256) void bucketize_k(const double* __restrict__ x, long long n,
                                                    const double* __restrict__ bnd, int nb,
                                                    long long* __restrict__ out) {
@@ -103,7 +104,7 @@ __global__ __launch_bounds__(256) void bucketize_k(const double* __restrict__ x,
     int lo = 0, hi = nb;
     while (lo < hi) {
       const int mid = (lo + hi) >> 1;
-      const bool le = b[mid] <= v;
+      const bool le = !(b[mid] > v);  // == (b[mid] <= v) for ordered pairs; a NaN goes to nb (upper_bound)
       lo = le ? mid + 1 : lo;
       hi = le ? hi : mid;
     }

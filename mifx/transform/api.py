@@ -222,6 +222,9 @@ def _moments(a: np.ndarray) -> dict:
         from ..ops import analyzers
 
         m = analyzers.column_moments(a, device=c.device)
+        if m["count"] != a.size:  # column_moments skips NaNs; here any NaN poisons the moments (numpy, parallel.py)
+            nan = float("nan")
+            return {"mean": nan, "var": nan, "min": nan, "max": nan, "count": int(a.size)}
         return {"mean": m["mean"], "var": m["std"] ** 2, "min": m["min"], "max": m["max"], "count": int(a.size)}
     return {"mean": float(a.mean()) if a.size else 0.0, "var": float(a.var()) if a.size else 0.0,
             "min": float(a.min()) if a.size else 0.0, "max": float(a.max()) if a.size else 0.0,
