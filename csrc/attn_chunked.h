@@ -51,16 +51,9 @@
 #include <stdint.h>
 
 #include "counter_rng.h"
+#include "mfma_stage.h"
 
 namespace {
-
-typedef __bf16 bf16;
-typedef __bf16 v8bf __attribute__((ext_vector_type(8)));
-typedef __bf16 v4bf __attribute__((ext_vector_type(4)));
-typedef short v4s __attribute__((ext_vector_type(4)));
-typedef short v8s __attribute__((ext_vector_type(8)));
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) v4s lds_v4s;
 
 constexpr int D = 64;      // head dim
 constexpr int LD = D + 8;  // LDS row of a [token][d] image (elements): 144 B. K and V of 512 rows must fit 160 KB
@@ -70,13 +63,6 @@ constexpr float kFloor = -3.0e38f;  // where the running maximum starts, and wha
 constexpr float kLog2e = 1.4426950408889634f;
 constexpr v4f kZero4 = {0.f, 0.f, 0.f, 0.f};
 
-__device__ __forceinline__ v4s tr_read(const bf16* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)(p));
-}
-__device__ __forceinline__ v8bf cat8(v4s a, v4s b) {
-  v8s r = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-  return __builtin_bit_cast(v8bf, r);
-}
 __device__ __forceinline__ v8bf ld8(const bf16* p) { return *(const v8bf*)p; }
 __device__ __forceinline__ v8bf zero8() {
   const v8s z = {0, 0, 0, 0, 0, 0, 0, 0};

@@ -25,18 +25,11 @@
 //    in split order (deterministic) into the parameter's layout (channels_last or contiguous).
 //  * blockIdx -> work is XCD-aware: the slices of a split (same pixels) and neighbouring splits (shared halo rows)
 //    run on one XCD, whose L2 then serves the re-reads.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "mfma_stage.h"
 
 namespace {
 
-typedef __bf16 bf16;
-typedef __bf16 v8bf __attribute__((ext_vector_type(8)));
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef short v4s __attribute__((ext_vector_type(4)));
-typedef short v8s __attribute__((ext_vector_type(8)));
 typedef unsigned int u4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) v4s lds_v4s;
 
 constexpr int NT = 256;
 constexpr int CS = 64;  // channels per slice (both operands): one 128-byte LDS row per pixel
@@ -49,11 +42,6 @@ constexpr int CS = 64;  // channels per slice (both operands): one 128-byte LDS 
 
 __device__ __forceinline__ v4f mfma(v8bf a, v8bf b, v4f c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ v4s tr_read(const bf16* p) { return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)p); }
-__device__ __forceinline__ v8bf cat8(v4s a, v4s b) {
-  const v8s r = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-  return __builtin_bit_cast(v8bf, r);
 }
 // element offset of (row, 16-channel block cb, element e) in a swizzled [rows][64] image
 __device__ __forceinline__ int sw(int row, int cb, int e) { return row * CS + 16 * (cb ^ ((row >> 1) & 3)) + e; }

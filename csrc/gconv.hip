@@ -18,14 +18,10 @@
 //    halo rows are reused from L2 while they are hot.
 //  * The input gradient of a stride-1 convolution is the same operation on dy with the weight flipped
 //    spatially and transposed ([g][c][R-1-r][S-1-s][k]) and pad' = R-1-pad, so one kernel serves both.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "mfma_stage.h"
 
 namespace {
 
-typedef __bf16 bf16;
-typedef __bf16 v8bf __attribute__((ext_vector_type(8)));
-typedef float v4f __attribute__((ext_vector_type(4)));
 typedef unsigned int u4 __attribute__((ext_vector_type(4)));
 
 constexpr int kThreads = 256;
@@ -373,17 +369,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 8))
 // elements per lane, come from ds_read_b64_tr_b16 transposed reads. The reduction order inside a 32-chunk is
 // permuted identically for both operands (element j of lane group g <-> pixel row 4g + j for j < 4,
 // 16 + 4g + j - 4 for j >= 4), which makes every transposed read conflict-free.
-typedef short v4s __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) v4s lds_v4s;
 constexpr int WLD = 144;  // LDS row (bf16 elements): 128 + 16 pad = 288 B
-
-__device__ __forceinline__ v4s tr_read(const bf16* p) { return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)p); }
-__device__ __forceinline__ v8bf cat8(v4s a, v4s b) {
-  const v4s r0 = a, r1 = b;
-  typedef short v8s __attribute__((ext_vector_type(8)));
-  const v8s r = {r0[0], r0[1], r0[2], r0[3], r1[0], r1[1], r1[2], r1[3]};
-  return __builtin_bit_cast(v8bf, r);
-}
 
 // Split over output pixels (splits > 1, blockIdx.z = g * splits + split): few (tap, k, group) tiles -- a single
 // group, e.g. ResNet-50's convs -- would leave most CUs idle, so the pixel reduction is cut into `splits` ranges of

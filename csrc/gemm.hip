@@ -11,51 +11,18 @@
 //  * each workgroup owns a BM x BN output tile; waves are WM x WN, each owning (BM/WM) x (BN/WN);
 //  * per K-tile of 64: every lane issues 16-byte global->LDS DMA loads (no VGPR round trip) for the NEXT tile
 //    while the waves run the MFMAs of the current one; one barrier per K-tile;
-//  * LDS images are row-major [rows][64] bf16 (128-byte rows) with the 16-byte chunk index XOR-swizzled by
-//    ((row >> 1) & 7): the 16 rows of an MFMA fragment read (ds_read_b128, lanes l & 15) then hit 16 distinct 16-byte
-//    slots of the 256-byte bank row. glds destinations are lane-linear, so the swizzle is applied to each lane's
-//    SOURCE address (guide rule 21) and to the fragment reads;
+//  * both LDS images are the row-major swizzled image of csrc/tile_index.h ([rows][64] bf16, fragments by
+//    ds_read_b128);
 //  * MFMA 16x16x32 bf16 with the weight fragment as the A operand: the accumulator's lane l holds output row
 //    m = l & 15 and four CONSECUTIVE columns n = 4 (l >> 4) + r, so the epilogue stores 8 bytes per lane per tile
 //    and reads 4 consecutive bias values at once.
-//  * XCD-aware tile order: consecutive workgroups run on different XCDs (round-robin dispatch), so the tile index
-//    is remapped (bijectively, guide section 5 "XCD swizzle") so that each XCD walks a contiguous run of tiles
-//    sharing activation rows in its own L2.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+//  * XCD-aware tile order (xcd_tile of csrc/tile_index.h): each XCD walks a contiguous run of tiles sharing
+//    activation rows in its own L2.
+#include "mfma_stage.h"
 
 namespace {
 
-typedef __bf16 bf16;
-typedef __bf16 v8bf __attribute__((ext_vector_type(8)));
-typedef __bf16 v4bf __attribute__((ext_vector_type(4)));
-typedef float v4f __attribute__((ext_vector_type(4)));
-
 constexpr int BK = 64;
-
-// EPI_ADD_R: Y = X W^T + R (R bf16 [M, N], passed as `bias`): the input-gradient GEMM dX = dY W computed as an NT
-// product against a transposed weight copy, with the residual gradient folded in (mifx.ops.gemm.GradSlot)
-// EPI_GELU_BWD: Y = dZ = (X W^T) o GELU'(Z + bias) with Z the saved pre-bias product of the FFN-in GEMM (read), plus
-// per-workgroup column sums of the stored dZ (the bias gradient) into part[M / BM][N]: the FFN-out input gradient
-// and the bias-GELU backward in one pass (the unfused path writes dGELU [M, N] and reads it back)
-enum Epi { EPI_NONE = 0, EPI_BIAS = 1, EPI_BIAS_GELU = 2, EPI_ADD_R = 3, EPI_GELU_BWD = 4 };
-
-// GELU(erf) with a branch-free erf (Abramowitz & Stegun 7.1.26: |error| <= 1.5e-7, far below the bf16 output's
-// 2^-9 relative step): the library erff evaluates piecewise polynomials selected per |x|, which diverge inside a
-// wave and made the fused epilogue cost more than the separate bias_gelu pass it replaces.
-__device__ __forceinline__ float erf_fast(float x) {
-  const float ax = fabsf(x);
-  const float t = __builtin_amdgcn_rcpf(1.f + 0.3275911f * ax);
-  const float poly = t * (0.254829592f + t * (-0.284496736f + t * (1.421413741f + t * (-1.453152027f + t * 1.061405429f))));
-  const float r = 1.f - poly * __expf(-ax * ax);
-  return copysignf(r, x);
-}
-__device__ __forceinline__ float gelu_f(float x) { return 0.5f * x * (1.f + erf_fast(x * 0.70710678118654752f)); }
-__device__ __forceinline__ float gelu_grad_f(float x) {
-  return 0.5f * (1.f + erf_fast(x * 0.70710678118654752f)) + x * 0.3989422804014327f * __expf(-0.5f * x * x);
-}
-
-__device__ __forceinline__ int swz(int row, int chunk) { return chunk ^ ((row >> 1) & 7); }
 
 // OPT bit 0: raise the wave priority around each MFMA block (guide T3: the SQ then issues this wave's MFMAs ahead of
 // other waves' LDS / VMEM issue); bit 1: software-pipeline the LDS fragment reads one 32-deep k-step ahead of the
@@ -77,13 +44,11 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void gemm_nt(const bf16* __restric
 
   const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
   const int wm = w / WN, wn = w % WN;
-  // XCD-aware bijective tile order (guide: q = nwg / 8, r = nwg % 8)
-  const int nwg = gridDim.x, bid = blockIdx.x, xcd = bid % 8, q = nwg / 8, rr = nwg % 8;
-  const int tile = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + bid / 8;
-  const int nb_n = N / BN;
+  const int tile = xcd_tile(blockIdx.x, gridDim.x), nb_n = N / BN;
   const int m0 = (tile / nb_n) * BM, n0 = (tile % nb_n) * BN;
 
-  // per-lane DMA source offsets (elements) inside a K-tile, and the wave-uniform LDS destinations
+  // per-lane DMA source offsets (elements) inside a K-tile, and the wave-uniform LDS destinations (row_img_src by
+  // hand: through the helper the 6-wave 256x144 build, with its clamped last round, compiles to different code)
   int xoff[XR], woff[WR];
 #pragma unroll
   for (int i = 0; i < XR; ++i) {
@@ -101,16 +66,10 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void gemm_nt(const bf16* __restric
     const int k0 = kt * BK;
 #pragma unroll
     for (int i = 0; i < XR; ++i)
-      if ((BM * 8) % NT == 0 || i * NT + 64 * w < BM * 8)
-        __builtin_amdgcn_global_load_lds((const void*)(X + xoff[i] + k0),
-                                         (__attribute__((address_space(3))) void*)(bx + (i * NT + 64 * w) * 16), 16, 0,
-                                         0);
+      if ((BM * 8) % NT == 0 || i * NT + 64 * w < BM * 8) glds16(X + xoff[i] + k0, bx + (i * NT + 64 * w) * 16);
 #pragma unroll
     for (int i = 0; i < WR; ++i)
-      if ((BN * 8) % NT == 0 || i * NT + 64 * w < BN * 8)
-        __builtin_amdgcn_global_load_lds((const void*)(W + woff[i] + k0),
-                                         (__attribute__((address_space(3))) void*)(bw + (i * NT + 64 * w) * 16), 16, 0,
-                                         0);
+      if ((BN * 8) % NT == 0 || i * NT + 64 * w < BN * 8) glds16(W + woff[i] + k0, bw + (i * NT + 64 * w) * 16);
   };
 
   v4f acc[NR][MR];
@@ -123,15 +82,9 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void gemm_nt(const bf16* __restric
   const int KT = K / BK;
   auto frags = [&](const unsigned char* bx, const unsigned char* bw, int ks, v8bf (&wf)[NR], v8bf (&xf)[MR]) {
 #pragma unroll
-    for (int a = 0; a < NR; ++a) {
-      const int row = wn * TN + 16 * a + fr;
-      wf[a] = *(const v8bf*)(bw + row * 128 + swz(row, 4 * ks + fc) * 16);
-    }
+    for (int a = 0; a < NR; ++a) wf[a] = row_frag(bw, wn * TN + 16 * a + fr, 4 * ks + fc);
 #pragma unroll
-    for (int b = 0; b < MR; ++b) {
-      const int row = wm * TM + 16 * b + fr;
-      xf[b] = *(const v8bf*)(bx + row * 128 + swz(row, 4 * ks + fc) * 16);
-    }
+    for (int b = 0; b < MR; ++b) xf[b] = row_frag(bx, wm * TM + 16 * b + fr, 4 * ks + fc);
   };
   auto mma = [&](const v8bf (&wf)[NR], const v8bf (&xf)[MR]) {
     if (OPT & 1) __builtin_amdgcn_s_setprio(1);
@@ -145,15 +98,14 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void gemm_nt(const bf16* __restric
   constexpr bool RING3 = (OPT & 4) != 0;
   static_assert(!RING3 || ((BM * 8) % NT == 0 && (BN * 8) % NT == 0), "3-buffer ring: whole DMA rounds only");
   constexpr int G = XR + WR;  // DMAs per thread per K-tile
-  // s_waitcnt immediate (gfx9 encoding): vmcnt = G, expcnt / lgkmcnt not waited on
-  constexpr int WAIT_G = (G & 15) | (7 << 4) | (15 << 8) | ((G >> 4) << 14);
   issue(0, 0);
   if (RING3 && KT > 1) issue(1, 1);
   for (int kt = 0; kt < KT; ++kt) {
     int cur;
-    if constexpr (RING3) {
+    if constexpr (RING3) {  // ring_next<3, G> of mfma_stage.h, spelled out: its tail test `kt + NS - 2 <= KT - 1`
+                            // compiles to different code here than `kt + 1 < KT`
       if (kt + 1 < KT)
-        __builtin_amdgcn_s_waitcnt(WAIT_G);  // tile kt retired, tile kt + 1 still in flight
+        __builtin_amdgcn_s_waitcnt(vm_wait(G));  // tile kt retired, tile kt + 1 still in flight
       else
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();  // every wave's tile-kt DMAs retired; buffer (kt + 2) % 3 no longer read
@@ -301,16 +253,34 @@ int dispatch_epi(int epi, int bias_f32, const void* X, const void* W, const void
                   : launch<BM, BN, WM, WN, EPI_BIAS_GELU, bf16, OPT>(X, W, bias, Y, Z, M, N, K, st);
 }
 
+// (index = the `cfg` argument) BM x BN tile, WM x WN waves, OPT bits, GB: mifx_gemm_nt_gelu_bwd accepts the index.
+// Written once: the table mifx_gemm_configs reports and both dispatches expand this list.
+// 9..: whole-wave tilings of BERT-base's shapes at 4096 tokens on 256 CUs (256 tiles each): 256x192 (FFN-in),
+// 256x144 (QKV, 6 waves), 128x96 (attention-out / FFN-out). 19 is 10 again: OPT 7 (the three-buffer ring) has no
+// 256x144 build -- six waves do not make whole DMA rounds of that tile.
+#define NT_CONFIGS(X)                                                                                     \
+  X(256, 256, 2, 4, 0, 0) X(256, 128, 4, 2, 0, 0) X(128, 128, 2, 2, 0, 0) X(128, 256, 2, 4, 0, 0)         \
+  X(256, 256, 2, 4, 3, 0) X(128, 128, 2, 2, 3, 0) X(256, 128, 4, 2, 3, 0) X(128, 128, 2, 2, 1, 1)         \
+  X(256, 128, 2, 2, 2, 0) X(256, 192, 2, 4, 3, 1) X(256, 144, 2, 3, 3, 0) X(128, 96, 2, 2, 3, 1)          \
+  X(128, 96, 2, 2, 1, 1) X(128, 96, 2, 2, 5, 0) X(128, 128, 2, 2, 5, 0) X(256, 128, 4, 2, 5, 0)           \
+  X(128, 96, 2, 2, 7, 0) X(128, 128, 2, 2, 7, 0) X(256, 128, 4, 2, 7, 0) X(256, 144, 2, 3, 3, 0)
 struct Cfg {
   int bm, bn, opt;
 };
-// (index = the `cfg` argument; BM x BN tile, OPT bits)
-// 9..: whole-wave tilings of BERT-base's shapes at 4096 tokens on 256 CUs (256 tiles each): 256x192 (FFN-in),
-// 256x144 (QKV, 6 waves), 128x96 (attention-out / FFN-out)
-constexpr Cfg kCfgs[] = {{256, 256, 0}, {256, 128, 0}, {128, 128, 0}, {128, 256, 0}, {256, 256, 3}, {128, 128, 3},
-                         {256, 128, 3}, {128, 128, 1}, {256, 128, 2}, {256, 192, 3}, {256, 144, 3}, {128, 96, 3},
-                         {128, 96, 1}, {128, 96, 5}, {128, 128, 5}, {256, 128, 5}, {128, 96, 7}, {128, 128, 7},
-                         {256, 128, 7}, {256, 144, 7}};
+#define X(bm, bn, wm, wn, opt, gb) {bm, bn, opt},
+constexpr Cfg kCfgs[] = {NT_CONFIGS(X)};
+#undef X
+// gb_only: -2 for a configuration without the GB mark
+int run_cfg(int cfg, bool gb_only, int epi, int bias_f32, const void* X, const void* W, const void* bias, void* Y,
+            void* Z, int M, int N, int K, hipStream_t st, float* part) {
+  int i = 0;
+#define X(bm, bn, wm, wn, opt, gb) \
+  if (cfg == i++)                  \
+    return gb_only && !gb ? -2 : dispatch_epi<bm, bn, wm, wn, opt>(epi, bias_f32, X, W, bias, Y, Z, M, N, K, st, part);
+  NT_CONFIGS(X)
+#undef X
+  return -1;
+}
 
 // dst[C][R] = src[R][C] (bf16), 64 x 64 tiles through LDS: 16-byte loads along src rows, 16-byte stores along dst
 // rows (8 consecutive src rows of one column gathered from LDS). The transposed weight copy of the dX GEMMs.
@@ -373,13 +343,7 @@ int mifx_gemm_nt_gelu_bwd(int cfg, int bias_f32, const void* X, const void* W, c
   if ((uintptr_t)X % 16 || (uintptr_t)W % 16 || (uintptr_t)Y % 8 || (uintptr_t)Z % 8) return -1;
   if ((long long)M * K >= (1ll << 31) || (long long)N * K >= (1ll << 31)) return -1;
   void* z = const_cast<void*>(Z);
-  switch (cfg) {
-    case 9: return dispatch_epi<256, 192, 2, 4, 3>(EPI_GELU_BWD, bias_f32, X, W, bias, Y, z, M, N, K, st, part);
-    case 11: return dispatch_epi<128, 96, 2, 2, 3>(EPI_GELU_BWD, bias_f32, X, W, bias, Y, z, M, N, K, st, part);
-    case 12: return dispatch_epi<128, 96, 2, 2, 1>(EPI_GELU_BWD, bias_f32, X, W, bias, Y, z, M, N, K, st, part);
-    case 7: return dispatch_epi<128, 128, 2, 2, 1>(EPI_GELU_BWD, bias_f32, X, W, bias, Y, z, M, N, K, st, part);
-    default: return -2;  // configuration without a GELU-backward build
-  }
+  return run_cfg(cfg, true, EPI_GELU_BWD, bias_f32, X, W, bias, Y, z, M, N, K, st, part);
 }
 
 // n transposes in one launch: ents = device array of TrEntry {src, dst, R, C, tile0, 0} with tile0 the running sum
@@ -421,28 +385,7 @@ int mifx_gemm_nt(int cfg, int epi, int bias_f32, const void* X, const void* W, c
   if (epi == 3 && (uintptr_t)bias % 8) return -1;
   if ((uintptr_t)X % 16 || (uintptr_t)W % 16 || (uintptr_t)Y % 8 || (Z != nullptr && (uintptr_t)Z % 8)) return -1;
   if ((long long)M * K >= (1ll << 31) || (long long)N * K >= (1ll << 31)) return -1;  // 32-bit element offsets
-  switch (cfg) {
-    case 0: return dispatch_epi<256, 256, 2, 4, 0>(epi, bias_f32, X, W, bias, Y, Z, M, N, K, st);
-    case 1: return dispatch_epi<256, 128, 4, 2, 0>(epi, bias_f32, X, W, bias, Y, Z, M, N, K, st);
-    case 2: return dispatch_epi<128, 128, 2, 2, 0>(epi, bias_f32, X, W, bias, Y, Z, M, N, K, st);
-    case 3: return dispatch_epi<128, 256, 2, 4, 0>(epi, bias_f32, X, W, bias, Y, Z, M, N, K, st);
-    case 4: return dispatch_epi<256, 256, 2, 4, 3>(epi, bias_f32, X, W, bias, Y, Z, M, N, K, st);
-    case 5: return dispatch_epi<128, 128, 2, 2, 3>(epi, bias_f32, X, W, bias, Y, Z, M, N, K, st);
-    case 6: return dispatch_epi<256, 128, 4, 2, 3>(epi, bias_f32, X, W, bias, Y, Z, M, N, K, st);
-    case 7: return dispatch_epi<128, 128, 2, 2, 1>(epi, bias_f32, X, W, bias, Y, Z, M, N, K, st);
-    case 8: return dispatch_epi<256, 128, 2, 2, 2>(epi, bias_f32, X, W, bias, Y, Z, M, N, K, st);
-    case 9: return dispatch_epi<256, 192, 2, 4, 3>(epi, bias_f32, X, W, bias, Y, Z, M, N, K, st);
-    case 10: return dispatch_epi<256, 144, 2, 3, 3>(epi, bias_f32, X, W, bias, Y, Z, M, N, K, st);
-    case 11: return dispatch_epi<128, 96, 2, 2, 3>(epi, bias_f32, X, W, bias, Y, Z, M, N, K, st);
-    case 12: return dispatch_epi<128, 96, 2, 2, 1>(epi, bias_f32, X, W, bias, Y, Z, M, N, K, st);
-    case 13: return dispatch_epi<128, 96, 2, 2, 5>(epi, bias_f32, X, W, bias, Y, Z, M, N, K, st);
-    case 14: return dispatch_epi<128, 128, 2, 2, 5>(epi, bias_f32, X, W, bias, Y, Z, M, N, K, st);
-    case 15: return dispatch_epi<256, 128, 4, 2, 5>(epi, bias_f32, X, W, bias, Y, Z, M, N, K, st);
-    case 16: return dispatch_epi<128, 96, 2, 2, 7>(epi, bias_f32, X, W, bias, Y, Z, M, N, K, st);
-    case 17: return dispatch_epi<128, 128, 2, 2, 7>(epi, bias_f32, X, W, bias, Y, Z, M, N, K, st);
-    case 18: return dispatch_epi<256, 128, 4, 2, 7>(epi, bias_f32, X, W, bias, Y, Z, M, N, K, st);
-    default: return dispatch_epi<256, 144, 2, 3, 3>(epi, bias_f32, X, W, bias, Y, Z, M, N, K, st);
-  }
+  return run_cfg(cfg, false, epi, bias_f32, X, W, bias, Y, Z, M, N, K, st, nullptr);
 }
 
 }  // extern "C"

@@ -21,18 +21,15 @@
 //    behind waves 0-3 (the guide's stagger): on each SIMD one wave runs its MFMA block while its partner issues LDS
 //    reads and DMAs, then they swap. `s_setprio(1)` around every MFMA block keeps the compiler from moving MFMAs
 //    across the barriers (guide T5).
-//  * LDS rows are 128 bytes with the 16-byte chunk index XOR-swizzled by (row >> 1) & 7 (conflict-free
-//    ds_read_b128 of the 16 rows of a fragment); the DMA destination is lane-linear, so the swizzle is applied to each
-//    lane's SOURCE address (guide rule 21) and to the fragment reads.
+//  * the half-tiles are the row-major swizzled images of csrc/tile_index.h (128-byte rows, conflict-free
+//    ds_read_b128 of the 16 rows of a fragment).
 //  * the weight fragment is the MFMA's A operand, so a lane's accumulator holds one output row and four CONSECUTIVE
 //    columns (8-byte stores, 4 consecutive bias values).
-//  * XCD-aware bijective tile order (consecutive workgroups land on different XCDs; each XCD walks a contiguous run of
-//    tiles that share X row panels in its L2).
+//  * XCD-aware tile order (xcd_tile of csrc/tile_index.h: each XCD walks a run of tiles that share X row panels).
 //
 // TN layout (weight gradients, dW = dY^T X: both operands token-major, the reduction is their ROW index): the same
-// schedule with half-tiles of 64 tokens x BM/2 (BN/2) columns; an LDS row is a token's 256 (or 128) bytes with its
-// 16-byte chunks rotated per token (conflict-free transposed reads, csrc/gemm_tn.hip's rot<>), and the MFMA fragments
-// (8 consecutive tokens of one column per lane) come from two ds_read_b64_tr_b16. GROUPED launch: a table of up to
+// schedule with half-tiles of 64 tokens x BM/2 (BN/2) columns, the token-major rotated images of csrc/tile_index.h (an
+// LDS row is a token's 256, 128 or 64 bytes; MFMA fragments from two ds_read_b64_tr_b16). GROUPED launch: a table of up to
 // 64 problems in the kernel arguments, each workgroup finds its (problem, tile) by binary search over the per-problem
 // first-tile indices. A BERT step's 48 weight-gradient products are off the backward's critical path, so they are
 // deferred to the end of the backward and run as ONE launch of full 256 x 256 tiles over the whole 4096-token
@@ -43,57 +40,17 @@
 // (dX = dY W + residual gradient) / GELU backward dZ = (X W^T) o GELU'(Z + bias) with per-tile column sums (the FFN-out
 // input gradient fused with FFN-in's bias-GELU backward) / per-tile column sum and sum of squares of the stored bf16
 // output (the BatchNorm statistics of a 1x1 convolution, folded into the GEMM that produces it).
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
 #include <type_traits>
 
-namespace {
+#include "mfma_stage.h"
 
-typedef __bf16 bf16;
-typedef __bf16 v8bf __attribute__((ext_vector_type(8)));
-typedef __bf16 v4bf __attribute__((ext_vector_type(4)));
-typedef float v4f __attribute__((ext_vector_type(4)));
+namespace {
 
 constexpr int BK = 64;
 constexpr int NT = 512;
 
-enum Epi { EPI_NONE = 0, EPI_BIAS = 1, EPI_BIAS_GELU = 2, EPI_ADD_R = 3, EPI_GELU_BWD = 4, EPI_STATS = 5,
-           EPI_ADD_STATS = 6, EPI_F32 = 7, EPI_BNBWD = 8, EPI_ADD_BNBWD = 9 };
-
-__device__ __forceinline__ float erf_fast(float x) {  // Abramowitz & Stegun 7.1.26, |error| <= 1.5e-7, branch-free
-  const float ax = fabsf(x);
-  const float t = __builtin_amdgcn_rcpf(1.f + 0.3275911f * ax);
-  const float poly = t * (0.254829592f + t * (-0.284496736f + t * (1.421413741f + t * (-1.453152027f + t * 1.061405429f))));
-  return copysignf(1.f - poly * __expf(-ax * ax), x);
-}
-__device__ __forceinline__ float gelu_f(float x) { return 0.5f * x * (1.f + erf_fast(x * 0.70710678118654752f)); }
-__device__ __forceinline__ float gelu_grad_f(float x) {
-  return 0.5f * (1.f + erf_fast(x * 0.70710678118654752f)) + x * 0.3989422804014327f * __expf(-0.5f * x * x);
-}
-
-__device__ __forceinline__ int swz(int row, int chunk) { return chunk ^ ((row >> 1) & 7); }
-
-typedef short v4s __attribute__((ext_vector_type(4)));
-typedef short v8s __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) v4s lds_v4s;
-
-// TN images: chunk rotation of token row t for a row of CPR 16-byte chunks (every 32-lane half of a transposed
-// fragment read touches 64 distinct banks; tools/lds_banks_tn.py)
-template <int CPR>
-__device__ __forceinline__ int rot(int t) {
-  static_assert(CPR == 4 || CPR == 8 || CPR == 16, "chunks per token row");
-  if constexpr (CPR == 4) return 2 * ((t >> 3) & 1);  // 64-byte rows (narrow tiles): the 16-lane groups of a half
-                                                      // read tokens 8 apart, shifted 8 banks
-  if constexpr (CPR == 8) return ((t & 3) + 4 * ((t >> 3) & 3)) & 7;
-  return (2 * (t & 3) + 8 * ((t >> 3) & 3)) & 15;
-}
-__device__ __forceinline__ v8bf tr_frag(const unsigned char* p1, const unsigned char* p2) {
-  const v4s a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)p1);
-  const v4s b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)p2);
-  const v8s r = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-  return __builtin_bit_cast(v8bf, r);
-}
+// (0-4: mfma_stage.h)
+enum Epi8 { EPI_STATS = 5, EPI_ADD_STATS = 6, EPI_F32 = 7, EPI_BNBWD = 8, EPI_ADD_BNBWD = 9 };
 
 // Implicit-GEMM 3x3 convolution over NHWC activations (ResNet-50's bottleneck conv2, BASELINE config 5): input
 // [Nb][H][W][C] (C a power of two >= 64), output pixels [Nb][OH][OW], taps (r, s) in 0..2, stride / pad. The GEMM's
@@ -151,9 +108,6 @@ struct Group {
               // uniform 256 x 256 tiles only)
 };
 
-// s_waitcnt immediate (gfx9 encoding): vmcnt = n, expcnt / lgkmcnt not waited on
-constexpr int vm_wait(int n) { return (n & 15) | (7 << 4) | (15 << 8) | ((n >> 4) << 14); }
-
 // The body: one BM x BN tile of Y = X W^T (NT: X [M, K], W [N, K] row-major) or of C = A^T B (TN: A [K, M],
 // B [K, N] row-major; X := A, W := B, "K" = tokens), m0 / n0 its origin. CV: implicit-convolution operand (above);
 // tok0: the first token of this item's chunk (CV 2: B is then the whole conv input, gathered by pixel index).
@@ -209,28 +163,18 @@ __device__ __forceinline__ void gemm8_tile(const bf16* __restrict__ X, const bf1
 #pragma unroll
   for (int i = 0; i < XR; ++i) {
     const int qq = ADUP ? tid % ADMA : i * NT + tid;
-    if constexpr (TN) {
-      const int t = qq / CPA, pc = qq % CPA;  // token row, physical chunk
-      int c = pc - rot<CPA>(t);
-      c = c < 0 ? c + CPA : c;
-      aoff[i] = t * M + m0 + 8 * c;
-    } else {
-      const int row = qq >> 3;
-      aoff[i] = (m0 + row) * K + 8 * swz(row, qq & 7);
-    }
+    if constexpr (TN)
+      aoff[i] = tok_img_src<CPA>(qq / CPA, qq % CPA, M, m0);
+    else
+      aoff[i] = row_img_src(qq >> 3, qq & 7, m0, K);
   }
 #pragma unroll
   for (int i = 0; i < WR; ++i) {
     const int qq = WDUP ? tid % BDMA : i * NT + tid;
-    if constexpr (TN) {
-      const int t = qq / CPB, pc = qq % CPB;
-      int c = pc - rot<CPB>(t);
-      c = c < 0 ? c + CPB : c;
-      boff[i] = t * N + n0 + 8 * c;
-    } else {
-      const int row = qq >> 3;
-      boff[i] = (n0 + row) * K + 8 * swz(row, qq & 7);
-    }
+    if constexpr (TN)
+      boff[i] = tok_img_src<CPB>(qq / CPB, qq % CPB, N, n0);
+    else
+      boff[i] = row_img_src(qq >> 3, qq & 7, n0, K);
   }
   // CV 1: each A DMA row's output pixel, decoded once: image base pixel, top-left input coordinate, swizzled chunk
   int cpix[CV == 1 ? 2 : 1][CV == 1 ? XR : 1], cih[CV == 1 ? 2 : 1][CV == 1 ? XR : 1],
@@ -255,11 +199,9 @@ __device__ __forceinline__ void gemm8_tile(const bf16* __restrict__ X, const bf1
   if constexpr (CV == 2) {
 #pragma unroll
     for (int i = 0; i < WR; ++i) {
-      const int qq = WDUP ? tid % BDMA : i * NT + tid, t = qq / CPB, pc = qq % CPB;  // (narrow: as boff above)
-      int c = pc - rot<CPB>(t);
-      c = c < 0 ? c + CPB : c;
+      const int qq = WDUP ? tid % BDMA : i * NT + tid, t = qq / CPB;  // (narrow: as boff above)
       btok[i] = t;
-      bcol[i] = 8 * c;
+      bcol[i] = tok_img_src<CPB>(t, qq % CPB, 0, 0);
     }
   }
   // AX: table loads (before every DMA: retired by the prologue's counted wait)
@@ -291,9 +233,7 @@ __device__ __forceinline__ void gemm8_tile(const bf16* __restrict__ X, const bf1
         const int ih = cih[hh][i] + r, iw = ciw[hh][i] + sx;
         const bool ok = (unsigned)ih < (unsigned)geo.H && (unsigned)iw < (unsigned)geo.W;
         const bf16* src = ok ? X + ((size_t)(cpix[hh][i] + ih * geo.W + iw) << geo.cshift) + c0 + cch[i] : g_zero_page;
-        __builtin_amdgcn_global_load_lds((const void*)src,
-                                         (__attribute__((address_space(3))) void*)(dst + (i * NT + 64 * w) * 16), 16,
-                                         0, 0);
+        glds16(src, (dst + (i * NT + 64 * w) * 16));
       }
       return;
     }
@@ -311,9 +251,7 @@ __device__ __forceinline__ void gemm8_tile(const bf16* __restrict__ X, const bf1
             ok ? W + ((size_t)((nb * geo.H + ih) * geo.W + iw) << geo.cshift) + c0 + bcol[i] : g_zero_page;
         // (narrow B half: waves 4-7 re-issue waves 0-3's DMAs -- same token rows, same LDS bytes -- not the next
         // K-tile's rows into the A half behind it)
-        __builtin_amdgcn_global_load_lds(
-            (const void*)src,
-            (__attribute__((address_space(3))) void*)(dst + (WDUP ? (64 * w) % BDMA : i * NT + 64 * w) * 16), 16, 0, 0);
+        glds16(src, (dst + (WDUP ? (64 * w) % BDMA : i * NT + 64 * w) * 16));
       }
       return;
     }
@@ -322,10 +260,7 @@ __device__ __forceinline__ void gemm8_tile(const bf16* __restrict__ X, const bf1
       const bf16* src = TN ? X + (size_t)k0 * M + (h == 2 ? HA : 0) : X + (h == 2 ? HA * K : 0) + k0;
 #pragma unroll
       for (int i = 0; i < XR; ++i)
-        __builtin_amdgcn_global_load_lds(
-            (const void*)(src + aoff[i]),
-            (__attribute__((address_space(3))) void*)(dst + (ADUP ? (64 * w) % ADMA : i * NT + 64 * w) * 16), 16, 0,
-            0);
+        glds16(src + aoff[i], (dst + (ADUP ? (64 * w) % ADMA : i * NT + 64 * w) * 16));
     } else {
       unsigned char* dst = buf + (h == 1 ? OFF_B0 : OFF_B1);
       const bf16* src = TN ? W + (size_t)k0 * N + (h == 3 ? HB : 0) : W + (h == 3 ? HB * K : 0) + k0;
@@ -334,8 +269,7 @@ __device__ __forceinline__ void gemm8_tile(const bf16* __restrict__ X, const bf1
         // (AX TN: the duplicate DMAs of a transformed narrow half land in the scratch area after the table)
         unsigned char* d = (AX && TN && WDUP && 64 * w >= BDMA) ? lds + 2 * BUF + 4 * TABF + (64 * w - BDMA) * 16
                                                               : dst + (WDUP ? (64 * w) % BDMA : i * NT + 64 * w) * 16;
-        __builtin_amdgcn_global_load_lds((const void*)(src + boff[i]), (__attribute__((address_space(3))) void*)d,
-                                         16, 0, 0);
+        glds16(src + boff[i], d);
       }
     }
   };
@@ -355,6 +289,8 @@ __device__ __forceinline__ void gemm8_tile(const bf16* __restrict__ X, const bf1
   // TN fragment geometry: lane (r = lane & 15 -> token quad q = r >> 2, column quad p = r & 3; h = lane >> 4): the
   // two transposed reads deliver tokens 32 ks + 8 h + q and + 4 of column 16 f + 4 p .. (4 consecutive per read)
   const int tq = fr >> 2, tp = fr & 3;
+  // (tok_frag of mfma_stage.h by hand, the chunk count a run-time argument: through the helper, or with the count
+  // a template argument, the grouped kernel compiles to different code)
   auto tn_frag = [&](const unsigned char* half, int cpr_rot, int col0, int ks) -> v8bf {
     const int t1 = 32 * ks + 8 * fc + tq, t2 = t1 + 4;
     const int c = col0 / 8 + (tp >> 1);
@@ -362,7 +298,8 @@ __device__ __forceinline__ void gemm8_tile(const bf16* __restrict__ X, const bf1
         s2 = c + (cpr_rot == 16 ? rot<16>(t2) : cpr_rot == 8 ? rot<8>(t2) : rot<4>(t2));
     s1 = s1 >= cpr_rot ? s1 - cpr_rot : s1;
     s2 = s2 >= cpr_rot ? s2 - cpr_rot : s2;
-    return tr_frag(half + (t1 * cpr_rot + s1) * 16 + 8 * (tp & 1), half + (t2 * cpr_rot + s2) * 16 + 8 * (tp & 1));
+    return cat8(tr_read(half + (t1 * cpr_rot + s1) * 16 + 8 * (tp & 1)),
+                tr_read(half + (t2 * cpr_rot + s2) * 16 + 8 * (tp & 1)));
   };
   // AX commit: transform staged half x (0: A0 / B0, 1: A1 / B1) of K-tile t and write it to its LDS slots
   auto commit = [&](int x, int t) {
@@ -378,10 +315,7 @@ __device__ __forceinline__ void gemm8_tile(const bf16* __restrict__ X, const bf1
       } else {
         if (WDUP && tid >= BDMA) continue;  // (its duplicate DMAs went to the scratch area)
         slot = WDUP ? tid : i * NT + tid;
-        const int tr = slot / CPB, pc = slot % CPB;
-        int cc = pc - rot<CPB>(tr);
-        cc = cc < 0 ? cc + CPB : cc;
-        c = x * HB + 8 * cc;
+        c = tok_img_src<CPB>(slot / CPB, slot % CPB, 0, x * HB);
       }
       const int L = TN ? BN : K;
       const float4 s0 = *(const float4*)(tab + c), s1 = *(const float4*)(tab + c + 4);
@@ -405,7 +339,7 @@ __device__ __forceinline__ void gemm8_tile(const bf16* __restrict__ X, const bf1
         if constexpr (TN)
           r[f][ks] = tn_frag(half, CPA, wm * RPW + 16 * f, ks);
         else
-          r[f][ks] = *(const v8bf*)(half + row * 128 + swz(row, 4 * ks + fc) * 16);
+          r[f][ks] = row_frag(half, row, 4 * ks + fc);
       }
     }
     (void)k0;
@@ -419,7 +353,7 @@ __device__ __forceinline__ void gemm8_tile(const bf16* __restrict__ X, const bf1
         if constexpr (TN)
           rb[f][ks] = tn_frag(half, CPB, wn * CPW + 16 * f, ks);
         else
-          rb[f][ks] = *(const v8bf*)(half + row * 128 + swz(row, 4 * ks + fc) * 16);
+          rb[f][ks] = row_frag(half, row, 4 * ks + fc);
       }
     }
     (void)hb;
@@ -782,18 +716,13 @@ __device__ __forceinline__ void gemm8_tile(const bf16* __restrict__ X, const bf1
   }
 }
 
-__device__ __forceinline__ int xcd_tile() {  // bijective XCD-aware remap of blockIdx.x (guide section 5)
-  const int nwg = gridDim.x, bid = blockIdx.x, xcd = bid % 8, q = nwg / 8, rr = nwg % 8;
-  return (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + bid / 8;
-}
-
 template <int BM, int BN, int EPI, typename P>
 __global__ __launch_bounds__(NT, 1) void gemm8_nt(const bf16* __restrict__ X, const bf16* __restrict__ W,
                                                   const P* __restrict__ bias, bf16* __restrict__ Y,
                                                   bf16* __restrict__ Z, int M, int N, int K,
                                                   float* __restrict__ part, const bf16* __restrict__ R2) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-  const int tile = xcd_tile(), nb_n = N / BN;
+  const int tile = xcd_tile(blockIdx.x, gridDim.x), nb_n = N / BN;
   gemm8_tile<BM, BN, EPI, P, false>(X, W, bias, Y, Z, M, N, K, part, (tile / nb_n) * BM, (tile % nb_n) * BN, lds,
                                     Geo{}, 0, R2);
 }
@@ -806,7 +735,7 @@ __global__ __launch_bounds__(NT, 1) void gemm8_nt_bnx(const bf16* __restrict__ X
                                                       int N, int K, float* __restrict__ part,
                                                       const float* __restrict__ ax) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-  const int tile = xcd_tile(), nb_n = N / BN;
+  const int tile = xcd_tile(blockIdx.x, gridDim.x), nb_n = N / BN;
   gemm8_tile<BM, BN, EPI, bf16, false, 0, true>(X, W, bias, Y, nullptr, M, N, K, part, (tile / nb_n) * BM,
                                                 (tile % nb_n) * BN, lds, Geo{}, 0, nullptr, ax);
 }
@@ -818,7 +747,7 @@ __global__ __launch_bounds__(NT, 1) void gemm8_conv(const bf16* __restrict__ X, 
                                                     bf16* __restrict__ Z, int M, int N, int K,
                                                     float* __restrict__ part, const Geo geo) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-  const int tile = xcd_tile(), nb_n = N / BN;
+  const int tile = xcd_tile(blockIdx.x, gridDim.x), nb_n = N / BN;
   gemm8_tile<BM, BN, EPI, P, false, 1>(X, W, bias, Y, Z, M, N, K, part, (tile / nb_n) * BM, (tile % nb_n) * BN, lds,
                                        geo);
 }
@@ -832,9 +761,8 @@ __device__ __forceinline__ void grouped_item(const Prob& p, int item, int quad, 
             bn = (p.flags & TILE128) ? BN / 2 : (p.flags & NARROW_N) ? 64 : BN;
   const int nb_m = p.M / bm, nb_n = p.N / bn, tiles = nb_m * nb_n;
   const int sp = item / tiles, t = item - sp * tiles;
-  const int per_group = GM * nb_n, grp = t / per_group, first_m = grp * GM, gsz = min(GM, nb_m - first_m);
-  const int wi = t - grp * per_group;
-  const int m0 = (first_m + wi % gsz) * bm, n0 = (wi / gsz) * bn;
+  const TileMN tl = grouped_tile(t, nb_m, nb_n);
+  const int m0 = tl.m * bm, n0 = tl.n * bn;
   const int t0 = sp * p.chunk, len = min(p.chunk, p.T - t0);
   const bf16* A = p.A + (size_t)t0 * p.M;
   if (p.flags & CONV) {  // (F32 only; the B rows are gathered from the whole input by pixel index t0 + ...)
@@ -891,8 +819,7 @@ __global__ __launch_bounds__(NT, 1) void gemm8_tn_grouped(const Group g) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   int item, quad = -1;
   if ((int)blockIdx.x < g.n_big) {  // bijective XCD-aware remap over the full-size items
-    const int nwg = g.n_big, bid = blockIdx.x, xcd = bid % 8, q = nwg / 8, rr = nwg % 8;
-    item = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + bid / 8;
+    item = xcd_tile(blockIdx.x, g.n_big);
   } else {
     const int sidx = blockIdx.x - g.n_big;
     item = g.n_big + sidx / 4;
@@ -1054,10 +981,25 @@ int dispatch(int epi, int bias_f32, const void* X, const void* W, const void* bi
   return -1;
 }
 
+// (index = the `cfg` argument) BM x BN tile. Written once: the table mifx_gemm8_configs reports and with_tile, through
+// which every entry point dispatches, both expand this list.
+#define GEMM8_CONFIGS(X) X(256, 256) X(256, 128) X(128, 256) X(128, 128) X(256, 64) X(128, 64)
 struct Cfg {
   int bm, bn;
 };
-constexpr Cfg kCfgs[] = {{256, 256}, {256, 128}, {128, 256}, {128, 128}, {256, 64}, {128, 64}};
+#define X(bm, bn) {bm, bn},
+constexpr Cfg kCfgs[] = {GEMM8_CONFIGS(X)};
+#undef X
+// f(BM, BN) with the tile of configuration cfg as integral constants
+template <typename F>
+int with_tile(int cfg, F&& f) {
+  int i = 0;
+#define X(bm, bn) \
+  if (cfg == i++) return f(std::integral_constant<int, bm>{}, std::integral_constant<int, bn>{});
+  GEMM8_CONFIGS(X)
+#undef X
+  return -1;
+}
 
 }  // namespace
 
@@ -1096,14 +1038,9 @@ int mifx_gemm8_nt(int cfg, int epi, int bias_f32, const void* X, const void* W, 
   if ((uintptr_t)X % 16 || (uintptr_t)W % 16 || (uintptr_t)Y % 16 || (Z != nullptr && (uintptr_t)Z % 8)) return -1;
   if ((epi == 3 || epi == 6) && (uintptr_t)bias % 16) return -1;
   if ((long long)M * K >= (1ll << 31) || (long long)N * K >= (1ll << 31)) return -1;  // 32-bit element offsets
-  switch (cfg) {
-    case 0: return dispatch<256, 256>(epi, bias_f32, X, W, bias, Y, Z, M, N, K, part, st, R2);
-    case 1: return dispatch<256, 128>(epi, bias_f32, X, W, bias, Y, Z, M, N, K, part, st, R2);
-    case 2: return dispatch<128, 256>(epi, bias_f32, X, W, bias, Y, Z, M, N, K, part, st, R2);
-    case 3: return dispatch<128, 128>(epi, bias_f32, X, W, bias, Y, Z, M, N, K, part, st, R2);
-    case 4: return dispatch<256, 64>(epi, bias_f32, X, W, bias, Y, Z, M, N, K, part, st, R2);
-    default: return dispatch<128, 64>(epi, bias_f32, X, W, bias, Y, Z, M, N, K, part, st, R2);
-  }
+  return with_tile(cfg, [&](auto bm, auto bn) {
+    return dispatch<bm(), bn()>(epi, bias_f32, X, W, bias, Y, Z, M, N, K, part, st, R2);
+  });
 }
 
 // Y[M, N] = relu(X scale + shift) . W[N, K]^T (+ R: epi 6) with ax = fp32 [scale[K], shift[K]] (a BatchNorm's
@@ -1122,14 +1059,8 @@ int mifx_gemm8_nt_bnx(int cfg, int epi, const void* X, const void* W, const void
   if (epi == 6 && (bias == nullptr || (uintptr_t)bias % 16)) return -1;
   if ((uintptr_t)X % 16 || (uintptr_t)W % 16 || (uintptr_t)Y % 16 || (uintptr_t)ax % 16) return -1;
   if ((long long)M * K >= (1ll << 31) || (long long)N * K >= (1ll << 31)) return -1;
-  switch (cfg) {
-    case 0: return dispatch_bnx<256, 256>(epi, X, W, bias, Y, M, N, K, part, ax, st);
-    case 1: return dispatch_bnx<256, 128>(epi, X, W, bias, Y, M, N, K, part, ax, st);
-    case 2: return dispatch_bnx<128, 256>(epi, X, W, bias, Y, M, N, K, part, ax, st);
-    case 3: return dispatch_bnx<128, 128>(epi, X, W, bias, Y, M, N, K, part, ax, st);
-    case 4: return dispatch_bnx<256, 64>(epi, X, W, bias, Y, M, N, K, part, ax, st);
-    default: return dispatch_bnx<128, 64>(epi, X, W, bias, Y, M, N, K, part, ax, st);
-  }
+  return with_tile(
+      cfg, [&](auto bm, auto bn) { return dispatch_bnx<bm(), bn()>(epi, X, W, bias, Y, M, N, K, part, ax, st); });
 }
 
 // 3x3 convolution as an implicit GEMM (see Geo): x bf16 NHWC [Nb][H][W][C], w bf16 [N][3][3][C] (channels_last
@@ -1150,14 +1081,8 @@ int mifx_gemm8_conv3x3(int cfg, int epi, const void* x, const void* w, const voi
   if (epi == 8 && (bias == nullptr || Z == nullptr || (uintptr_t)bias % 16)) return -1;
   if ((uintptr_t)x % 16 || (uintptr_t)w % 16 || (uintptr_t)y % 16) return -1;
   const Geo g = make_geo(H, W, C, OH, OW, stride, pad);
-  switch (cfg) {
-    case 0: return dispatch_conv<256, 256>(epi, x, w, bias, y, Z, M, N, K, part, g, st);
-    case 1: return dispatch_conv<256, 128>(epi, x, w, bias, y, Z, M, N, K, part, g, st);
-    case 2: return dispatch_conv<128, 256>(epi, x, w, bias, y, Z, M, N, K, part, g, st);
-    case 3: return dispatch_conv<128, 128>(epi, x, w, bias, y, Z, M, N, K, part, g, st);
-    case 4: return dispatch_conv<256, 64>(epi, x, w, bias, y, Z, M, N, K, part, g, st);
-    default: return dispatch_conv<128, 64>(epi, x, w, bias, y, Z, M, N, K, part, g, st);
-  }
+  return with_tile(
+      cfg, [&](auto bm, auto bn) { return dispatch_conv<bm(), bn()>(epi, x, w, bias, y, Z, M, N, K, part, g, st); });
 }
 
 // The device-side geometry record of a convolution for mifx_gemm8_tn_grouped's CONV problems: a 3x3 pad-`pad`
@@ -1187,14 +1112,9 @@ int mifx_gemm8_conv1x1s(int cfg, int epi, const void* x, const void* w, void* y,
   if (epi == 5 && part == nullptr) return -1;
   if ((uintptr_t)x % 16 || (uintptr_t)w % 16 || (uintptr_t)y % 16) return -1;
   const Geo g = make_geo(H, W, C, OH, OW, stride, 1, 4, 1);
-  switch (cfg) {
-    case 0: return dispatch_conv<256, 256>(epi, x, w, nullptr, y, nullptr, M, N, C, part, g, st);
-    case 1: return dispatch_conv<256, 128>(epi, x, w, nullptr, y, nullptr, M, N, C, part, g, st);
-    case 2: return dispatch_conv<128, 256>(epi, x, w, nullptr, y, nullptr, M, N, C, part, g, st);
-    case 3: return dispatch_conv<128, 128>(epi, x, w, nullptr, y, nullptr, M, N, C, part, g, st);
-    case 4: return dispatch_conv<256, 64>(epi, x, w, nullptr, y, nullptr, M, N, C, part, g, st);
-    default: return dispatch_conv<128, 64>(epi, x, w, nullptr, y, nullptr, M, N, C, part, g, st);
-  }
+  return with_tile(cfg, [&](auto bm, auto bn) {
+    return dispatch_conv<bm(), bn()>(epi, x, w, nullptr, y, nullptr, M, N, C, part, g, st);
+  });
 }
 
 // Grouped TN GEMM: for i < n, C_i[M_i, N_i] = A_i[T_i, M_i]^T B_i[T_i, N_i] (bf16 row-major operands, fp32

@@ -15,6 +15,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "tile_index.h"
+
 namespace {
 
 constexpr int BM = 64, BN = 64, BK = 16, LDP = 64 + 4, NT = 256;
@@ -29,8 +31,7 @@ __global__ __launch_bounds__(NT) void gemm_f32_nn(const float* __restrict__ A, c
   const int nb_n = (N + BN - 1) / BN;
   // XCD-aware tile order: the 8 workgroups dispatched together land on 8 XCDs; give each XCD a contiguous run of
   // tiles (shared A rows / B columns in its L2)
-  const int nwg = gridDim.x, bid = blockIdx.x, xcd = bid % 8, q = nwg / 8, rr = nwg % 8;
-  const int tile = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + bid / 8;
+  const int tile = xcd_tile(blockIdx.x, gridDim.x);
   const int m0 = (tile / nb_n) * BM, n0 = (tile % nb_n) * BN;
   const int wm = w >> 1, wn = w & 1;
 

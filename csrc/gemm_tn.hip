@@ -12,53 +12,18 @@
 //  * 4 waves (2 x 2), each owning a (BM/2) x (BN/2) block of 16 x 16 MFMA tiles (mfma_f32_16x16x32_bf16);
 //  * per 64-token K-tile every lane issues 16-byte global->LDS DMA loads (no VGPR round trip) of A rows [64][BM] and
 //    B rows [64][BN] into a ring of NS buffers (~144 KB), NS - 1 tiles ahead of the MFMAs; one barrier per K-tile;
-//  * both operands sit in LDS token-major, so the MFMA fragments (8 consecutive tokens per lane) are read with
-//    ds_read_b64_tr_b16: a 16-lane group supplies 4 token rows x 16 columns, each lane receives one column's 4
-//    tokens; two reads (+4 rows) make the 8-token fragment. The 16-byte chunks of row t sit rotated by rot(t)
-//    inside their row (applied to each lane's DMA SOURCE address, as DMA destinations are lane-linear): with the
-//    rotation below every 32-lane half of every fragment read touches 64 distinct banks (checked by
-//    tools/lds_banks_tn.py for each chunk count);
+//  * both operands sit in LDS as the token-major rotated image of csrc/tile_index.h, so the MFMA fragments (8
+//    consecutive tokens per lane) are pairs of ds_read_b64_tr_b16 transposed reads, conflict-free for every tile width
+//    here (tests/test_tile_index.py);
 //  * the MFMA takes the B fragment as its A operand, so the accumulator lane holds C[m][n .. n + 3]: 8-byte bf16
 //    stores (or 16-byte fp32 partial stores) in the epilogue;
-//  * XCD-aware tile order: consecutive workgroups run on different XCDs (round-robin dispatch), so the tile index is
-//    remapped bijectively so that each XCD walks a contiguous run of tiles, grouped 4 m-blocks wide, in its own L2.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+//  * XCD-aware tile order (xcd_tile, then grouped_tile of csrc/tile_index.h): each XCD walks a contiguous run of
+//    tiles, grouped 4 m-blocks wide, so it re-reads few A and B strips per K-tile from its own L2.
+#include "mfma_stage.h"
 
 namespace {
 
-typedef __bf16 bf16;
-typedef __bf16 v8bf __attribute__((ext_vector_type(8)));
-typedef __bf16 v4bf __attribute__((ext_vector_type(4)));
-typedef short v4s __attribute__((ext_vector_type(4)));
-typedef short v8s __attribute__((ext_vector_type(8)));
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) v4s lds_v4s;
-
 constexpr int BK = 64;
-
-// chunk rotation of token row t for a row of CPA 16-byte chunks (conflict-free transposed fragment reads)
-template <int CPA>
-__device__ __forceinline__ int rot(int t) {
-  static_assert(CPA == 8 || CPA == 12 || CPA == 16 || CPA == 24, "chunks per row");
-  if constexpr (CPA == 8) return ((t & 3) + 4 * ((t >> 3) & 3)) & 7;
-  if constexpr (CPA == 12) return (2 * ((t >> 3) & 3)) % 12;
-  if constexpr (CPA == 24) return (6 * (t & 3) + 6 * ((t >> 3) & 3)) % 24;
-  return (2 * (t & 3) + 8 * ((t >> 3) & 3)) & 15;
-}
-template <int CPA>
-__device__ __forceinline__ int slot_of(int t, int c) {  // physical chunk of logical chunk c in row t
-  const int p = c + rot<CPA>(t);
-  return p >= CPA ? p - CPA : p;
-}
-
-__device__ __forceinline__ v4s tr_read(const unsigned char* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)(p));
-}
-__device__ __forceinline__ v8bf cat8(v4s a, v4s b) {
-  v8s r = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-  return __builtin_bit_cast(v8bf, r);
-}
 
 // OUT_F32: store the fp32 partial of split blockIdx.y at P + blockIdx.y * M * N (else bf16 C directly).
 // OPT bit 0: raise the wave priority around each MFMA block (bit 1 in the config table: the 8-wave gemm_tn_k2).
@@ -77,32 +42,21 @@ __global__ __launch_bounds__(256) void gemm_tn(const bf16* __restrict__ A, const
 
   const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
   const int wm = w / WN, wn = w % WN;
-  const int nwg = gridDim.x, bid = blockIdx.x, xcd = bid % 8, q8 = nwg / 8, r8 = nwg % 8;
-  const int tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + bid / 8;
-  // grouped order: runs of GM m-blocks x all n-blocks, m fastest, so an XCD's run of consecutive tiles covers a
-  // GM x (run / GM) block of the output and re-reads few A and B strips per K-tile from its L2
-  constexpr int GM = 4;
-  const int nb_m = M / BM, nb_n = N / BN, per_group = GM * nb_n;
-  const int group = tile / per_group, first_m = group * GM, gsz = min(GM, nb_m - first_m);
-  const int wi = tile - group * per_group;
-  const int m0 = (first_m + wi % gsz) * BM, n0 = (wi / gsz) * BN;
+  const TileMN tl = grouped_tile(xcd_tile(blockIdx.x, gridDim.x), M / BM, N / BN);
+  const int m0 = tl.m * BM, n0 = tl.n * BN;
   const int t_begin = blockIdx.y * tps, KT = tps / BK;
 
   // per-lane DMA source offsets (elements, relative to the K-tile's first token row)
   int aoff[AR], boff[BR];
 #pragma unroll
   for (int i = 0; i < AR; ++i) {
-    const int s = min(i * NT + tid, BK * CPA - 1), t = s / CPA, p = s % CPA;
-    int c = p - rot<CPA>(t);
-    c = c < 0 ? c + CPA : c;
-    aoff[i] = t * M + m0 + 8 * c;
+    const int s = min(i * NT + tid, BK * CPA - 1);
+    aoff[i] = tok_img_src<CPA>(s / CPA, s % CPA, M, m0);
   }
 #pragma unroll
   for (int i = 0; i < BR; ++i) {
-    const int s = min(i * NT + tid, BK * CPB - 1), t = s / CPB, p = s % CPB;
-    int c = p - rot<CPB>(t);
-    c = c < 0 ? c + CPB : c;
-    boff[i] = t * N + n0 + 8 * c;
+    const int s = min(i * NT + tid, BK * CPB - 1);
+    boff[i] = tok_img_src<CPB>(s / CPB, s % CPB, N, n0);
   }
   auto issue = [&](int kt, int buf) {
     unsigned char* ba = lds + buf * BUF;
@@ -112,16 +66,10 @@ __global__ __launch_bounds__(256) void gemm_tn(const bf16* __restrict__ A, const
     const bf16* b0 = B + t0 * N;
 #pragma unroll
     for (int i = 0; i < AR; ++i)
-      if ((BK * CPA) % NT == 0 || i * NT + 64 * w < BK * CPA)
-        __builtin_amdgcn_global_load_lds((const void*)(a0 + aoff[i]),
-                                         (__attribute__((address_space(3))) void*)(ba + (i * NT + 64 * w) * 16), 16, 0,
-                                         0);
+      if ((BK * CPA) % NT == 0 || i * NT + 64 * w < BK * CPA) glds16(a0 + aoff[i], ba + (i * NT + 64 * w) * 16);
 #pragma unroll
     for (int i = 0; i < BR; ++i)
-      if ((BK * CPB) % NT == 0 || i * NT + 64 * w < BK * CPB)
-        __builtin_amdgcn_global_load_lds((const void*)(b0 + boff[i]),
-                                         (__attribute__((address_space(3))) void*)(bb + (i * NT + 64 * w) * 16), 16, 0,
-                                         0);
+      if ((BK * CPB) % NT == 0 || i * NT + 64 * w < BK * CPB) glds16(b0 + boff[i], bb + (i * NT + 64 * w) * 16);
   };
 
   v4f acc[MR][NR];
@@ -133,43 +81,20 @@ __global__ __launch_bounds__(256) void gemm_tn(const bf16* __restrict__ A, const
   // fragment read geometry: lane (r, h), r = lane & 15 -> (row quad q = r >> 2, column quad p = r & 3)
   const int r = lane & 15, h = lane >> 4, q = r >> 2, p = r & 3;
   auto read_frags = [&](const unsigned char* ba, const unsigned char* bb, int ks, v8bf (&af)[MR], v8bf (&bf)[NR]) {
-    const int t1 = 32 * ks + 8 * h + q, t2 = t1 + 4;
+    const int t1 = 32 * ks + 8 * h + q;
 #pragma unroll
-    for (int a = 0; a < MR; ++a) {
-      const int c = (wm * TM + 16 * a) / 8 + (p >> 1);
-      const unsigned char* p1 = ba + (t1 * CPA + slot_of<CPA>(t1, c)) * 16 + 8 * (p & 1);
-      const unsigned char* p2 = ba + (t2 * CPA + slot_of<CPA>(t2, c)) * 16 + 8 * (p & 1);
-      af[a] = cat8(tr_read(p1), tr_read(p2));
-    }
+    for (int a = 0; a < MR; ++a) af[a] = tok_frag<CPA>(ba, t1, (wm * TM + 16 * a) / 8, p);
 #pragma unroll
-    for (int b = 0; b < NR; ++b) {
-      const int c = (wn * TN + 16 * b) / 8 + (p >> 1);
-      const unsigned char* p1 = bb + (t1 * CPB + slot_of<CPB>(t1, c)) * 16 + 8 * (p & 1);
-      const unsigned char* p2 = bb + (t2 * CPB + slot_of<CPB>(t2, c)) * 16 + 8 * (p & 1);
-      bf[b] = cat8(tr_read(p1), tr_read(p2));
-    }
+    for (int b = 0; b < NR; ++b) bf[b] = tok_frag<CPB>(bb, t1, (wn * TN + 16 * b) / 8, p);
   };
 
-  // NS-buffer ring, NS - 1 K-tiles in flight: one K-tile's MFMAs (~300 cycles) are far shorter than a DMA's
-  // latency from L2 / MALL, so the loads of the next NS - 2 tiles overlap the wait for this one. A counted
-  // `s_waitcnt vmcnt` retires only the oldest tile (G DMAs per thread per tile); the barrier then orders it for
-  // every wave and frees the buffer read in the previous iteration, which the next issue refills.
+  // NS-buffer ring (mfma_stage.h; one K-tile's MFMAs here take ~300 cycles), G DMAs per thread per tile
   constexpr int G = AR + BR;
-  constexpr int INFL = (NS - 2) * G;
-  static_assert(INFL < 64, "vmcnt range");
-  constexpr int WAIT_STEADY = (INFL & 15) | (7 << 4) | (15 << 8) | ((INFL >> 4) << 14);
 #pragma unroll
   for (int i = 0; i < NS - 1; ++i)
     if (i < KT) issue(i, i);
   for (int kt = 0; kt < KT; ++kt) {
-    if (kt + NS - 2 <= KT - 1)
-      __builtin_amdgcn_s_waitcnt(WAIT_STEADY);  // tile kt retired, the NS - 2 after it still in flight
-    else
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    if (kt + NS - 1 < KT) issue(kt + NS - 1, (kt + NS - 1) % NS);
-    const unsigned char* ba = lds + (kt % NS) * BUF;
+    const unsigned char* ba = lds + ring_next<NS, G>(kt, KT, issue) * BUF;
     const unsigned char* bb = ba + ABYTES;
     v8bf af0[MR], bf0[NR], af1[MR], bf1[NR];
     read_frags(ba, bb, 0, af0, bf0);
@@ -224,13 +149,8 @@ __global__ __launch_bounds__(512) void gemm_tn_k2(const bf16* __restrict__ A, co
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
   const int qd = w & 3, kg = w >> 2, wm = qd >> 1, wn = qd & 1;
-  const int nwg = gridDim.x, bid = blockIdx.x, xcd = bid % 8, q8 = nwg / 8, r8 = nwg % 8;
-  const int tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + bid / 8;
-  constexpr int GM = 4;
-  const int nb_m = M / BM, nb_n = N / BN, per_group = GM * nb_n;
-  const int group = tile / per_group, first_m = group * GM, gsz = min(GM, nb_m - first_m);
-  const int wi = tile - group * per_group;
-  const int m0 = (first_m + wi % gsz) * BM, n0 = (wi / gsz) * BN;
+  const TileMN tl = grouped_tile(xcd_tile(blockIdx.x, gridDim.x), M / BM, N / BN);
+  const int m0 = tl.m * BM, n0 = tl.n * BN;
   const int t_begin = blockIdx.y * tps, KT = tps / BK;
   // this wave's 3 DMA wave-instructions: (operand, instruction index) -> LDS slots [64 i, 64 i + 64)
   int doff[G], dslot[G];
@@ -241,10 +161,10 @@ __global__ __launch_bounds__(512) void gemm_tn_k2(const bf16* __restrict__ A, co
     const bool isa = kg == 0 ? j < 2 : j == 0;
     const int i = isa ? w + 8 * j : (kg == 0 ? w + 4 : (w - 4) + 8 * (j - 1));
     const int sl = 64 * i + lane, t = sl / 12, pp = sl % 12;
-    int c = pp - rot<12>(t);
-    c = c < 0 ? c + 12 : c;
     dis_a[j] = isa;
     dslot[j] = 64 * i;
+    int c = pp - rot<12>(t);  // (tok_img_src by hand: through the helper this kernel compiles to different code)
+    c = c < 0 ? c + 12 : c;
     doff[j] = isa ? t * M + m0 + 8 * c : t * N + n0 + 8 * c;
   }
   auto issue = [&](int kt, int buf) {
@@ -254,7 +174,7 @@ __global__ __launch_bounds__(512) void gemm_tn_k2(const bf16* __restrict__ A, co
     for (int j = 0; j < G; ++j) {
       const bf16* src = dis_a[j] ? A + t0 * M + doff[j] : B + t0 * N + doff[j];
       unsigned char* dst = dis_a[j] ? ba + dslot[j] * 16 : ba + ABYTES + dslot[j] * 16;
-      __builtin_amdgcn_global_load_lds((const void*)src, (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
+      glds16(src, dst);
     }
   };
   v4f acc[MR][NR];
@@ -263,34 +183,25 @@ __global__ __launch_bounds__(512) void gemm_tn_k2(const bf16* __restrict__ A, co
 #pragma unroll
     for (int b = 0; b < NR; ++b) acc[a][b] = (v4f){0.f, 0.f, 0.f, 0.f};
   const int r = lane & 15, h = lane >> 4, q = r >> 2, p = r & 3;
-  const int t1 = 32 * kg + 8 * h + q, t2 = t1 + 4;
+  const int t1 = 32 * kg + 8 * h + q, t2 = t1 + 4;  // (k-step kg of every K-tile)
   int ao1[MR], ao2[MR], bo1[NR], bo2[NR];  // byte offsets of this lane's fragment reads inside a buffer
 #pragma unroll
   for (int a = 0; a < MR; ++a) {
     const int c = (wm * TM + 16 * a) / 8 + (p >> 1);
-    ao1[a] = (t1 * CPA + slot_of<CPA>(t1, c)) * 16 + 8 * (p & 1);
-    ao2[a] = (t2 * CPA + slot_of<CPA>(t2, c)) * 16 + 8 * (p & 1);
+    ao1[a] = tok_frag_off<CPA>(t1, c, p);
+    ao2[a] = tok_frag_off<CPA>(t2, c, p);
   }
 #pragma unroll
   for (int b = 0; b < NR; ++b) {
     const int c = (wn * TN + 16 * b) / 8 + (p >> 1);
-    bo1[b] = ABYTES + (t1 * CPB + slot_of<CPB>(t1, c)) * 16 + 8 * (p & 1);
-    bo2[b] = ABYTES + (t2 * CPB + slot_of<CPB>(t2, c)) * 16 + 8 * (p & 1);
+    bo1[b] = ABYTES + tok_frag_off<CPB>(t1, c, p);
+    bo2[b] = ABYTES + tok_frag_off<CPB>(t2, c, p);
   }
-  constexpr int INFL = (NS - 2) * G;
-  constexpr int WAIT_STEADY = (INFL & 15) | (7 << 4) | (15 << 8) | ((INFL >> 4) << 14);
 #pragma unroll
   for (int i = 0; i < NS - 1; ++i)
     if (i < KT) issue(i, i);
   for (int kt = 0; kt < KT; ++kt) {
-    if (kt + NS - 2 <= KT - 1)
-      __builtin_amdgcn_s_waitcnt(WAIT_STEADY);
-    else
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    if (kt + NS - 1 < KT) issue(kt + NS - 1, (kt + NS - 1) % NS);
-    const unsigned char* bf = lds + (kt % NS) * BUF;
+    const unsigned char* bf = lds + ring_next<NS, G>(kt, KT, issue) * BUF;
     v8bf af[MR], bfr[NR];
 #pragma unroll
     for (int a = 0; a < MR; ++a) af[a] = cat8(tr_read(bf + ao1[a]), tr_read(bf + ao2[a]));
@@ -385,24 +296,35 @@ int dispatch_k2(const void* A, const void* B, void* C, float* P, int M, int N, i
   return (int)hipGetLastError();
 }
 
+// (index = the `cfg` argument) BM x BN tile, OPT bits, ring depth NS0 (0: the deepest that fits). Written once: the
+// table mifx_gemm_tn_configs reports and the dispatch both expand this list. OPT bit 1 is the 8-wave gemm_tn_k2,
+// which exists for this one tile and depth only.
+#define TN_CONFIGS(X)                                                                                            \
+  X(96, 96, 0, 0) X(96, 96, 1, 0) X(128, 128, 0, 0) X(128, 96, 0, 0) X(96, 128, 0, 0) X(64, 64, 0, 0)            \
+  X(128, 64, 0, 0) X(64, 128, 0, 0) X(96, 96, 0, 3) X(96, 96, 0, 2) X(128, 128, 0, 2) X(128, 128, 0, 3)          \
+  X(64, 64, 0, 3) X(128, 64, 0, 3) X(64, 128, 0, 3) X(192, 192, 0, 3) X(192, 96, 0, 3) X(96, 192, 0, 3)          \
+  X(96, 96, 2, 6) X(96, 96, 1, 2) X(128, 128, 1, 2)
 struct Cfg {
   int bm, bn, opt, ns;
 };
-constexpr Cfg kCfgs[] = {{96, 96, 0, 0},  {96, 96, 1, 0},   {128, 128, 0, 0}, {128, 96, 0, 0}, {96, 128, 0, 0},
-                         {64, 64, 0, 0},  {128, 64, 0, 0},  {64, 128, 0, 0},  {96, 96, 0, 3},  {96, 96, 0, 2},
-                         {128, 128, 0, 2}, {128, 128, 0, 3}, {64, 64, 0, 3},   {128, 64, 0, 3}, {64, 128, 0, 3},
-                         {192, 192, 0, 3}, {192, 96, 0, 3},  {96, 192, 0, 3},  {96, 96, 2, 6},  {96, 96, 1, 2},
-                         {128, 128, 1, 2}};
+#define X(bm, bn, opt, ns) {bm, bn, opt, ns},
+constexpr Cfg kCfgs[] = {TN_CONFIGS(X)};
+#undef X
 
-template <int BM, int BN, int OPT, int NS0 = 0>
+template <int BM, int BN, int OPT, int NS0>
 int dispatch(const void* A, const void* B, void* C, float* P, int M, int N, int T, int S, hipStream_t st) {
-  if (S == 1) return launch<BM, BN, false, OPT, NS0>(A, B, C, nullptr, M, N, T, 1, st);
-  const int rc = launch<BM, BN, true, OPT, NS0>(A, B, nullptr, P, M, N, T, S, st);
-  if (rc != 0) return rc;
-  const long long n8 = (long long)M * N / 8;
-  hipLaunchKernelGGL(splits_sum, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, st, (const float4*)P, S, n8,
-                     (v8bf*)C);
-  return (int)hipGetLastError();
+  if constexpr (OPT & 2) {  // 8 waves, k-steps split over wave pairs
+    static_assert(BM == 96 && BN == 96 && NS0 == 6, "gemm_tn_k2's tile and ring depth");
+    return dispatch_k2(A, B, C, P, M, N, T, S, st);
+  } else {
+    if (S == 1) return launch<BM, BN, false, OPT, NS0>(A, B, C, nullptr, M, N, T, 1, st);
+    const int rc = launch<BM, BN, true, OPT, NS0>(A, B, nullptr, P, M, N, T, S, st);
+    if (rc != 0) return rc;
+    const long long n8 = (long long)M * N / 8;
+    hipLaunchKernelGGL(splits_sum, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, st, (const float4*)P, S, n8,
+                       (v8bf*)C);
+    return (int)hipGetLastError();
+  }
 }
 
 }  // namespace
@@ -433,29 +355,12 @@ int mifx_gemm_tn(int cfg, const void* A, const void* B, void* C, float* P, int M
   if (S > 1 && P == nullptr) return -1;
   if ((uintptr_t)A % 16 || (uintptr_t)B % 16 || (uintptr_t)C % 16 || (P != nullptr && (uintptr_t)P % 16)) return -1;
   if ((long long)T * M >= (1ll << 31) || (long long)T * N >= (1ll << 31)) return -1;  // 32-bit element offsets
-  switch (cfg) {
-    case 0: return dispatch<96, 96, 0>(A, B, C, P, M, N, T, S, st);
-    case 1: return dispatch<96, 96, 1>(A, B, C, P, M, N, T, S, st);
-    case 2: return dispatch<128, 128, 0>(A, B, C, P, M, N, T, S, st);
-    case 3: return dispatch<128, 96, 0>(A, B, C, P, M, N, T, S, st);
-    case 4: return dispatch<96, 128, 0>(A, B, C, P, M, N, T, S, st);
-    case 5: return dispatch<64, 64, 0>(A, B, C, P, M, N, T, S, st);
-    case 6: return dispatch<128, 64, 0>(A, B, C, P, M, N, T, S, st);
-    case 7: return dispatch<64, 128, 0>(A, B, C, P, M, N, T, S, st);
-    case 8: return dispatch<96, 96, 0, 3>(A, B, C, P, M, N, T, S, st);
-    case 9: return dispatch<96, 96, 0, 2>(A, B, C, P, M, N, T, S, st);
-    case 10: return dispatch<128, 128, 0, 2>(A, B, C, P, M, N, T, S, st);
-    case 11: return dispatch<128, 128, 0, 3>(A, B, C, P, M, N, T, S, st);
-    case 12: return dispatch<64, 64, 0, 3>(A, B, C, P, M, N, T, S, st);
-    case 13: return dispatch<128, 64, 0, 3>(A, B, C, P, M, N, T, S, st);
-    case 14: return dispatch<64, 128, 0, 3>(A, B, C, P, M, N, T, S, st);
-    case 15: return dispatch<192, 192, 0, 3>(A, B, C, P, M, N, T, S, st);
-    case 16: return dispatch<192, 96, 0, 3>(A, B, C, P, M, N, T, S, st);
-    case 17: return dispatch<96, 192, 0, 3>(A, B, C, P, M, N, T, S, st);
-    case 18: return dispatch_k2(A, B, C, P, M, N, T, S, st);  // 8 waves, k-steps split over wave pairs
-    case 19: return dispatch<96, 96, 1, 2>(A, B, C, P, M, N, T, S, st);
-    default: return dispatch<128, 128, 1, 2>(A, B, C, P, M, N, T, S, st);
-  }
+  int i = 0;
+#define X(bm, bn, opt, ns) \
+  if (cfg == i++) return dispatch<bm, bn, opt, ns>(A, B, C, P, M, N, T, S, st);
+  TN_CONFIGS(X)
+#undef X
+  return -1;
 }
 
 }  // extern "C"

@@ -23,7 +23,7 @@ def test_pick_config_prefers_full_waves(monkeypatch):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("cfg", list(range(19)))
+@pytest.mark.parametrize("cfg", list(range(20)))
 @pytest.mark.parametrize("epi,bias_dtype", [(0, None), (1, torch.bfloat16), (1, torch.float32), (2, torch.bfloat16),
                                             (2, torch.float32)])
 def test_gemm_nt_matches_fp32_reference(cfg, epi, bias_dtype):

@@ -2,7 +2,11 @@
 banks each): for every chunk count per token row (CPA = BM / 8), find a row rotation rot(t) of the 16-byte chunks such
 that every 32-lane half of every fragment read (token rows 32 ks + 8 h + q (+4), h in {0, 1} or {2, 3}, q = 0..3; the
 two chunks of a 16-column block) touches 16 distinct 16-byte bank slots. Prints the (x1, x2, x3) of
-rot(t) = x1 (t & 3) + x2 ((t >> 2) & 1) + x3 ((t >> 3) & 3) mod CPA that the kernel uses."""
+rot(t) = x1 (t & 3) + x2 ((t >> 2) & 1) + x3 ((t >> 3) & 3) mod CPA that the kernel uses.
+
+This is the search that found the rotations; it works on a Python re-statement of the formula. The check of the
+formula the kernels actually run (rot / slot_of / tok_frag_off in csrc/tile_index.h, every chunk count they
+instantiate) is tests/test_tile_index.py."""
 import itertools
 def ok(CPA, rot, xor=False):
     for ks in (0,1):
