@@ -1,4 +1,5 @@
-// KFP taxi DNN (one-hot indicator columns -> hidden 1500 -> 1 logit) as gather / scatter kernels.
+// KFP taxi DNN (one-hot indicator columns -> hidden layer (reference: 1500 wide) -> 1 logit) as gather / scatter
+// kernels; with more hidden layers (csrc/tdnn_stack.hip) this file is the first layer.
 //
 // Reference: `kubeflow-pipelines/taxi/preprocessing.py:104-124` builds a
 // 6,170-wide one-hot input (13 indicator columns + 3 numeric) that TF multiplies by a dense
@@ -27,58 +28,19 @@
 //    (grid H/256 x chunks), then a fixed-order combine and the same update; block 0 updates b2. Up to
 //    64 examples tdnn_head_bwd writes one chunk per example itself (no tdnn_dense_partial launch).
 #include <hip/hip_runtime.h>
-#include "feed.h"
+#include "tdnn_common.h"
 #include <stdint.h>
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kMaxH = 4096;
 constexpr int kMaxFields = 32;
 constexpr int kMaxDense = 8;
 
-__device__ __forceinline__ float block_sum(float v, float* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  if (lane == 0) red[w] = v;
-  __syncthreads();
-  float t = 0.f;
-#pragma unroll
-  for (int i = 0; i < kThreads / 64; ++i) t += red[i];
-  __syncthreads();
-  return t;
-}
-
-// record of example b of this step (see the header): the record feed of csrc/feed.h at step step_ctr[0] (global
-// stream stride / offset, optional per-epoch shuffle), or records start_fixed.. in stored order
-struct BatchSel {
-  long long n;
-  const long long* ctr;
-  long long start_fixed;
-  int B;
-  MifxFeed feed;
-  long long* rec_out;  // nullable: tdnn_head_bwd records which record each example of the step was
-  __device__ __forceinline__ MifxFeedStep start() const {
-    if (ctr) return mifx_feed_step(feed, ctr[0], n);
-    MifxFeedStep s;
-    s.e0 = 0;
-    s.i0 = start_fixed;
-    s.h = 1;
-    return s;
-  }
-  __device__ __forceinline__ long long rec(const MifxFeedStep& st, int b) const {
-    if (!ctr) {
-      const long long e = st.i0 + b;
-      return e >= n ? e - n : e;  // host guarantees B <= n
-    }
-    return mifx_feed_record(feed, st, b, n);
-  }
-};
-
 // grid (B, nh): block (b, c) owns hidden units [256c, 256c + 256) of example b — B x ceil(H/256)
 // workgroups so even the B=32 reference batch puts ~200 WGs in flight; each thread issues its
-// 16 independent row loads back to back. Writes a = relu(z) and this block's partial logit.
+// 16 independent row loads back to back. Writes a = relu(z) and this block's partial logit (kHead; a first layer
+// under a stack, csrc/tdnn_stack.hip, has no head: a only).
+template <bool kHead>
 __global__ __launch_bounds__(kThreads) void tdnn_fwd(const float* __restrict__ W1, const float* __restrict__ b1,
                                                     const float* __restrict__ w2, const int* __restrict__ rows, int F,
                                                     const float* __restrict__ xd, int D, int dense_row0, int H,
@@ -101,10 +63,12 @@ __global__ __launch_bounds__(kThreads) void tdnn_fwd(const float* __restrict__ W
     for (int d = 0; d < D; ++d) acc += sx[d] * W1[(size_t)(dense_row0 + d) * H + h];
     const float a = fmaxf(acc, 0.f);
     a_out[(size_t)b * H + h] = a;
-    p = a * w2[h];
+    if constexpr (kHead) p = a * w2[h];
   }
-  const float t = block_sum(p, red);
-  if (threadIdx.x == 0) part_out[(size_t)b * nh + blockIdx.y] = t;
+  if constexpr (kHead) {
+    const float t = block_sum(p, red);
+    if (threadIdx.x == 0) part_out[(size_t)b * nh + blockIdx.y] = t;
+  }
 }
 
 // grid (B, nh): logit from the partials (fixed order), BCE loss, dlogit, dz = dlogit * w2 * [a > 0]
@@ -196,7 +160,9 @@ __global__ __launch_bounds__(kThreads) void tdnn_sparse_adagrad(float* __restric
 }
 
 // grid (ceil(H/256), nchunk): per-chunk batch reductions for the dense params, into
-// part[chunk][k][h] with k = 0..D-1 dense W1 rows, D = b1, D+1 = w2
+// part[chunk][k][h] with k = 0..D-1 dense W1 rows, D = b1, D+1 = w2 (kHead only: under a stack w2 is not this
+// layer's, and a / dlogit are not read)
+template <bool kHead>
 __global__ __launch_bounds__(kThreads) void tdnn_dense_partial(const float* __restrict__ xd, int D, BatchSel sel,
                                                               const float* __restrict__ a,
                                                               const float* __restrict__ dz,
@@ -214,7 +180,7 @@ __global__ __launch_bounds__(kThreads) void tdnn_dense_partial(const float* __re
   for (int b = b0; b < b1e; ++b) {
     const float g = dz[(size_t)b * H + h];
     gb1 += g;
-    gw2 += dlogit[b] * a[(size_t)b * H + h];
+    if constexpr (kHead) gw2 += dlogit[b] * a[(size_t)b * H + h];
 #pragma unroll
     for (int d = 0; d < kMaxDense; ++d)
       if (d < D) gd[d] += xd[(size_t)sel.rec(st, b) * D + d] * g;
@@ -222,18 +188,14 @@ __global__ __launch_bounds__(kThreads) void tdnn_dense_partial(const float* __re
   float* out = part + (size_t)c * (D + 2) * H;
   for (int d = 0; d < D; ++d) out[(size_t)d * H + h] = gd[d];
   out[(size_t)D * H + h] = gb1;
-  out[(size_t)(D + 1) * H + h] = gw2;
-}
-
-__device__ __forceinline__ void adagrad_one(float* w, float* acc, float g, float lr) {
-  const float s = *acc + g * g;
-  *acc = s;
-  *w -= lr * g * rsqrtf(s);
+  if constexpr (kHead) out[(size_t)(D + 1) * H + h] = gw2;
 }
 
 // grid (ceil(H/256), D + 3): blockIdx.y = k < D + 2 sums row k of the chunk partials (dense W1 row k, b1 at
 // k = D, w2 at k = D + 1) in chunk order -- 8 loads in flight per thread -- and updates it; the (0, D + 2) block
-// updates b2 and advances the step counter.
+// updates b2 and advances the step counter. Without kHead (first layer of a stack: grid (ceil(H/256), D + 2)) the
+// rows are k < D + 1 and the (0, D + 1) block only advances the counter.
+template <bool kHead>
 __global__ __launch_bounds__(kThreads) void tdnn_dense_apply(float* __restrict__ W1, float* __restrict__ acc1,
                                                             float* __restrict__ b1, float* __restrict__ accb1,
                                                             float* __restrict__ w2, float* __restrict__ accw2,
@@ -242,8 +204,12 @@ __global__ __launch_bounds__(kThreads) void tdnn_dense_apply(float* __restrict__
                                                             int nchunk, const float* __restrict__ dlogit, int B,
                                                             int H, float lr, long long* __restrict__ step_ctr) {
   const int k = blockIdx.y;
-  if (k == D + 2) {
+  if (k == D + (kHead ? 2 : 1)) {
     if (blockIdx.x != 0) return;
+    if constexpr (!kHead) {
+      if (threadIdx.x == 0 && step_ctr) step_ctr[0] += 1;
+      return;
+    }
     __shared__ float red[kThreads / 64];
     float p = 0.f;
     for (int b = threadIdx.x; b < B; b += kThreads) p += dlogit[b];
@@ -310,7 +276,7 @@ int mifx_tdnn_fwd_bwd(const float* W1, const float* b1, const float* w2, const f
     return -1;
   const BatchSel sel{n, step_ctr, start_fixed, B, MifxFeed{feed_stride, feed_offset, shuffle_key}, rec_out};
   const dim3 grid(B, (H + kThreads - 1) / kThreads);
-  hipLaunchKernelGGL(tdnn_fwd, grid, dim3(kThreads), 0, st, W1, b1, w2, rows, F, xd, D, dense_row0, H, sel, a_out,
+  hipLaunchKernelGGL(tdnn_fwd<true>, grid, dim3(kThreads), 0, st, W1, b1, w2, rows, F, xd, D, dense_row0, H, sel, a_out,
                      part_logit);
   float* direct = train && B <= kDirectChunks ? dense_part : nullptr;
   if (train && B <= kDirectChunks && dense_part == nullptr) return -1;
@@ -335,11 +301,49 @@ int mifx_tdnn_adagrad(float* W1, float* acc1, float* b1, float* accb1, float* w2
   const int nchunk = mifx_tdnn_chunks(B);
   const int hb = (H + kThreads - 1) / kThreads;
   if (B > kDirectChunks)  // (small batches: tdnn_head_bwd wrote the per-example chunks)
-    hipLaunchKernelGGL(tdnn_dense_partial, dim3(hb, nchunk), dim3(kThreads), 0, st, xd, D, sel, a, dz, dlogit, B, H,
+    hipLaunchKernelGGL(tdnn_dense_partial<true>, dim3(hb, nchunk), dim3(kThreads), 0, st, xd, D, sel, a, dz, dlogit, B, H,
                        dense_part);
-  hipLaunchKernelGGL(tdnn_dense_apply, dim3(hb, D + 3), dim3(kThreads), 0, st, W1, acc1, b1, accb1, w2, accw2, b2,
+  hipLaunchKernelGGL(tdnn_dense_apply<true>, dim3(hb, D + 3), dim3(kThreads), 0, st, W1, acc1, b1, accb1, w2, accw2, b2,
                      accb2, D,
                      dense_row0, dense_part, nchunk, dlogit, B, H, lr, step_ctr);
+  return (int)hipGetLastError();
+}
+
+// ---- first layer of a stack (csrc/tdnn_stack.hip holds layers 2..L and the head): the same kernels without the head.
+
+// a_out [B, H] = relu(b1 + gathered W1 rows + dense rows); record selection as mifx_tdnn_fwd_bwd
+int mifx_tdnn_l1_fwd(const float* W1, const float* b1, const int* rows, int F, const float* xd, int D, int dense_row0,
+                     long long n, const long long* step_ctr, long long start_fixed, int B, int H, float* a_out,
+                     long long feed_stride, long long feed_offset, unsigned long long shuffle_key, hipStream_t st) {
+  if (H <= 0 || H > kMaxH || F > kMaxFields || D > kMaxDense || B <= 0 || n < B || start_fixed < 0 ||
+      start_fixed >= n || feed_stride < B || feed_offset < 0 || feed_offset + B > feed_stride)
+    return -1;
+  const BatchSel sel{n, step_ctr, start_fixed, B, MifxFeed{feed_stride, feed_offset, shuffle_key}, nullptr};
+  const dim3 grid(B, (H + kThreads - 1) / kThreads);
+  hipLaunchKernelGGL(tdnn_fwd<false>, grid, dim3(kThreads), 0, st, W1, b1, (const float*)nullptr, rows, F, xd, D,
+                     dense_row0, H, sel, a_out, (float*)nullptr);
+  return (int)hipGetLastError();
+}
+
+// Sparse-row Adagrad, then the dense W1 rows and b1, from dz [B, H] of the first layer; the last launch advances
+// step_ctr (when set). scratch: dense_part [mifx_tdnn_chunks(B) * (D + 2) * H] (one example per chunk up to 64
+// examples, as tdnn_head_bwd writes them for one layer; else the same chunks of >= 32)
+int mifx_tdnn_l1_adagrad(float* W1, float* acc1, float* b1, float* accb1, const int* rows, int F, const float* xd,
+                         int D, int dense_row0, long long n, long long* step_ctr, long long start_fixed,
+                         const float* dz, int B, int H, float lr, float* dense_part, long long feed_stride,
+                         long long feed_offset, unsigned long long shuffle_key, hipStream_t st) {
+  if (H <= 0 || H > kMaxH || D > kMaxDense || F > kMaxFields || B <= 0 || B > kMaxList || n < B ||
+      start_fixed < 0 || start_fixed >= n || feed_stride < B || feed_offset < 0 || feed_offset + B > feed_stride)
+    return -1;
+  const BatchSel sel{n, step_ctr, start_fixed, B, MifxFeed{feed_stride, feed_offset, shuffle_key}, nullptr};
+  hipLaunchKernelGGL(tdnn_sparse_adagrad, dim3(B * F), dim3(kThreads), 0, st, W1, acc1, rows, F, sel, dz, H, lr);
+  const int nchunk = mifx_tdnn_chunks(B);
+  const int hb = (H + kThreads - 1) / kThreads;
+  hipLaunchKernelGGL(tdnn_dense_partial<false>, dim3(hb, nchunk), dim3(kThreads), 0, st, xd, D, sel,
+                     (const float*)nullptr, dz, (const float*)nullptr, B, H, dense_part);
+  hipLaunchKernelGGL(tdnn_dense_apply<false>, dim3(hb, D + 2), dim3(kThreads), 0, st, W1, acc1, b1, accb1,
+                     (float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr, D, dense_row0, dense_part,
+                     nchunk, (const float*)nullptr, B, H, lr, step_ctr);
   return (int)hipGetLastError();
 }
 

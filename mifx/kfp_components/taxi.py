@@ -163,7 +163,8 @@ def tft(a) -> None:
 
 
 def dnntrainer(a) -> None:
-    """Train the taxi DNN (hidden `hidden_layer_size`, Adagrad) and export a servable model."""
+    """Train the taxi DNN (hidden layers `hidden_layer_size`, comma-separated widths; Adagrad) and export a servable
+    model."""
     import torch
 
     from ..io import dataset
@@ -171,7 +172,14 @@ def dnntrainer(a) -> None:
     from ..serving.saved_model import save_module
     from ..trainer.taxi_dnn_trainer import TaxiDNNTrainer
 
+    hidden = [int(x) for x in str(a.hidden_layer_size).split(",") if x.strip()]
+    if not hidden or min(hidden) < 1:
+        raise ValueError(f"hidden_layer_size={a.hidden_layer_size!r}: one or more positive layer widths, "
+                         "comma-separated")
     n_gpus = int(a.num_gpus or 1)
+    if len(hidden) > 1 and a.device != "cpu" and max(n_gpus, int(os.environ.get("WORLD_SIZE", "1"))) > 1:
+        raise ValueError(f"hidden_layer_size={a.hidden_layer_size!r}: GPU data parallelism is single-layer only; "
+                         "train a stack with num_gpus=1 (or device=cpu)")
     if n_gpus > 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1:
         # data parallel: this container step launches one rank per GPU of itself (rank 0 exports)
         from ..trainer.distributed import run_ranks
@@ -183,8 +191,7 @@ def dnntrainer(a) -> None:
 
     env = mdist.init("gloo" if a.device == "cpu" else None)
     pg = torch.distributed.group.WORLD if env.world_size > 1 else None
-    hidden = [int(x) for x in str(a.hidden_layer_size).split(",") if x.strip()]
-    cfg = TaxiDNNConfig(hidden=hidden[0], label=a.target)
+    cfg = TaxiDNNConfig(hidden_units=hidden, label=a.target)
     cols = dataset.table_to_numpy(dataset.read_split(os.path.join(a.transformed_data_dir, "train")))
     ids, dense, y = columns_to_tensors(cols, cfg)
     dev = a.device or ("cuda" if torch.cuda.is_available() else "cpu")
@@ -205,7 +212,7 @@ def dnntrainer(a) -> None:
     acc = float(((logits > 0) == (ey.numpy() > 0.5)).mean())
     export = os.path.join(a.training_output_dir, "export", "export", "1")
     model = tr.model.cpu()
-    save_module(export, model, "mifx.models.taxi_dnn:TaxiDNN", {"hidden": cfg.hidden, "seed": None}, None)
+    save_module(export, model, "mifx.models.taxi_dnn:TaxiDNN", {"hidden_units": list(cfg.hidden_units), "seed": None}, None)
     with open(os.path.join(export, "transform_dir.txt"), "w") as f:
         f.write(os.path.abspath(a.transformed_data_dir))
     _metrics(a.training_output_dir, [("accuracy", acc)])

@@ -2,7 +2,8 @@
 PyTorch autograd + TF-semantics Adagrad on CPU (the numerics oracle).
 
 Reference: dnntrainer component (`taxi-cab-classification-pipeline.py:117-126`): Adagrad lr 0.1,
-hidden 1500, 3,000 steps, binary head; TF's Adagrad starts accumulators at 0.1."""
+hidden_layer_size '1500' (a comma-separated list of layer widths: `TaxiDNNConfig.hidden_units`), 3,000 steps, binary
+head; TF's Adagrad starts accumulators at 0.1."""
 from __future__ import annotations
 
 import numpy as np
@@ -18,6 +19,11 @@ class TaxiDNNTrainer:
     deduplicates rows in-kernel (no sort/unique, whose dynamic output size synchronised the host every step). So
     the step is captured once into hipGraphs -- one step and `steps_per_graph` consecutive steps -- and replayed
     (`graph=False`: eager launches of the same kernels).
+
+    More than one hidden layer (`hidden_units` = [H1, .., HL]): the same first-layer kernels without the head, and
+    csrc/tdnn_stack.hip for layers 2..L -- exact-f32 MFMA forward and input gradient, the head over a_L, and one
+    kernel per layer that sums the weight gradient over the batch in registers and applies Adagrad in its epilogue
+    (mifx.ops.tdnn_stack.train_step: 4 + 3 (L - 1) + 3 launches, same stream, same device-side batch selection).
 
     Data parallel (`process_group`, one rank per GPU): the 6170 x 1500 first layer makes the DENSE gradient 37 MB
     (the bandwidth-relevant case), but a step touches only batch x 13 of its 6,167 sparse rows. So
@@ -36,7 +42,17 @@ class TaxiDNNTrainer:
         process group every rank keeps all records and trains on its slice of one global stream (stride
         world x batch, offset rank x batch), so the job equals one process at batch world x batch."""
         self.device = torch.device(device)
-        self.model = (model or TaxiDNN()).to(self.device)
+        model = model or TaxiDNN()
+        self.units = list(model.cfg.hidden_units)
+        self.stack = None
+        if len(self.units) > 1 and ((self.device.type == "cuda") if native is None else native):
+            from ..ops import tdnn_stack  # (checked before anything is moved to or launched on the device)
+
+            if process_group is not None:
+                raise ValueError(f"hidden_units={self.units}: GPU data parallelism is single-layer only (the sparse "
+                                 "exchange ships first-layer state); train a stack on one GPU or on the CPU path")
+            tdnn_stack.validate(self.units, batch)
+        self.model = model.to(self.device)
         self.batch, self.lr, self.loss_reduction = batch, lr, loss_reduction
         self.native = (self.device.type == "cuda") if native is None else native
         self.dense_row0 = self.model.cfg.sparse_rows
@@ -59,10 +75,14 @@ class TaxiDNNTrainer:
             if batch > embag_mlp.limits()["max_batch"]:
                 raise ValueError(f"batch {batch} > {embag_mlp.limits()['max_batch']} (csrc/embag_mlp.hip kMaxList)")
             self.step_ctr = torch.zeros(1, dtype=torch.int64, device=self.device)
-            p = {n: getattr(self.model, n) for n in ("W1", "b1", "w2", "b2")}
-            self.params = {n: t.data for n, t in p.items()}
+            self.params = {n: t.data for n, t in self.model.named_parameters()}  # W1, b1, [Wh.k, bh.k,] w2, b2
             self.accs = {n: torch.full_like(t, initial_accumulator_value) for n, t in self.params.items()}
-            self.bufs = embag_mlp.make_buffers(batch, self.model.cfg.hidden, len(self.model.cfg.dense), self.device)
+            if len(self.units) > 1:
+                self.stack = tdnn_stack.Stack(self.params, self.accs, self.units, batch, len(self.model.cfg.dense),
+                                              self.device)
+                self.bufs = {"loss": self.stack.loss}
+            else:
+                self.bufs = embag_mlp.make_buffers(batch, self.units[0], len(self.model.cfg.dense), self.device)
             if self.world > 1:
                 self._init_exchange()
         else:
@@ -167,6 +187,12 @@ class TaxiDNNTrainer:
             return
         scale = 1.0 if self.loss_reduction == "sum" else 1.0 / self.batch
         p = self.params
+        if self.stack is not None:
+            from ..ops import tdnn_stack
+
+            tdnn_stack.train_step(self.stack, self.rows, self.dense, self.label, self.dense_row0, scale, self.lr,
+                                  self.step_ctr, self.feed)
+            return
         self._k.fwd_bwd(p["W1"], p["b1"], p["w2"], p["b2"], self.rows, self.dense, self.label, self.dense_row0, scale,
                         True, self.bufs, batch=self.batch, step_ctr=self.step_ctr, feed=self.feed)
         self._k.adagrad(p, self.accs, self.rows, self.dense, self.dense_row0, self.bufs, self.lr, batch=self.batch,
@@ -234,7 +260,12 @@ class TaxiDNNTrainer:
         for s in range(0, len(ids), batch):
             r = self.model.rows(ids[s:s + batch].to(self.device)).to(torch.int32).contiguous()
             xd = dense[s:s + batch].to(self.device).float().contiguous()
-            if self.native:
+            if self.stack is not None:
+                from ..ops import tdnn_stack
+
+                s = tdnn_stack.Stack(self.params, None, self.units, len(r), xd.shape[1], self.device)
+                out.append(tdnn_stack.logits(s, r, xd, self.dense_row0).cpu())
+            elif self.native:
                 bufs = self._k.make_buffers(len(r), self.model.cfg.hidden, xd.shape[1], self.device)
                 self._k.fwd_bwd(self.params["W1"], self.params["b1"], self.params["w2"], self.params["b2"], r, xd,
                                 bufs["logit"], self.dense_row0, 1.0, False, bufs)
@@ -245,6 +276,4 @@ class TaxiDNNTrainer:
 
     def _forward_rows(self, rows: torch.Tensor, xd: torch.Tensor) -> torch.Tensor:
         """Reference forward on global W1 rows (what the HIP kernel computes)."""
-        m = self.model
-        z = m.b1 + m.W1[rows.long()].sum(1) + xd @ m.W1[self.dense_row0:]
-        return torch.relu(z) @ m.w2 + m.b2
+        return self.model.forward_rows(rows.long(), xd)
