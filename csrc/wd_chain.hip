@@ -389,6 +389,49 @@ __device__ __forceinline__ void mask_grad(const v4f (&g)[TBN][K / 16], const v8b
     }
 }
 
+// WDC_ABL (ablation builds of tools/build_wdc_abl.sh for step A/Bs, same results; profiles/wd_epilogue.md): bit 0 the
+// wave sums as ds_bpermute (__shfl_xor), bit 2 every build with the two-barrier epilogue, bit 3 the histogram
+// atomics behind B0 in every build
+#ifndef WDC_ABL
+#define WDC_ABL 0
+#endif
+constexpr bool ABL_SUM = WDC_ABL & 1, ABL_EPI = WDC_ABL & 4, ABL_ATOM = WDC_ABL & 8;
+
+// ---- wave sums on the VALU (no ds_bpermute round trips through the LDS pipe).
+// v_permlaneN_swap(vdst, src) as mask_grad uses it: [0] = vdst with its rows 1, 3 (N = 16) / lanes 32-63 (N = 32)
+// replaced by src's rows 0, 2 / lanes 0-31; [1] = src with those replaced by what vdst held there.
+template <int CTRL>
+__device__ __forceinline__ float add_dpp(float v) {  // v + v of the lane DPP control CTRL selects (v_add_f32_dpp)
+  return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false));
+}
+// Sum of a over the wave in lanes 0-31 and of b in lanes 32-63: the xor butterfly 32, 16, 8, 4, 2, 1 of both values in
+// two swaps and six adds. Bit-identical in those lanes to `for (o = 32; o; o >>= 1) v += __shfl_xor(v, o)`: every
+// step of that loop adds a lane's value and its partner's, and IEEE addition is commutative, so it does not matter
+// which of the two is the left operand.
+//  * xor 32: the swap gives (a lo | b lo) and (a hi | b hi); their sum holds a[l] + a[l ^ 32] in lanes 0-31 and
+//    b[l] + b[l ^ 32] in lanes 32-63 -- from here each half carries one value.
+//  * xor 16: the swap of c with itself gives rows (c0 c0 c2 c2) and (c1 c1 c3 c3); their sum is c[l] + c[l ^ 16].
+//  * after xor 32, 16 and 8 a value depends on lane mod 8 only, so row_ror:8 (partner l +- 8 in the row = l ^ 8) and
+//    row_ror:4 (partner l - 4 in the row, equal to l ^ 4 mod 8) deliver the xor partner's value; quad_perm [2,3,0,1]
+//    and [1,0,3,2] are xor 2 and xor 1 themselves.
+__device__ __forceinline__ float wave_sum2(float a, float b) {
+  if constexpr (ABL_SUM) {
+    for (int o = 32; o > 0; o >>= 1) {
+      a += __shfl_xor(a, o);
+      b += __shfl_xor(b, o);
+    }
+    return __lane_id() < 32 ? a : b;
+  }
+  const v2u p = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
+  float c = __uint_as_float(p[0]) + __uint_as_float(p[1]);
+  const v2u q = __builtin_amdgcn_permlane16_swap(__float_as_uint(c), __float_as_uint(c), false, false);
+  c = __uint_as_float(q[0]) + __uint_as_float(q[1]);
+  c = add_dpp<0x128>(c);  // row_ror:8
+  c = add_dpp<0x124>(c);  // row_ror:4
+  c = add_dpp<0x4E>(c);   // quad_perm:[2,3,0,1]
+  return add_dpp<0xB1>(c);  // quad_perm:[1,0,3,2]
+}
+
 // stage dZ (gradient tiles, C order of the layer above: tiles 2m, 2m+1 = the 16-byte fragment of C positions
 // 32 m + 8 h, as bwd_dA consumes them) and the layer's input activation fragments (C order) for the dW product
 // of a layer with dims K x N; rows permuted by sperm16 inside each 16-row block.
@@ -685,6 +728,15 @@ __global__ __launch_bounds__(64 * (T / (16 * TBN)), 1) void wdc_fused(const uint
   int* wgi = (int*)wgrad;
   constexpr int NWAVE = T / (16 * TBN), NTHR = 64 * NWAVE, EPW = 16 * TBN;  // waves, threads, examples per wave
   const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, r = lane & 15, h = lane >> 4;
+  // EARLY: the one-iteration training builds reduce the loss / dlogit sums right behind the loss phase, under the
+  // backward, and run the epilogue without a barrier (see there). Not where the sums accumulate over iterations
+  // (T = 128), not in the eval path (it never passes B0), not with the in-kernel tail or the persistent loop, whose
+  // epilogues reuse LDS.
+  // (the plain training step of the T = 256 and T = 64 libraries)
+  constexpr bool SLAB_STEP = ONE_ITER && TRAIN && !TAIL && !PERSIST;
+  constexpr bool EARLY = SLAB_STEP && !ABL_EPI;
+  // the histogram atomics in front of B0: in the same two builds, the ones whose step A/B was measured
+  constexpr bool ATOM_EARLY = SLAB_STEP && !ABL_ATOM;
   bool stamp_on = true;
   (void)stamp_on;
   STAMP(0);
@@ -1022,9 +1074,27 @@ __global__ __launch_bounds__(64 * (T / (16 * TBN)), 1) void wdc_fused(const uint
     float dlb[TBN];
 #pragma unroll
     for (int tb = 0; tb < TBN; ++tb) dlb[tb] = (float)(bf16)__shfl(dl, 16 * tb + r);
+    STAMP(4);
+    if constexpr (EARLY) {
+      // One iteration: both sums are final here. red[] is written in front of B0 and read in the epilogue, with B0
+      // and every layer barrier in between -- B0 alone makes it visible to the whole workgroup.
+      const float s = wave_sum2(loss_sum, dl_sum);
+      if ((lane & 31) == 0) red[(lane >> 5) * NWAVE + w] = s;
+    }
+    // the wide gradient's fixed-point histogram: wgrad was zeroed in front of the prologue barrier and no stage
+    // region reaches it, so nothing orders these atomics against B0; the histogram is final after the next barrier
+    // any wave passes behind them (ATOM_EARLY: B0, otherwise layer 5's first)
+    auto wide_hist = [&]() {
+      if (own) {
+        const int q = __float2int_rn(fminf(fmaxf(dl * qscale, -qmax), qmax));
+#pragma unroll
+        for (int f = 0; f < 9; ++f) atomicAdd(&wgi[ids[f]], q);
+      }
+    };
+    if constexpr (ATOM_EARLY) wide_hist();
+    STAMP(20);
 
     // ---- layer 5: stage (dZ5, A4); dW5; dA4 = w5 (x) dl on the VALU, masked
-    STAMP(4);
     uint16_t* const S5 = lds + SB5;
     uint16_t* const S4 = lds + SB4;
     uint16_t* const S3 = lds + SB3;
@@ -1034,11 +1104,8 @@ __global__ __launch_bounds__(64 * (T / (16 * TBN)), 1) void wdc_fused(const uint
     // the weights are done -- layers 3 to 1 stage over them with only the layer barriers in between)
     block_sync_lds();
     STAMP(5);
-    if (own) {
-      const int q = __float2int_rn(fminf(fmaxf(dl * qscale, -qmax), qmax));
-#pragma unroll
-      for (int f = 0; f < 9; ++f) atomicAdd(&wgi[ids[f]], q);
-    }
+    if constexpr (!ATOM_EARLY) wide_hist();
+    STAMP(21);
     {
       v4bf d5[TBN][1];
 #pragma unroll
@@ -1077,7 +1144,8 @@ __global__ __launch_bounds__(64 * (T / (16 * TBN)), 1) void wdc_fused(const uint
       }
       mask_grad<K5, KT5, TBN>(g, a4, dz4);
     }
-    block_sync_lds();
+    STAMP(22);
+    block_sync_lds();  // (the wide histogram is final from here at the latest: every wave's atomics are done)
     STAMP(6);
     if (l5) dw_phase<K5, N5, 1, 1>(acc5, S5, 0, 0, w & 3, 0, r, h);  // (waves 0..2: the live k tiles)
     WDC_EMIT(1, acc5, ct5);
@@ -1159,19 +1227,19 @@ __global__ __launch_bounds__(64 * (T / (16 * TBN)), 1) void wdc_fused(const uint
   STAMP(16);
 
   // ---- epilogue: per-workgroup slab (same layout as wd_fused)
-  for (int o = 32; o > 0; o >>= 1) {
-    loss_sum += __shfl_xor(loss_sum, o);
-    dl_sum += __shfl_xor(dl_sum, o);
+  // EARLY: no barrier. red[] was written in front of B0 and the wide histogram is final since layer 5's first
+  // barrier; the waves still in dW1 only read their staging area, which nothing below touches.
+  if constexpr (!EARLY) {
+    const float s = wave_sum2(loss_sum, dl_sum);
+    __syncthreads();  // last dW reads done; red/wgrad final
+    STAMP(18);  // (stamp builds: the epilogue split -- 16 -> 18 wave reduction + this barrier)
+    if ((lane & 31) == 0) red[(lane >> 5) * NWAVE + w] = s;
+    // (the dW tiles went out in the last iteration, each right after its layer's dW phase: their stores drain
+    // under the remaining layers' compute instead of here)
+    __syncthreads();
+  } else {
+    STAMP(18);
   }
-  __syncthreads();  // last dW reads done; red/wgrad final
-  STAMP(18);  // (stamp builds: the epilogue split -- 16 -> 18 wave reduction + this barrier)
-  if (lane == 0) {
-    red[w] = loss_sum;
-    red[NWAVE + w] = dl_sum;
-  }
-  // (the dW tiles went out in the last iteration, each right after its layer's dW phase: their stores drain
-  // under the remaining layers' compute instead of here)
-  __syncthreads();
   if constexpr (TRAIN && PERSIST) {  // wide weights: optimizer on the histogram gradient, in LDS + master copy
     const bool s1_live = ta.hw.kind >= 2;
     const int w0 = stride - WIDE_PAD;

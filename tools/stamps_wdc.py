@@ -29,12 +29,15 @@ from mifx.data.synthetic import synthetic_records  # noqa: E402
 from mifx.models.wide_deep import WideDeepModel  # noqa: E402
 from mifx.trainer.fused_wide_deep import FusedWideDeepTrainer  # noqa: E402
 
-NAMES = {1: "prologue", 2: "loop->iter", 3: "gather+fwd", 4: "loss", 5: "B0", 6: "stage5+B", 7: "dW5+dA4",
-         8: "B+stage4+B", 9: "dW4+dA3", 10: "B+stage3+B", 11: "dW3+dA2", 12: "B+stage2+B", 13: "dW2+dA1",
-         14: "B+stage1+B", 15: "dW1", 16: "->epi", 17: "epilogue"}
+# phases in program order: (label, stamp at its end); a phase runs from the previous entry's stamp (the first from
+# stamp 0). Stamps 20-22 split what used to be "B0" and "stage5+B"; 18 and 19 split the epilogue.
+PHASES = [("prologue", 1), ("loop->iter", 2), ("gather+fwd", 3), ("loss", 4), ("sums+hist", 20), ("B0 wait", 5),
+          ("hist(late)", 21), ("stage5+dA4", 22), ("L5 B wait", 6), ("dW5+dA4", 7), ("B+stage4+B", 8), ("dW4+dA3", 9),
+          ("B+stage3+B", 10), ("dW3+dA2", 11), ("B+stage2+B", 12), ("dW2+dA1", 13), ("B+stage1+B", 14), ("dW1", 15),
+          ("->epi", 16), ("epi:sum+B", 18), ("epi:B+hist", 19), ("epi:loss", 17)]
 # T = 256: every layer stages its T rows once (csrc/wd_chain.hip, the rotated LDS placement): a layer is stage +
 # activation gradient + barrier, then dW phase + barrier
-NAMES256 = {**NAMES, 8: "stg4+dA3+B", 9: "dW4+B", 10: "stg3+dA2+B", 11: "dW3+B", 12: "stg2+dA1+B", 13: "dW2+B",
+NAMES256 = {8: "stg4+dA3+B", 9: "dW4+B", 10: "stg3+dA2+B", 11: "dW3+B", 12: "stg2+dA1+B", 13: "dW2+B",
             14: "stage1+B"}
 CFGS = [(4, 40, False), (8, 65536, False), (8, 65536, True)] if "--quick" in sys.argv else \
     [(4, 40, False), (8, 40, False), (4, 65536, False), (8, 128, False), (8, 65536, False), (8, 65536, True)]
@@ -52,13 +55,13 @@ for NW, batch, big in CFGS:
     assert lib.mifx_wdc_stamps(buf) == 0
     st = [[buf[w * 32 + i] for i in range(32)] for w in range(NW)]
     print(f"== batch {batch} grid {tr.grid} T {tr.tile}: cycles per phase (block 0; the 2nd iteration when there is one)")
-    for i in range(1, 18):
-        d = [st[w][i] - st[w][i - 1] for w in range(NW)]
-        nm = (NAMES256 if big else NAMES)[i]
-        print(f"  {nm:>12}: " + " ".join(f"{x:8d}" for x in d))
-    # the epilogue split (stamps 18, 19 sit between 16 and 17)
-    for nm, a, b in (("epi:reduce+B", 16, 18), ("epi:B+hist", 18, 19), ("epi:loss", 19, 17)):
-        print(f"  {nm:>12}: " + " ".join(f"{st[w][b] - st[w][a]:8d}" for w in range(NW)))
+    # (the one-iteration training builds reduce in "sums+hist" and have no epilogue barrier: "epi:sum+B" is empty,
+    # "epi:B+hist" the histogram's slab stores alone; "hist(late)" is empty where the atomics stand in front of B0)
+    prev = 0
+    for nm, i in PHASES:
+        nm = NAMES256.get(i, nm) if big else nm
+        print(f"  {nm:>12}: " + " ".join(f"{st[w][i] - st[w][prev]:8d}" for w in range(NW)))
+        prev = i
     print(f"  iteration (stamp 2 -> 15), wave 0: {st[0][15] - st[0][2]}; kernel (0 -> 17): {st[0][17] - st[0][0]}")
 
 # per-block global clock (100 MHz) of the last launch (the 8-wave B=65536 trainer above): dispatch stagger and
