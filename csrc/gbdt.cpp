@@ -24,7 +24,8 @@
 // Node statistics (the *_stats entries): every grower can also record each node's gain and cover (hessian sum), which
 // feature importances and feature contributions need. mifx_gbdt_paths_build turns a forest with covers into the path
 // table of gbdt_shap.h and mifx_gbdt_contribs evaluates path-dependent TreeSHAP from it (the device twin is k_contribs
-// in gbdt_prep.hip).
+// in gbdt_prep.hip); mifx_gbdt_interactions gives the interaction values, one conditioned pass per feature over the
+// leaves that hold it (the device twin is k_interactions in gbdt_interactions.hip).
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -633,6 +634,40 @@ int mifx_gbdt_paths_build(int n_trees, const int* tree_off, const int* feature, 
   return 0;
 }
 
+// is recs[0, n_recs) whole leaves of at most MIFX_SHAP_MAX_PATH elements with features in [0, f)
+static bool shap_table_fits(const MifxShapRec* recs, long n_recs, int f) {
+  for (long pos = 0; pos < n_recs;) {
+    const int m = recs[pos].i;
+    if (m < 0 || m > MIFX_SHAP_MAX_PATH || pos + 1 + m > n_recs) return false;
+    for (int e = 0; e < m; ++e)
+      if (recs[pos + 1 + e].i < 0 || recs[pos + 1 + e].i >= f) return false;
+    pos += 1 + m;
+  }
+  return true;
+}
+
+// one row's contributions phi[0 .. f) and bias phi[f], the table walked in order; obits (or null) receives every
+// leaf's o bits
+static void shap_contribs_row(const double* xi, int f, const MifxShapRec* recs, long n_recs, double base, double* phi,
+                              uint16_t* leaf_obits) {
+  for (int j = 0; j < f; ++j) phi[j] = 0.0;
+  double bias = base;
+  for (long pos = 0; pos < n_recs;) {
+    const MifxShapRec& hd = recs[pos];
+    const int m = hd.i;
+    bias += hd.b;
+    unsigned obits = 0;
+    if (m > 0) {
+      const MifxShapRec* e = recs + pos + 1;
+      for (int k = 0; k < m; ++k) obits |= (unsigned)mifx_shap_passes(e[k], xi[e[k].i]) << k;
+      mifx_shap_leaf_m(m, e, obits, hd.a, [&](int j, double x) { phi[j] += x; });
+    }
+    if (leaf_obits) *leaf_obits++ = (uint16_t)obits;
+    pos += 1 + m;
+  }
+  phi[f] = bias;
+}
+
 // Contributions of the leaves in recs[0, n_recs) (a prefix of a path table that ends at a leaf boundary) for every
 // row of a row-major [n, f] table: out[i * stride + j] for j < f is feature j's contribution, out[i * stride + f]
 // the bias, base plus every leaf's share. One accumulator row per data row, the table walked in order, so the result
@@ -640,34 +675,64 @@ int mifx_gbdt_paths_build(int n_trees, const int* tree_off, const int* feature, 
 int mifx_gbdt_contribs(const double* X, long n, int f, const MifxShapRec* recs, long n_recs, double base, double* out,
                        long stride, int threads) {
   if (n < 0 || f < 1 || n_recs < 0 || stride < f + 1) return -1;
-  for (long pos = 0; pos < n_recs;) {
-    const int m = recs[pos].i;
-    if (m < 0 || m > MIFX_SHAP_MAX_PATH || pos + 1 + m > n_recs) return -1;
-    for (int e = 0; e < m; ++e)
-      if (recs[pos + 1 + e].i < 0 || recs[pos + 1 + e].i >= f) return -1;
-    pos += 1 + m;
-  }
+  if (!shap_table_fits(recs, n_recs, f)) return -1;
   const int chunks = n > 64 ? (int)std::min<long>(std::max(1, threads), n) : 1;
   parallel_for(chunks, chunks, [&](int c) {
     const long lo = n * c / chunks, hi = n * (c + 1) / chunks;
-    for (long i = lo; i < hi; ++i) {
-      const double* xi = X + (size_t)i * f;
-      double* phi = out + (size_t)i * stride;
-      for (int j = 0; j < f; ++j) phi[j] = 0.0;
-      double bias = base;
-      for (long pos = 0; pos < n_recs;) {
-        const MifxShapRec& hd = recs[pos];
-        const int m = hd.i;
-        bias += hd.b;
-        if (m > 0) {
-          const MifxShapRec* e = recs + pos + 1;
-          unsigned obits = 0;
-          for (int k = 0; k < m; ++k) obits |= (unsigned)mifx_shap_passes(e[k], xi[e[k].i]) << k;
-          mifx_shap_leaf_m(m, e, obits, hd.a, [&](int j, double x) { phi[j] += x; });
+    for (long i = lo; i < hi; ++i)
+      shap_contribs_row(X + (size_t)i * f, f, recs, n_recs, base, out + (size_t)i * stride, nullptr);
+  });
+  return 0;
+}
+
+// Interaction values (XGBoost's pred_interactions) of the first n_leaves leaves of a path table for every row of a
+// row-major [n, f] table: out[r * stride + i * (f + 1) + j] is Phi[i][j] of row r, an (f + 1) x (f + 1) matrix.
+// leaf_off [n_leaves + 1]: the leaves' record offsets. feat_off [f + 1], feat_leaf, feat_pos: per feature the
+// ascending leaves whose path holds it and its element index there (mifx/gbdt/shap.py builds them); entries of
+// leaves >= n_leaves end a list. Cell (i, j), i != j < f, sums mifx_shap_leaf_skip's shares over feature i's
+// leaves in that order from 0; the diagonal is mifx_shap_diagonal of the row's contribution (the arithmetic of
+// mifx_gbdt_contribs); row and column f are zero but for the bias in (f, f). One matrix per data row and thread, so
+// the result does not depend on the thread count. -1: a table or an index that does not fit (checked before any row).
+int mifx_gbdt_interactions(const double* X, long n, int f, const MifxShapRec* recs, const int* leaf_off, int n_leaves,
+                           const int* feat_off, const int* feat_leaf, const int* feat_pos, double base, double* out,
+                           long stride, int threads) {
+  if (n < 0 || f < 1 || n_leaves < 0 || stride < (long)(f + 1) * (f + 1) || leaf_off[0] != 0) return -1;
+  for (int l = 0; l < n_leaves; ++l)  // leaf_off is the walk of the headers
+    if (leaf_off[l + 1] <= leaf_off[l] || recs[leaf_off[l]].i != leaf_off[l + 1] - leaf_off[l] - 1) return -1;
+  const long n_recs = leaf_off[n_leaves];
+  if (!shap_table_fits(recs, n_recs, f)) return -1;
+  std::vector<int> feat_end(f);  // the end of every list under this leaf limit
+  for (int i = 0; i < f; ++i) {
+    if (feat_off[i] < 0 || feat_off[i + 1] < feat_off[i]) return -1;
+    int q = feat_off[i], last = -1;
+    for (; q < feat_off[i + 1] && feat_leaf[q] < n_leaves; ++q) {
+      const int l = feat_leaf[q], c = feat_pos[q];
+      if (l <= last || c < 0 || c >= recs[leaf_off[l]].i || recs[leaf_off[l] + 1 + c].i != i) return -1;
+      last = l;
+    }
+    feat_end[i] = q;
+  }
+  const int w = f + 1;
+  const int chunks = (int)std::max<long>(1, std::min<long>(threads, n));
+  parallel_for(chunks, chunks, [&](int t) {
+    const long lo = n * t / chunks, hi = n * (t + 1) / chunks;
+    std::vector<double> phi(w);
+    std::vector<uint16_t> obits(std::max(1, n_leaves));  // every leaf's o bits of the row, taken once
+    for (long r = lo; r < hi; ++r) {
+      double* M = out + (size_t)r * stride;
+      shap_contribs_row(X + (size_t)r * f, f, recs, n_recs, base, phi.data(), obits.data());
+      for (int i = 0; i < f; ++i) {
+        double* row = M + (size_t)i * w;
+        for (int j = 0; j < w; ++j) row[j] = 0.0;
+        for (int q = feat_off[i]; q < feat_end[i]; ++q) {
+          const MifxShapRec* hd = recs + leaf_off[feat_leaf[q]];
+          mifx_shap_leaf_skip_m(hd->i, hd + 1, feat_pos[q], obits[feat_leaf[q]], hd->a,
+                                [&](int j, double x) { row[j] += x; });
         }
-        pos += 1 + m;
+        row[i] = mifx_shap_diagonal(phi[i], f, i, [&](int j) { return row[j]; });
       }
-      phi[f] = bias;
+      for (int j = 0; j < f; ++j) M[(size_t)f * w + j] = 0.0;
+      M[(size_t)f * w + f] = phi[f];
     }
   });
   return 0;

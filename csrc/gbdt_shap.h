@@ -1,6 +1,8 @@
 // Path-dependent TreeSHAP in path form: ONE copy of the per-(row, leaf) arithmetic, included by the host function
 // (csrc/gbdt.cpp, mifx_gbdt_contribs) and by the device kernel (csrc/gbdt_prep.hip, k_contribs), which therefore
-// agree bit for bit: + - * / and comparisons only, nothing contracted into FMAs.
+// agree bit for bit: + - * / and comparisons only, nothing contracted into FMAs. The interaction values
+// (mifx_gbdt_interactions, and k_interactions in csrc/gbdt_interactions.hip) run the same routine over a leaf without
+// one of its elements (mifx_shap_leaf_skip, at the end of this file).
 //
 // The path table (built once per model by mifx_gbdt_paths_build in gbdt.cpp) is a flat array of 32-byte records.
 // Every leaf, trees in order and leaves in node order, is one header record followed by its m element records, one
@@ -49,15 +51,15 @@ MIFX_SHAP_HD bool mifx_shap_passes(const MifxShapRec& e, double x) {
   return !(x < e.b) && (!(e.j & MIFX_SHAP_HAS_HI) || x < e.c);
 }
 
-// One leaf with M elements e[0 .. M) for one row: bit k of obits is o of element k, v the leaf value.
-// add(feature, x) receives the M contributions in element order.
-template <int M, class Add>
-MIFX_SHAP_HD void mifx_shap_leaf(const MifxShapRec* e, unsigned obits, double v, Add&& add) {
+// One leaf with M elements at(0) .. at(M - 1) (references to their records) for one row: bit k of obits is o of
+// element k, v the leaf value. add(feature, x) receives the M contributions in element order.
+template <int M, class At, class Add>
+MIFX_SHAP_HD void mifx_shap_leaf_at(At&& at, unsigned obits, double v, Add&& add) {
   double w[M + 1];
   w[0] = 1.0;
 MIFX_SHAP_UNROLL
   for (int l = 1; l <= M; ++l) {  // EXTEND by element l - 1; the path then holds l + 1 elements
-    const double z = e[l - 1].a;
+    const double z = at(l - 1).a;
     const bool o = (obits >> (l - 1)) & 1u;
     w[l] = 0.0;
 MIFX_SHAP_UNROLL
@@ -69,7 +71,7 @@ MIFX_SHAP_UNROLL
   }
 MIFX_SHAP_UNROLL
   for (int k = 0; k < M; ++k) {  // UNWIND element k: the sum of the weights of the path without it
-    const double z = e[k].a;
+    const double z = at(k).a;
     const bool o = (obits >> k) & 1u;
     double total = 0.0;
     if (o) {
@@ -85,8 +87,14 @@ MIFX_SHAP_UNROLL
 MIFX_SHAP_UNROLL
       for (int i = M - 1; i >= 0; --i) total += (w[i] * rz) * ((double)(M + 1) / (double)(M - i));
     }
-    add(e[k].i, (total * ((o ? 1.0 : 0.0) - z)) * v);
+    add(at(k).i, (total * ((o ? 1.0 : 0.0) - z)) * v);
   }
+}
+
+// the elements in an array e[0 .. M)
+template <int M, class Add>
+MIFX_SHAP_HD void mifx_shap_leaf(const MifxShapRec* e, unsigned obits, double v, Add&& add) {
+  mifx_shap_leaf_at<M>([e](int k) -> const MifxShapRec& { return e[k]; }, obits, v, add);
 }
 
 // the same for a run-time m in [1, MIFX_SHAP_MAX_PATH] (uniform over a workgroup on the device: a scalar branch)
@@ -107,4 +115,51 @@ MIFX_SHAP_HD void mifx_shap_leaf_m(int m, const MifxShapRec* e, unsigned obits, 
     case 12: mifx_shap_leaf<12>(e, obits, v, add); break;
     default: break;
   }
+}
+
+// ---- interaction values (XGBoost's pred_interactions: one conditioned pass per feature of the path)
+//
+// Conditioning on element c of a leaf with M elements takes it off the path and scales the leaf by o_c ("on") or by
+// z_c ("off"); half the difference of the two passes is the leaf's share of Phi[feature_c][feature_j], j != c:
+//   (x_j * (o_c - z_c)) * 0.5,  x_j = what mifx_shap_leaf<M - 1> yields for element j over the elements without c
+// (element order, the unchanged v). obits holds all M bits; add(feature_j, share) is called M - 1 times, never for
+// c. The skipped index only addresses the records: the weights stay indexed by constants.
+template <int M, class Add>
+MIFX_SHAP_HD void mifx_shap_leaf_skip(const MifxShapRec* e, int c, unsigned obits, double v, Add&& add) {
+  if (M > 1) {
+    const double d = (((obits >> c) & 1u) ? 1.0 : 0.0) - e[c].a;
+    const unsigned low = (1u << c) - 1u;
+    const unsigned rest = (obits & low) | ((obits >> 1) & ~low);  // bit c taken out
+    mifx_shap_leaf_at<(M > 1 ? M - 1 : 1)>([e, c](int k) -> const MifxShapRec& { return e[k + (k >= c ? 1 : 0)]; },
+                                           rest, v, [&](int j, double x) { add(j, (x * d) * 0.5); });
+  }
+}
+
+// for a run-time m in [1, MIFX_SHAP_MAX_PATH] and c in [0, m), both uniform over a workgroup on the device
+template <class Add>
+MIFX_SHAP_HD void mifx_shap_leaf_skip_m(int m, const MifxShapRec* e, int c, unsigned obits, double v, Add&& add) {
+  switch (m) {
+    case 2: mifx_shap_leaf_skip<2>(e, c, obits, v, add); break;
+    case 3: mifx_shap_leaf_skip<3>(e, c, obits, v, add); break;
+    case 4: mifx_shap_leaf_skip<4>(e, c, obits, v, add); break;
+    case 5: mifx_shap_leaf_skip<5>(e, c, obits, v, add); break;
+    case 6: mifx_shap_leaf_skip<6>(e, c, obits, v, add); break;
+    case 7: mifx_shap_leaf_skip<7>(e, c, obits, v, add); break;
+    case 8: mifx_shap_leaf_skip<8>(e, c, obits, v, add); break;
+    case 9: mifx_shap_leaf_skip<9>(e, c, obits, v, add); break;
+    case 10: mifx_shap_leaf_skip<10>(e, c, obits, v, add); break;
+    case 11: mifx_shap_leaf_skip<11>(e, c, obits, v, add); break;
+    case 12: mifx_shap_leaf_skip<12>(e, c, obits, v, add); break;
+    default: break;  // m = 1: no pairs
+  }
+}
+
+// The diagonal cell of matrix row i from phi_i and the row's off-diagonal cells cell(j): phi_i minus their sum,
+// taken from 0 in ascending j.
+template <class Cell>
+MIFX_SHAP_HD double mifx_shap_diagonal(double phi_i, int f, int i, Cell&& cell) {
+  double s = 0.0;
+  for (int j = 0; j < f; ++j)
+    if (j != i) s += cell(j);
+  return phi_i - s;
 }

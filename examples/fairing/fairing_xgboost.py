@@ -43,6 +43,10 @@ def run_training_and_eval(device="cpu", subsample=1.0, colsample_bytree=1.0, col
     lead = np.argsort(-np.abs(contribs[:-1]))[:5]
     print(f"row 0: prediction {contribs.sum():.0f} = bias {contribs[-1]:.0f} " +
           " ".join(f"{contribs[j]:+.0f}[f{j}]" for j in lead) + " + the other columns")
+    pairs = model.predict_interactions(vx[:1])[0][:-1, :-1]  # [features, features]: main effects on the diagonal
+    i, j = np.unravel_index(np.argmax(np.abs(pairs - np.diag(np.diag(pairs)))), pairs.shape)
+    print(f"row 0: strongest interaction f{i} x f{j}: {pairs[i, j] + pairs[j, i]:+.0f} "
+          f"(main effects {pairs[i, i]:+.0f} and {pairs[j, j]:+.0f})")
     return mae
 
 

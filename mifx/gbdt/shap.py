@@ -1,6 +1,9 @@
 """Feature contributions of a forest on the host: the path table of csrc/gbdt_shap.h (built and validated by
 mifx_gbdt_paths_build in csrc/gbdt.cpp) and path-dependent TreeSHAP from it (mifx_gbdt_contribs). The device route
-(mifx/ops/gbdt_prep.py: DevicePaths, contribs) uploads the same table and returns the same bits."""
+(mifx/ops/gbdt_prep.py: DevicePaths, contribs) uploads the same table and returns the same bits.
+
+Interaction values (mifx_gbdt_interactions; on the device mifx/ops/gbdt_prep.py: interactions) walk, per feature, only
+the leaves whose path holds it: `PathTable.feature_leaves` is that index."""
 from __future__ import annotations
 
 import ctypes
@@ -33,7 +36,10 @@ def _fns():
     lib.mifx_gbdt_paths_build.restype = ctypes.c_int
     lib.mifx_gbdt_contribs.argtypes = [_D, lg, ctypes.c_int, vp, lg, ctypes.c_double, vp, lg, ctypes.c_int]
     lib.mifx_gbdt_contribs.restype = ctypes.c_int
-    return lib.mifx_gbdt_paths_build, lib.mifx_gbdt_contribs
+    lib.mifx_gbdt_interactions.argtypes = [_D, lg, ctypes.c_int, vp, _I, ctypes.c_int, _I, _I, _I, ctypes.c_double, vp,
+                                           lg, ctypes.c_int]
+    lib.mifx_gbdt_interactions.restype = ctypes.c_int
+    return lib.mifx_gbdt_paths_build, lib.mifx_gbdt_contribs, lib.mifx_gbdt_interactions
 
 
 class PathTable:
@@ -63,7 +69,7 @@ class PathTable:
         fe, le, ri = (cat(k, np.int32) for k in (0, 3, 4))
         thr, val, cov = (cat(k, np.float64) for k in (1, 5, 6))
         dl = cat(2, np.uint8)
-        build, _ = _fns()
+        build = _fns()[0]
         info = (ctypes.c_long * 3)()
 
         def call(recs, leaf_off, tree_leaf):
@@ -85,6 +91,25 @@ class PathTable:
         """Records of the first n_trees trees."""
         return int(self.leaf_off[self.tree_leaf[n_trees]])
 
+    def feature_leaves(self):
+        """The per-feature leaf lists, built once: int32 `off` [f + 1], `leaf` and `pos` (CSR: feature i's entries
+        are off[i] .. off[i + 1], the ascending leaves whose path holds i and i's element index in each) and `rec`
+        [entries + 1], the running sum of the listed leaves' record counts. The leaves of the first trees are a
+        prefix of every list, and a feature that never splits has an empty one."""
+        if getattr(self, "_feature_leaves", None) is None:
+            head = self.leaf_off[:-1]
+            m = self.recs["i"][head].astype(np.int64) if len(head) else np.zeros(0, np.int64)
+            leaf = np.repeat(np.arange(len(head)), m)
+            pos = np.arange(len(leaf)) - np.repeat(np.cumsum(m) - m, m)
+            feat = self.recs["i"][head.astype(np.int64)[leaf] + 1 + pos]
+            order = np.argsort(feat, kind="stable")  # within a feature the leaves stay ascending
+            off = np.concatenate([[0], np.cumsum(np.bincount(feat, minlength=self.nfeat))])
+            rec = np.concatenate([[0], np.cumsum(1 + m[leaf[order]])])
+            if rec[-1] >= 2 ** 31:
+                raise ValueError("the per-feature leaf lists hold 2^31 records or more")
+            self._feature_leaves = tuple(np.ascontiguousarray(a, np.int32) for a in (off, leaf[order], pos[order], rec))
+        return self._feature_leaves
+
 
 def contribs(table: PathTable, X: np.ndarray, n_trees: int, base: float, out: np.ndarray, threads: int) -> None:
     """out [n, >= f + 1] (a view with a row stride, unit column stride): the first n_trees trees' contributions per
@@ -96,5 +121,24 @@ def contribs(table: PathTable, X: np.ndarray, n_trees: int, base: float, out: np
         return
     rc = _fns()[1](X.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), len(X), table.nfeat, table.recs.ctypes.data,
                    table.n_recs(n_trees), float(base), out.ctypes.data, out.strides[0] // 8, int(threads))
+    if rc != 0:
+        raise ValueError("the path table does not fit the feature table")
+
+
+def interactions(table: PathTable, X: np.ndarray, n_trees: int, base: float, out: np.ndarray, threads: int) -> None:
+    """out [n, f + 1, f + 1] (a view with a row stride, the matrices contiguous): the first n_trees trees' interaction
+    values per row of the float64 [n, f] table X; cell (f, f) holds the bias of `contribs`."""
+    w = table.nfeat + 1
+    assert X.dtype == np.float64 and X.flags.c_contiguous and X.shape[1] == table.nfeat
+    assert out.dtype == np.float64 and out.shape == (len(X), w, w) and out.strides[1:] == (8 * w, 8)
+    assert out.strides[0] % 8 == 0 and 0 <= n_trees <= table.n_trees
+    if not len(X):
+        return
+    from .xgb import _I, _p
+
+    off, leaf, pos, _ = table.feature_leaves()
+    rc = _fns()[2](X.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), len(X), table.nfeat, table.recs.ctypes.data,
+                   _p(table.leaf_off, _I), int(table.tree_leaf[n_trees]), _p(off, _I), _p(leaf, _I), _p(pos, _I),
+                   float(base), out.ctypes.data, out.strides[0] // 8, int(threads))
     if rc != 0:
         raise ValueError("the path table does not fit the feature table")

@@ -47,7 +47,10 @@ between the device and its host twin. XGBoost's `loss_chg` is 2 * (gain + gamma)
 importances are the same quantity. `get_score(importance_type)` and `feature_importances_` (constructor argument
 `importance_type`, default "gain") are XGBoost's; `predict_contribs(X)` is its `pred_contribs`: exact path-dependent
 TreeSHAP in margin space, on the host (csrc/gbdt.cpp) for host input and on the GPU (csrc/gbdt_prep.hip) for a device
-tensor, the same bits. `pred_interactions` and approximate (Saabas) contributions are not implemented."""
+tensor, the same bits. `predict_interactions(X)` is its `pred_interactions`: the (f + 1) x (f + 1) SHAP interaction
+values per row from the same path tables, one conditioned pass per feature over the leaves that hold it, on the host
+(mifx_gbdt_interactions) or on the GPU (csrc/gbdt_interactions.hip), the same bits. Approximate (Saabas)
+contributions are not implemented."""
 from __future__ import annotations
 
 import ctypes
@@ -596,6 +599,17 @@ class _Base:
             self._dev_paths = None
         return cache[1]
 
+    def _device_paths(self, dev, tables):
+        """The path tables on `dev`, uploaded once per model and device (fit and a new tree limit reset them)."""
+        from ..ops import gbdt_prep as P
+
+        cache = getattr(self, "_dev_paths", None)
+        if cache is None:
+            cache = self._dev_paths = {}
+        if dev.index not in cache:
+            cache[dev.index] = [P.DevicePaths(t, dev) for t in tables]
+        return cache[dev.index]
+
     def predict_contribs(self, X, _recs_per_chunk: int | None = None, _route: str | None = None):
         """Per-row feature contributions in margin space (XGBoost's pred_contribs: path-dependent TreeSHAP):
         [n, f + 1], or [n, K, f + 1] for a K-class model; column j < f is feature j's Shapley value in the game whose
@@ -619,15 +633,10 @@ class _Base:
             from ..ops import gbdt_prep as P
 
             torch = sys.modules["torch"]
-            cache = getattr(self, "_dev_paths", None)
-            if cache is None:
-                cache = self._dev_paths = {}
-            if X.device.index not in cache:  # the tables, uploaded once per model and device (fit resets them)
-                cache[X.device.index] = [P.DevicePaths(t, X.device) for t in tables]
             Xd = P.as_device_matrix(X, X.device)
             out = torch.empty((len(Xd), K, f + 1), dtype=torch.float64, device=X.device)
             for k in range(K if len(Xd) else 0):  # one launch per class over the class's own table
-                P.contribs(cache[X.device.index][k], Xd, self._base_margin, out[:, k, :], counts[k],
+                P.contribs(self._device_paths(X.device, tables)[k], Xd, self._base_margin, out[:, k, :], counts[k],
                            _recs_per_chunk, _route)
             return out[:, 0, :] if K == 1 else out
         X = np.ascontiguousarray(_host(X), dtype=np.float64)
@@ -635,6 +644,43 @@ class _Base:
         for k in range(K):
             shap.contribs(tables[k], X, counts[k], self._base_margin, out[:, k, :], self._nthreads())
         return out[:, 0, :] if K == 1 else out
+
+    def predict_interactions(self, X, _recs_per_chunk: int | None = None, _route: str | None = None,
+                             _threads: int | None = None):
+        """Per-row SHAP interaction values in margin space (XGBoost's pred_interactions, path-dependent):
+        [n, f + 1, f + 1], or [n, K, f + 1, f + 1] for a K-class model, float64. Cell (i, j), i != j < f, is the
+        Shapley interaction index of features i and j in the game of predict_contribs; both (i, j) and (j, i) are
+        computed, each from its own conditioned pass, and agree to rounding. The diagonal (i, i) is feature i's
+        contribution minus the rest of row i, so row i sums to predict_contribs' column i and the matrix to the
+        margin; cell (f, f) is the bias and the rest of row and column f is zero.
+
+        Inputs, trees, devices and errors are predict_contribs': numpy or CPU input gives a numpy array from the
+        host function (threads: n_jobs, the same bits for any count), a tensor on a GPU a tensor there from the
+        device kernel with the same bits. The result takes 8 (f + 1)^2 bytes per row and class and is made in one
+        piece. The private arguments are the kernels' launch geometry."""
+        from . import shap
+
+        K, limit, f = self._num_class(), self._tree_limit(), self._nfeat
+        X = X if _is_tensor(X) else np.asarray(X)
+        if X.ndim != 2 or X.shape[1] != f:
+            raise ValueError(f"expected [n, {f}] features")
+        tables = self._path_tables(limit)
+        counts = [len(range(k, limit, K)) for k in range(K)]
+        if _on_gpu(X):
+            from ..ops import gbdt_prep as P
+
+            torch = sys.modules["torch"]
+            Xd = P.as_device_matrix(X, X.device)
+            out = torch.empty((len(Xd), K, f + 1, f + 1), dtype=torch.float64, device=X.device)
+            for k in range(K if len(Xd) else 0):  # one launch per class over the class's own table
+                P.interactions(self._device_paths(X.device, tables)[k], Xd, self._base_margin, out[:, k], counts[k],
+                               _recs_per_chunk, _route, _threads)
+            return out[:, 0] if K == 1 else out
+        X = np.ascontiguousarray(_host(X), dtype=np.float64)
+        out = np.empty((len(X), K, f + 1, f + 1), np.float64)
+        for k in range(K):
+            shap.interactions(tables[k], X, counts[k], self._base_margin, out[:, k], self._nthreads())
+        return out[:, 0] if K == 1 else out
 
 
 class XGBRegressor(_Base):

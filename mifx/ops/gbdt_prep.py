@@ -3,7 +3,8 @@ columns, binning of the raw table into the learner's row-major [n, f] uint16 lay
 features. Each equals its host function in csrc/gbdt.cpp exactly (mifx_gbdt_cuts, mifx_gbdt_bin, mifx_gbdt_predict).
 
 Feature contributions (`DevicePaths`, `contribs`): path-dependent TreeSHAP from the path table that the host builds
-(mifx/gbdt/shap.py), equal to the host's mifx_gbdt_contribs bit for bit.
+(mifx/gbdt/shap.py), equal to the host's mifx_gbdt_contribs bit for bit. Interaction values (`interactions`,
+csrc/gbdt_interactions.hip) from the same table and its per-feature leaf lists, equal to mifx_gbdt_interactions.
 
 The column sort is torch.sort on the device, one column at a time; everything else is the kernels of gbdt_prep.hip.
 The private `_...` arguments are launch geometry: no result depends on them."""
@@ -52,6 +53,19 @@ def _fns():
                                                              VP]),
     }
     assert fns["node_bytes"]() == NODE_DTYPE.itemsize
+    return fns
+
+
+@functools.lru_cache(maxsize=None)
+def _interaction_fns():
+    lib = _lib.load("gbdt_interactions")
+    fns = {
+        "min_chunk": sig(lib, "mifx_gbdt_interactions_min_chunk", []),
+        "max_lds": sig(lib, "mifx_gbdt_interactions_max_lds", []),
+        "launch": sig(lib, "mifx_gbdt_interactions_launch", [VP, I32, LONG, I32, VP, VP, I32, VP, VP, VP, VP, VP, LONG,
+                                                            I32, I32, I32, VP, LONG, VP]),
+    }
+    assert fns["max_lds"]() == _fns()["contrib_max_lds"]() and fns["min_chunk"]() == _fns()["contrib_min_chunk"]()
     return fns
 
 
@@ -279,6 +293,13 @@ class DevicePaths:
         self.table, self.nfeat, self.n_trees, self.dev = table, table.nfeat, table.n_trees, dev
         self.recs = torch.from_numpy(table.recs.view(np.uint8).reshape(-1)).to(dev)
         self.leaf_off = torch.from_numpy(table.leaf_off).to(dev)
+        self._feature_leaves = None
+
+    def feature_leaves(self):
+        """The table's per-feature leaf lists (PathTable.feature_leaves) on the device, uploaded on first use."""
+        if self._feature_leaves is None:
+            self._feature_leaves = tuple(torch.from_numpy(a).to(self.dev) for a in self.table.feature_leaves())
+        return self._feature_leaves
 
 
 def contrib_lds_threads(f: int, chunk: int | None = None) -> int:
@@ -287,6 +308,22 @@ def contrib_lds_threads(f: int, chunk: int | None = None) -> int:
     fns = _fns()
     room = fns["contrib_max_lds"]() - int(chunk or RECS_PER_CHUNK) * fns["contrib_rec_bytes"]()
     return next((t for t in (fns["contrib_threads"](), 128, 64) if f * t * 8 <= room), 0)
+
+
+def _contrib_geometry(f: int, _recs_per_chunk, _route, _threads):
+    """The validated (records per chunk, route, threads per workgroup) of a contribs or interactions launch."""
+    fns = _fns()
+    chunk = int(_recs_per_chunk or RECS_PER_CHUNK)
+    if chunk < fns["contrib_min_chunk"]() or chunk * fns["contrib_rec_bytes"]() > fns["contrib_max_lds"]():
+        raise ValueError("launch geometry out of range")
+    fits = contrib_lds_threads(f, chunk)
+    route = ("lds" if fits else "output") if _route is None else _route
+    if route not in ("lds", "output"):
+        raise ValueError(f"unknown route {route!r}")
+    threads = int(_threads or (fits if route == "lds" else fns["contrib_threads"]()))
+    if threads not in (64, 128, fns["contrib_threads"]()) or (route == "lds" and threads > fits):
+        raise ValueError(f"{f} sums per row of {threads} threads do not fit in LDS beside a chunk of {chunk} records")
+    return chunk, route, threads
 
 
 def contribs(paths: DevicePaths, Xd: torch.Tensor, base: float, out: torch.Tensor, n_trees: int | None = None,
@@ -309,19 +346,43 @@ def contribs(paths: DevicePaths, Xd: torch.Tensor, base: float, out: torch.Tenso
         raise ValueError(f"out must be a float64 [n, {f + 1}] tensor on {Xd.device} with unit column stride")
     fns = _fns()
     n_trees = paths.n_trees if n_trees is None else int(n_trees)
-    chunk = int(_recs_per_chunk or RECS_PER_CHUNK)
     if not 0 <= n_trees <= paths.n_trees:
         raise ValueError(f"n_trees must be in [0, {paths.n_trees}]")
-    if chunk < fns["contrib_min_chunk"]() or chunk * fns["contrib_rec_bytes"]() > fns["contrib_max_lds"]():
-        raise ValueError("launch geometry out of range")
-    fits = contrib_lds_threads(f, chunk)
-    route = ("lds" if fits else "output") if _route is None else _route
-    if route not in ("lds", "output"):
-        raise ValueError(f"unknown route {route!r}")
-    threads = int(_threads or (fits if route == "lds" else fns["contrib_threads"]()))
-    if threads not in (64, 128, fns["contrib_threads"]()) or (route == "lds" and threads > fits):
-        raise ValueError(f"{f} sums per row of {threads} threads do not fit in LDS beside a chunk of {chunk} records")
+    chunk, route, threads = _contrib_geometry(f, _recs_per_chunk, _route, _threads)
     with torch.cuda.device(Xd.device):
         check(fns["contribs"](ptr(Xd), int(Xd.dtype == torch.float64), n, f, ptr(paths.recs), ptr(paths.leaf_off),
                               int(paths.table.tree_leaf[n_trees]), float(base), chunk, threads, int(route == "lds"), ptr(out),
                               out.stride(0), stream_handle(Xd.device)), "mifx_gbdt_prep_contribs")
+
+
+def interactions(paths: DevicePaths, Xd: torch.Tensor, base: float, out: torch.Tensor, n_trees: int | None = None,
+                 _recs_per_chunk: int | None = None, _route: str | None = None, _threads: int | None = None) -> None:
+    """Interaction values (XGBoost's pred_interactions) of the first n_trees trees of `paths` per row of a device
+    table, written into `out` [n, f + 1, f + 1] (float64 on the device; a view with any row stride whose matrices are
+    contiguous, so a class's slice of [n, K, f + 1, f + 1] works). The bits of the host's mifx_gbdt_interactions.
+
+    One launch of `contribs` into a [n, f + 1] buffer (the diagonal and the bias come from it), then k_interactions
+    (csrc/gbdt_interactions.hip) on the same stream: one thread per (row, matrix row), the workgroups of matrix row i
+    walking the leaves that hold feature i. The private arguments are `contribs`' launch geometry, for both kernels:
+    the result does not depend on them."""
+    _check_matrix(Xd)
+    n, f = Xd.shape
+    w = f + 1
+    if f != paths.nfeat or Xd.device != paths.dev:
+        raise ValueError(f"expected [n, {paths.nfeat}] features on {paths.dev}")
+    if not (out.dtype == torch.float64 and out.device == Xd.device and tuple(out.shape) == (n, w, w)
+            and out.stride(2) == 1 and out.stride(1) == w and out.stride(0) >= w * w):
+        raise ValueError(f"out must be a float64 [n, {w}, {w}] tensor on {Xd.device} with contiguous matrices")
+    n_trees = paths.n_trees if n_trees is None else int(n_trees)
+    if not 0 <= n_trees <= paths.n_trees:
+        raise ValueError(f"n_trees must be in [0, {paths.n_trees}]")
+    chunk, route, threads = _contrib_geometry(f, _recs_per_chunk, _route, _threads)
+    phi = torch.empty((n, w), dtype=torch.float64, device=Xd.device)
+    contribs(paths, Xd, base, phi, n_trees, chunk, route, threads)
+    off, leaf, pos, rec = paths.feature_leaves()
+    with torch.cuda.device(Xd.device):
+        check(_interaction_fns()["launch"](
+            ptr(Xd), int(Xd.dtype == torch.float64), n, f, ptr(paths.recs), ptr(paths.leaf_off),
+            int(paths.table.tree_leaf[n_trees]), ptr(off), ptr(leaf), ptr(pos), ptr(rec), ptr(phi), phi.stride(0), chunk,
+            threads, int(route == "lds"), ptr(out), out.stride(0), stream_handle(Xd.device)),
+            "mifx_gbdt_interactions_launch")
