@@ -6,8 +6,10 @@ Feature contributions (`DevicePaths`, `contribs`): path-dependent TreeSHAP from 
 (mifx/gbdt/shap.py), equal to the host's mifx_gbdt_contribs bit for bit. Interaction values (`interactions`,
 csrc/gbdt_interactions.hip) from the same table and its per-feature leaf lists, equal to mifx_gbdt_interactions.
 
-The column sort is torch.sort on the device, one column at a time; everything else is the kernels of gbdt_prep.hip.
-The private `_...` arguments are launch geometry: no result depends on them."""
+The column sort is a batched keys-only radix sort of our own (`device_sort_columns`, csrc/gbdt_sort.hip): a group of
+columns of the row-major table sorts in the same launches. `device_cuts(_sort="torch")` keeps the earlier route, one
+torch.sort per column, as the reference for tests and measurements (profiles/gbdt_sort.md).
+The private `_...` arguments are launch geometry or routes: no result depends on them."""
 from __future__ import annotations
 
 import ctypes
@@ -25,6 +27,8 @@ CUT_BLOCKS = 1024         # workgroups of the run-start count over one sorted co
 ROWS_PER_WG = 1024        # rows one workgroup bins with one staging of its feature tile's cut tables
 FEAT_TILE = 32            # features per workgroup: 32 * 255 cuts * 8 B = 65,280 B of LDS
 NODES_PER_CHUNK = 2048    # packed nodes staged in LDS at a time: 2048 * 24 B = 48 KB
+SORT_TILE = 4096          # keys of one column that one workgroup counts and scatters per radix pass
+SORT_BUDGET = 8 << 30     # bytes of key buffers, sorted output and scratch of one group of columns (gbdt_sort.md)
 
 NODE_DTYPE = np.dtype([("v", np.float64), ("feature", np.int32), ("left", np.int32), ("right", np.int32),
                        ("default_left", np.int32)])
@@ -96,13 +100,70 @@ def _check_matrix(Xd: torch.Tensor) -> None:
         raise ValueError(f"the device path supports 1 <= n < 2^31 rows and f >= 1, got {tuple(Xd.shape)}")
 
 
-def device_cuts(Xd: torch.Tensor, max_bins: int, _blocks: int | None = None):
+@functools.lru_cache(maxsize=None)
+def _sort_fns():
+    lib = _lib.load("gbdt_sort")
+    return {
+        "key_bytes": sig(lib, "mifx_gbdt_sort_key_bytes", [I32]),
+        "tile_step": sig(lib, "mifx_gbdt_sort_tile_step", []),
+        "max_tile": sig(lib, "mifx_gbdt_sort_max_tile", []),
+        "max_group": sig(lib, "mifx_gbdt_sort_max_group", []),
+        "scratch_bytes": sig(lib, "mifx_gbdt_sort_scratch_bytes", [LONG, I32, I32, I32], LONG),
+        "launch": sig(lib, "mifx_gbdt_sort_launch", [VP, I32, LONG, I32, I32, I32, I32, VP, VP, VP, VP]),
+    }
+
+
+def _sort_tile(_tile) -> int:
+    fns = _sort_fns()
+    tile = int(_tile or SORT_TILE)
+    if not fns["tile_step"]() <= tile <= fns["max_tile"]() or tile % fns["tile_step"]():
+        raise ValueError(f"the sort tile must be a multiple of {fns['tile_step']()} up to {fns['max_tile']()}, "
+                         f"got {tile}")
+    return tile
+
+
+def device_sort_columns(Xd: torch.Tensor, j0: int = 0, j1: int | None = None, _tile: int | None = None):
+    """Columns [j0, j1) of a device table [n, f] (all by default), each sorted: (sorted [j1 - j0, n] float64, nan_count
+    [j1 - j0] int64), both on the device. Per column the non-NaN values come first in ascending order (-0.0 before
+    +0.0; a float32 table's values widened exactly), then the NaNs. One radix sort over all the columns at once
+    (csrc/gbdt_sort.hip), enqueued on the current stream; `_tile` (keys per workgroup) does not change the result."""
+    _check_matrix(Xd)
+    fns = _sort_fns()
+    n, f = Xd.shape
+    j0, j1 = int(j0), f if j1 is None else int(j1)
+    if not 0 <= j0 < j1 <= f:
+        raise ValueError(f"expected columns 0 <= j0 < j1 <= {f}, got [{j0}, {j1})")
+    if j1 - j0 > fns["max_group"]():
+        raise ValueError(f"at most {fns['max_group']()} columns sort at once, got {j1 - j0}")
+    tile, is64 = _sort_tile(_tile), int(Xd.dtype == torch.float64)
+    with torch.cuda.device(Xd.device):
+        scratch = torch.empty(fns["scratch_bytes"](n, j1 - j0, tile, is64), dtype=torch.uint8, device=Xd.device)
+        out = torch.empty((j1 - j0, n), dtype=torch.float64, device=Xd.device)
+        nan_count = torch.empty(j1 - j0, dtype=torch.int64, device=Xd.device)
+        check(fns["launch"](ptr(Xd), is64, n, f, j0, j1 - j0, tile, ptr(scratch), ptr(out), ptr(nan_count),
+                            stream_handle(Xd.device)), "mifx_gbdt_sort_launch")
+    return out, nan_count
+
+
+def sort_group(n: int, f: int, is64: bool, tile: int | None = None) -> int:
+    """The most columns (at most f) whose key buffers, sorted output and scratch stay inside SORT_BUDGET; at least 1."""
+    fns = _sort_fns()
+    per_column = fns["scratch_bytes"](n, 1, _sort_tile(tile), int(is64)) + 8 * n
+    return int(max(1, min(f, fns["max_group"](), SORT_BUDGET // per_column)))
+
+
+def device_cuts(Xd: torch.Tensor, max_bins: int, _blocks: int | None = None, _sort: str | None = None,
+                _group: int | None = None):
     """Per-feature cut points of a device table [n, f]: (cuts, cut_flat, cut_off, ncut) as XGB*._bin_matrix sets
     them on the host -- a list of f float64 arrays, their concatenation (one zero if there is none), the int32
-    offsets and counts. Each column is sorted by torch.sort (NaNs last), then one counting pass and max_bins - 1
-    binary searches pick the cuts; they come back to the host in one read at the end."""
+    offsets and counts. The columns are sorted (NaNs last) a group at a time by `device_sort_columns`, `_group`
+    columns per group (by default as many as SORT_BUDGET holds), or with `_sort="torch"` one at a time by torch.sort;
+    then per column one counting pass and max_bins - 1 binary searches pick the cuts. They come back to the host in
+    one read at the end. Neither `_sort` nor `_group` changes the result."""
     _check_matrix(Xd)
     fns = _fns()
+    if _sort not in (None, "radix", "torch"):
+        raise ValueError(f"unknown sort route {_sort!r}")
     max_bins, blocks = int(max_bins), int(_blocks or CUT_BLOCKS)
     if not 2 <= max_bins <= fns["max_bins"]():
         raise ValueError(f"max_bins must be in [2, {fns['max_bins']()}] on the device, got {max_bins}")
@@ -114,12 +175,22 @@ def device_cuts(Xd: torch.Tensor, max_bins: int, _blocks: int | None = None):
         cuts = torch.zeros((f, max_bins - 1), dtype=torch.float64, device=dev)
         count = torch.zeros(f, dtype=torch.int32, device=dev)
         scratch = torch.empty(fns["cut_scratch_bytes"](), dtype=torch.uint8, device=dev)
-        for j in range(f):
-            col = Xd[:, j].contiguous().to(torch.float64)
-            nan_count = torch.isnan(col).sum()
-            srt = torch.sort(col).values
-            check(fns["cuts"](ptr(srt), n, ptr(nan_count), max_bins, ptr(cuts[j]), ptr(count[j:]), ptr(scratch),
-                              blocks, stream_handle(dev)), "mifx_gbdt_prep_cuts")
+        if _sort == "torch":
+            for j in range(f):
+                col = Xd[:, j].contiguous().to(torch.float64)
+                nan_count = torch.isnan(col).sum()
+                srt = torch.sort(col).values
+                check(fns["cuts"](ptr(srt), n, ptr(nan_count), max_bins, ptr(cuts[j]), ptr(count[j:]), ptr(scratch),
+                                  blocks, stream_handle(dev)), "mifx_gbdt_prep_cuts")
+        else:
+            group = int(_group or sort_group(n, f, Xd.dtype == torch.float64))
+            if group < 1:
+                raise ValueError("launch geometry out of range")
+            for g0 in range(0, f, group):
+                srt, nan_count = device_sort_columns(Xd, g0, min(f, g0 + group))
+                for j in range(g0, min(f, g0 + group)):
+                    check(fns["cuts"](ptr(srt[j - g0]), n, ptr(nan_count[j - g0:]), max_bins, ptr(cuts[j]),
+                                      ptr(count[j:]), ptr(scratch), blocks, stream_handle(dev)), "mifx_gbdt_prep_cuts")
         ncut = count.cpu().numpy()
         table = cuts.cpu().numpy()
     out = [table[j, :ncut[j]].copy() for j in range(f)]

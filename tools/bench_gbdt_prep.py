@@ -6,7 +6,11 @@ Preparation, per size (standard-normal features, 32 of them, 256 bins):
   device  upload of the float64 table; per-column torch.sort (with the column copy and the NaN count); the cut kernels;
           the bin kernel -- each timed on its own (host clock around a window that ends in a device synchronise, after
           one warm-up pass), several repeats, min / median / max reported -- and the whole `device_cuts` + `device_bins`
-          as `fit` runs them now.
+          as `fit` runs them now (on its default sort route).
+  sort A/B  per size, for the float64 table, its float32 copy and a float64 table rounded to one decimal: the sort
+          step and `device_cuts` + `device_bins` on both routes of `device_cuts` -- "torch" (the per-column torch.sort
+          above) and "radix" (`device_sort_columns`, csrc/gbdt_sort.hip) -- in the same windows, the routes alternating
+          within every repeat; their cuts and bins are compared (and the float64 table's with the host's).
 Prediction (default 10^6 rows, 100 trees of depth 6): the host's mifx_gbdt_predict at --threads threads against the
 forest kernel, with and without the upload of X.
 
@@ -43,6 +47,10 @@ def main(argv=None) -> int:
     ap.add_argument("--host-repeats", type=int, default=2, help="timed repeats of the host preparation")
     ap.add_argument("--predict-rows", type=int, default=1_000_000, help="0: skip the prediction part")
     ap.add_argument("--predict-trees", type=int, default=100)
+    ap.add_argument("--no-rounded", dest="rounded", action="store_false",
+                    help="skip the sort A/B on the table rounded to one decimal")
+    ap.add_argument("--groups", type=int, nargs="*", default=[],
+                    help="also time the radix route with these many columns per group (float64 normal table)")
     ap.add_argument("--out", default=None, help="append one JSON line per measurement")
     a = ap.parse_args(argv)
 
@@ -139,7 +147,60 @@ def main(argv=None) -> int:
                    "cuts_equal_host": bool(same_cuts), "bins_equal_host": bool(same_bins)}
             emit(rec)
             ok = ok and same_cuts and same_bins
-            del X, bins
+            del bins
+
+            # the two sort routes of device_cuts side by side: "torch" (one torch.sort per column, with its column
+            # copy and NaN count) and "radix" (device_sort_columns, csrc/gbdt_sort.hip), alternating within a repeat
+            def radix_all(Xd, group):
+                return [P.device_sort_columns(Xd, g0, min(a.features, g0 + group))
+                        for g0 in range(0, a.features, group)]
+
+            def prepare_route(Xd, route, group=None):
+                c = P.device_cuts(Xd, a.max_bins, _sort=route, _group=group)
+                return c, P.device_bins(Xd, P.CutTables(c[1], c[2], c[3], dev))
+
+            tables_ab = [("normal", np.float64, X), ("normal", np.float32, X.astype(np.float32))]
+            if a.rounded:  # few distinct low mantissa bytes per column: where pass skipping should show
+                tables_ab.append(("rounded to 0.1", np.float64, np.round(X, 1)))
+            for name, dtype, Xh in tables_ab:
+                Xd = torch.from_numpy(Xh).to(dev)
+                group = P.sort_group(n, a.features, dtype is np.float64)
+                groups = [g for g in a.groups if g < a.features] if name == "normal" and dtype is np.float64 else []
+                t = {k: [] for k in ["torch_sort", "radix_sort", "torch_prepare", "radix_prepare"] +
+                     [f"radix_sort_group_{g}" for g in groups] + [f"radix_prepare_group_{g}" for g in groups]}
+                res = {}
+                for rep in range(a.repeats + 1):
+                    runs = [("torch_sort", lambda: sort_all(Xd)), ("radix_sort", lambda: radix_all(Xd, group)),
+                            ("torch_prepare", lambda: prepare_route(Xd, "torch")),
+                            ("radix_prepare", lambda: prepare_route(Xd, "radix"))]
+                    for g in groups:
+                        runs.append((f"radix_sort_group_{g}", lambda g=g: radix_all(Xd, g)))
+                        runs.append((f"radix_prepare_group_{g}", lambda g=g: prepare_route(Xd, "radix", g)))
+                    for key, fn in runs:
+                        out, ts = timed(fn, 1)
+                        if rep:
+                            t[key] += ts
+                        elif key.endswith("prepare"):
+                            res[key] = (out[0], out[1].cpu().numpy())
+                        del out
+                (ct, bt), (cr, br) = res["torch_prepare"], res["radix_prepare"]
+                same = all(np.array_equal(u, v) for u, v in zip(ct[0], cr[0])) and \
+                    all(np.array_equal(u, v) for u, v in zip(ct[1:], cr[1:])) and np.array_equal(bt, br)
+                if name == "normal" and dtype is np.float64:  # the host's tables are at hand for this one
+                    same = same and all(np.array_equal(u, v) for u, v in zip(cr[0], host._cuts))
+                med = {k: statistics.median(v) for k, v in t.items()}
+                margin = max(t["torch_prepare"]) - min(t["torch_prepare"])
+                emit({"what": "sort_ab", "n": n, "features": a.features, "max_bins": a.max_bins, "table": name,
+                      "dtype": np.dtype(dtype).name, "group": group, "tile": P.SORT_TILE,
+                      **{k + "_s": spread(v) for k, v in t.items()},
+                      "torch_over_radix_sort": round(med["torch_sort"] / med["radix_sort"], 2),
+                      "torch_over_radix_prepare": round(med["torch_prepare"] / med["radix_prepare"], 2),
+                      "radix_within_torch_spread": bool(med["radix_prepare"] <= med["torch_prepare"] + margin),
+                      "routes_equal": bool(same)})
+                ok = ok and same
+                del Xd, res
+                torch.cuda.empty_cache()
+            del X, tables_ab
 
         if a.predict_rows:
             n = a.predict_rows
