@@ -18,6 +18,10 @@
 // mifx_gbdt_grow_fixed is the same learner on fixed-point (int64) histograms with the split rule of gbdt_split.h:
 // the host twin of the device learner in gbdt_gpu.hip (larger tables, device="gpu"), which it reproduces bit for bit.
 //
+// Leaf-wise growth (the *_lossguide_stats entries): the open leaf with the largest gain is split next until a leaf
+// budget is reached; one driver over the double and the fixed-point arithmetic, the latter the host twin of
+// csrc/gbdt_lossguide.hip.
+//
 // Stochastic boosting (the *_ex entries): a tree is grown on a list of sampled rows as if the table held only them,
 // and a [max_depth, f] mask names the features each level may split on; the draws themselves are gbdt_sample.h's.
 //
@@ -518,6 +522,334 @@ int mifx_gbdt_grow_fixed(const uint16_t* bins, long n, int f, const int* nbins, 
   return mifx_gbdt_grow_fixed_ex(bins, n, f, nbins, g, h, max_depth, min_child_weight, lambda, gamma, eta, threads,
                                  max_nodes, feature, split_bin, default_left, left, right, value, leaf_of_row, nullptr,
                                  0, nullptr);
+}
+
+}  // extern "C"
+
+// ---- leaf-wise growth (grow_policy="lossguide"): the open node with the largest gain is split next (ties: the lowest
+// id), until max_leaves leaves exist or no node is open; children take the next two ids, left then right. A node's
+// candidate is its depth-wise one (same histograms, same scan), so the tree is the best-first prefix of the depth-wise
+// tree with the same depth limit. One driver; a Core supplies the arithmetic of one learner.
+namespace {
+
+struct LgArgs {
+  const uint16_t* bins;
+  long n;
+  int f;
+  const int* nbins;
+  const float *g, *h;
+  int max_depth, max_leaves;  // max_depth 0: no limit
+  double min_child_weight, lambda, gamma, eta;
+  int threads, max_nodes;
+  int *feature, *split_bin;
+  uint8_t* default_left;
+  int *left, *right;
+  double* value;
+  int* leaf_of_row;
+  const int* sample;
+  long n_rows;
+  const uint8_t* feature_mask;  // [f], null = all
+  double *node_gain, *node_cover;
+};
+
+struct LgCand {  // a node's candidate in either arithmetic
+  double gain = 0.0;
+  int feature = -1, bin = -1, default_left = 0;
+  bool leaf = true;
+};
+
+// the double learner of mifx_gbdt_grow_stats: smaller child built in row order, larger = parent - smaller
+struct DoubleCore {
+  struct Node {
+    int begin, end, depth, id;
+    LgCand cand;
+    double g = 0, h = 0, gl = 0, hl = 0;  // sums; the candidate's left sums
+    std::vector<Hist> hist;
+  };
+  const LgArgs& a;
+  const std::vector<int>& off;
+  const std::vector<int>& rows;
+  int th;
+  void start(Node& root) {
+    for (int r : rows) {
+      root.g += a.g[r];
+      root.h += a.h[r];
+    }
+  }
+  void build(Node& nd) {
+    nd.hist.assign(off[a.f], Hist{0.0, 0.0});
+    parallel_for(a.f, th, [&](int j) {
+      Hist* hj = nd.hist.data() + off[j];
+      const uint16_t* bj = a.bins + (size_t)j * a.n;
+      for (int k = nd.begin; k < nd.end; ++k) {
+        const uint16_t b = bj[rows[k]];
+        Hist& e = hj[b == kMissing ? a.nbins[j] : b];
+        e.g += a.g[rows[k]];
+        e.h += a.h[rows[k]];
+      }
+    });
+  }
+  void inherit(Node& large, Node& parent, const Node& small) {
+    large.hist = std::move(parent.hist);
+    for (size_t k = 0; k < large.hist.size(); ++k) {
+      large.hist[k].g -= small.hist[k].g;
+      large.hist[k].h -= small.hist[k].h;
+    }
+  }
+  void release(Node& nd) { std::vector<Hist>().swap(nd.hist); }
+  void search(Node& nd) {
+    std::vector<Split> per(a.f);
+    auto score = [&](double G, double H) { return G * G / (H + a.lambda); };
+    const double parent = score(nd.g, nd.h);
+    parallel_for(a.f, th, [&](int j) {
+      const Hist* hj = nd.hist.data() + off[j];
+      const int nb = a.feature_mask && !a.feature_mask[j] ? 1 : a.nbins[j];
+      const double gm = hj[a.nbins[j]].g, hm = hj[a.nbins[j]].h;
+      Split bs;
+      double gl = 0, hl = 0;
+      for (int b = 0; b + 1 < nb; ++b) {
+        gl += hj[b].g;
+        hl += hj[b].h;
+        for (int dir = 0; dir < 2; ++dir) {
+          if (dir == 1 && hm == 0.0 && gm == 0.0) break;
+          const double GL = gl + (dir ? gm : 0.0), HL = hl + (dir ? hm : 0.0);
+          const double GR = nd.g - GL, HR = nd.h - HL;
+          if (HL < a.min_child_weight || HR < a.min_child_weight) continue;
+          const double gain = 0.5 * (score(GL, HL) + score(GR, HR) - parent) - a.gamma;
+          if (gain > bs.gain) {
+            bs.gain = gain, bs.feature = j, bs.bin = b, bs.default_left = dir == 1;
+            bs.gl = GL, bs.hl = HL, bs.gr = GR, bs.hr = HR;
+          }
+        }
+      }
+      per[j] = bs;
+    });
+    Split best;
+    for (int j = 0; j < a.f; ++j)
+      if (per[j].feature >= 0 && per[j].gain > best.gain + 1e-12 * std::fabs(best.gain)) best = per[j];
+    nd.cand = LgCand{best.gain, best.feature, best.bin, best.default_left, best.feature < 0 || best.gain <= 1e-6};
+    nd.gl = best.gl, nd.hl = best.hl;
+  }
+  bool goes_left(const LgCand& c, int r) const {
+    const uint16_t b = a.bins[(size_t)c.feature * a.n + r];
+    return b == kMissing ? c.default_left != 0 : (int)b <= c.bin;
+  }
+  void children(const Node& p, Node& L, Node& R) const {
+    L.g = p.gl, L.h = p.hl;
+    R.g = p.g - p.gl, R.h = p.h - p.hl;  // (the depth-wise learner's GR, HR)
+  }
+  double value(const Node& nd) const { return -a.eta * nd.g / (nd.h + a.lambda); }
+  double cover(const Node& nd) const { return nd.h; }
+};
+
+// the fixed-point learner of mifx_gbdt_grow_fixed_stats (gbdt_split.h): the device twin
+struct FixedCore {
+  struct Node {
+    int begin, end, depth, id;
+    LgCand cand;
+    long long g = 0, h = 0, gl = 0, hl = 0;
+    std::vector<long long> hg, hh;
+    std::vector<int> hc;
+  };
+  const LgArgs& a;
+  const std::vector<int>& off;
+  const std::vector<int>& rows;
+  int th;
+  MifxGbParams prm{a.lambda, a.gamma, a.min_child_weight, a.eta};
+  int eg = 0, eh = 0;
+  std::vector<long long> qg, qh;  // by row id; rows outside the sample are never read
+  void start(Node& root) {
+    const long ns = (long)rows.size();
+    auto amax = [&](const float* v) {
+      double m = 0.0;
+      for (int r : rows) {
+        const double x = std::fabs((double)v[r]);
+        if (!(x <= m)) m = x;  // a NaN sticks: the exponent is then 0
+        if (std::isnan(x)) return x;
+      }
+      return m;
+    };
+    eg = mifx_gb_quant_exp(amax(a.g), ns), eh = mifx_gb_quant_exp(amax(a.h), ns);
+    qg.assign(a.n, 0), qh.assign(a.n, 0);
+    for (int r : rows) {
+      root.g += qg[r] = mifx_gb_quantise(a.g[r], eg);
+      root.h += qh[r] = mifx_gb_quantise(a.h[r], eh);
+    }
+  }
+  void build(Node& nd) {
+    nd.hg.assign(off[a.f], 0), nd.hh.assign(off[a.f], 0), nd.hc.assign(off[a.f], 0);
+    parallel_for(a.f, th, [&](int j) {
+      const uint16_t* bj = a.bins + (size_t)j * a.n;
+      const int nb = a.nbins[j];
+      for (int k = nd.begin; k < nd.end; ++k) {
+        const int r = rows[k], b = bj[r], s = off[j] + (b < nb ? b : nb);  // anything past the bins: missing
+        nd.hg[s] += qg[r];
+        nd.hh[s] += qh[r];
+        nd.hc[s] += 1;
+      }
+    });
+  }
+  void inherit(Node& large, Node& parent, const Node& small) {
+    large.hg = std::move(parent.hg), large.hh = std::move(parent.hh), large.hc = std::move(parent.hc);
+    for (size_t k = 0; k < large.hg.size(); ++k) {
+      large.hg[k] -= small.hg[k];
+      large.hh[k] -= small.hh[k];
+      large.hc[k] -= small.hc[k];
+    }
+  }
+  void release(Node& nd) {
+    std::vector<long long>().swap(nd.hg);
+    std::vector<long long>().swap(nd.hh);
+    std::vector<int>().swap(nd.hc);
+  }
+  void search(Node& nd) {
+    std::vector<MifxGbSplit> per(a.f);
+    const double parent = mifx_gb_parent_score(nd.g, nd.h, eg, eh, prm);
+    parallel_for(a.f, th, [&](int j) {
+      MifxGbSplit bs = mifx_gb_no_split();
+      if (!a.feature_mask || a.feature_mask[j])
+        mifx_gb_scan(nd.hg.data() + off[j], nd.hh.data() + off[j], nd.hc.data() + off[j], a.nbins[j], 0, a.nbins[j], 0,
+                     0, 0, nd.g, nd.h, eg, eh, j, prm, parent, &bs);
+      per[j] = bs;
+    });
+    MifxGbSplit best = mifx_gb_no_split();
+    for (int j = 0; j < a.f; ++j)
+      if (mifx_gb_feature_wins(per[j], best)) best = per[j];
+    nd.cand = LgCand{best.gain, best.feature, best.bin, best.default_left, mifx_gb_is_leaf(best)};
+    nd.gl = best.gl, nd.hl = best.hl;
+  }
+  bool goes_left(const LgCand& c, int r) const {
+    const int b = a.bins[(size_t)c.feature * a.n + r];
+    return b < a.nbins[c.feature] ? b <= c.bin : c.default_left != 0;
+  }
+  void children(const Node& p, Node& L, Node& R) const {
+    L.g = p.gl, L.h = p.hl;
+    R.g = p.g - p.gl, R.h = p.h - p.hl;
+  }
+  double value(const Node& nd) const { return mifx_gb_leaf_value(nd.g, nd.h, eg, eh, prm); }
+  double cover(const Node& nd) const { return mifx_gb_dequant(nd.h, eh); }
+};
+
+template <class Core>
+int grow_lossguide(const LgArgs& a) {
+  using Node = typename Core::Node;
+  if (a.max_leaves < 1 || a.max_depth < 0) return -1;
+  if (!rows_ok(a.sample, a.n_rows, a.n)) return -2;
+  std::vector<int> off(a.f + 1, 0);
+  for (int j = 0; j < a.f; ++j) off[j + 1] = off[j] + a.nbins[j] + 1;
+  const long ns = a.sample ? a.n_rows : a.n;
+  std::vector<int> rows(ns);
+  for (long i = 0; i < ns; ++i) rows[i] = a.sample ? a.sample[i] : (int)i;
+  if (a.sample)
+    for (long i = 0; i < a.n; ++i) a.leaf_of_row[i] = -1;
+  Core core{a, off, rows, ns * (long)a.f > 200000 ? a.threads : 1};
+
+  std::vector<Node> nodes;  // by id; a node's histogram lives until the node is split or closed
+  std::vector<int> open;
+  auto add = [&](int begin, int end, int depth) -> Node* {
+    const int id = (int)nodes.size();
+    if (id >= a.max_nodes) return nullptr;
+    a.feature[id] = a.split_bin[id] = a.left[id] = a.right[id] = -1;
+    a.default_left[id] = 0;
+    a.value[id] = 0.0;
+    if (a.node_gain) a.node_gain[id] = 0.0;
+    if (a.node_cover) a.node_cover[id] = 0.0;
+    nodes.push_back(Node{begin, end, depth, id});
+    return &nodes.back();
+  };
+  auto can_split = [&](const Node& nd) {  // before any histogram: rows, the depth limit
+    return nd.end - nd.begin >= 2 && (a.max_depth == 0 || nd.depth < a.max_depth);
+  };
+  auto settle = [&](Node& nd) {  // the node's sums are known: its entry as a leaf
+    a.value[nd.id] = nd.end > nd.begin ? core.value(nd) : 0.0;
+    if (a.node_cover) a.node_cover[nd.id] = core.cover(nd);
+  };
+  nodes.reserve(2 * (size_t)a.max_leaves);  // (pointers into it stay valid)
+  Node* root = add(0, (int)ns, 0);
+  if (!root) return -1;
+  core.start(*root);
+  settle(*root);
+  int leaves = 1;
+  if (can_split(*root) && a.max_leaves >= 2) {
+    core.build(*root);
+    core.search(*root);
+    if (!root->cand.leaf) open.push_back(0);
+  }
+  while (leaves < a.max_leaves && !open.empty()) {
+    size_t at = 0;  // open holds ascending ids: strict > keeps the lowest id among equal gains
+    for (size_t i = 1; i < open.size(); ++i)
+      if (nodes[open[i]].cand.gain > nodes[open[at]].cand.gain) at = i;
+    Node& p = nodes[open[at]];
+    open.erase(open.begin() + at);
+    const LgCand c = p.cand;
+    const int mid = (int)(std::stable_partition(rows.begin() + p.begin, rows.begin() + p.end,
+                                                [&](int r) { return core.goes_left(c, r); }) - rows.begin());
+    Node *L = add(p.begin, mid, p.depth + 1), *R = add(mid, p.end, p.depth + 1);
+    if (!L || !R) return -1;
+    ++leaves;
+    a.feature[p.id] = c.feature;
+    a.split_bin[p.id] = c.bin;
+    a.default_left[p.id] = (uint8_t)c.default_left;
+    a.left[p.id] = L->id;
+    a.right[p.id] = R->id;
+    a.value[p.id] = 0.0;
+    if (a.node_gain) a.node_gain[p.id] = c.gain;
+    core.children(p, *L, *R);
+    settle(*L);
+    settle(*R);
+    // candidates only where a child can still be split (both children share the depth; the last split of the budget
+    // needs none): smaller child built, larger = parent - smaller
+    if ((a.max_depth == 0 || L->depth < a.max_depth) && leaves < a.max_leaves) {
+      Node& small = (L->end - L->begin) <= (R->end - R->begin) ? *L : *R;
+      Node& large = &small == L ? *R : *L;
+      core.build(small);
+      core.inherit(large, p, small);
+      for (Node* ch : {L, R})
+        if (can_split(*ch)) {
+          core.search(*ch);
+          if (!ch->cand.leaf) open.push_back(ch->id);
+        }
+      for (Node* ch : {L, R})
+        if (ch->cand.leaf) core.release(*ch);  // closed: its histogram is never read again
+    }
+    core.release(p);
+  }
+  for (const Node& nd : nodes)
+    if (a.feature[nd.id] < 0)
+      for (int k = nd.begin; k < nd.end; ++k) a.leaf_of_row[rows[k]] = nd.id;
+  return (int)nodes.size();
+}
+
+}  // namespace
+
+extern "C" {
+
+// Leaf-wise twins of mifx_gbdt_grow_stats / mifx_gbdt_grow_fixed_stats: the same arguments, and max_leaves (>= 1);
+// max_depth 0 means no depth limit; the tree arrays hold max_nodes >= 2 * max_leaves - 1 entries; feature_mask
+// (null = all): [f], the features the tree may split on. mifx_gbdt_grow_fixed_lossguide_stats is the host twin of
+// the device grower in csrc/gbdt_lossguide.hip.
+int mifx_gbdt_grow_lossguide_stats(const uint16_t* bins, long n, int f, const int* nbins, const float* g,
+                                   const float* h, int max_depth, int max_leaves, double min_child_weight,
+                                   double lambda, double gamma, double eta, int threads, int max_nodes, int* feature,
+                                   int* split_bin, uint8_t* default_left, int* left, int* right, double* value,
+                                   int* leaf_of_row, const int* sample, long n_rows, const uint8_t* feature_mask,
+                                   double* node_gain, double* node_cover) {
+  return grow_lossguide<DoubleCore>(LgArgs{bins, n, f, nbins, g, h, max_depth, max_leaves, min_child_weight, lambda,
+                                           gamma, eta, threads, max_nodes, feature, split_bin, default_left, left,
+                                           right, value, leaf_of_row, sample, n_rows, feature_mask, node_gain,
+                                           node_cover});
+}
+
+int mifx_gbdt_grow_fixed_lossguide_stats(const uint16_t* bins, long n, int f, const int* nbins, const float* g,
+                                         const float* h, int max_depth, int max_leaves, double min_child_weight,
+                                         double lambda, double gamma, double eta, int threads, int max_nodes,
+                                         int* feature, int* split_bin, uint8_t* default_left, int* left, int* right,
+                                         double* value, int* leaf_of_row, const int* sample, long n_rows,
+                                         const uint8_t* feature_mask, double* node_gain, double* node_cover) {
+  return grow_lossguide<FixedCore>(LgArgs{bins, n, f, nbins, g, h, max_depth, max_leaves, min_child_weight, lambda,
+                                          gamma, eta, threads, max_nodes, feature, split_bin, default_left, left,
+                                          right, value, leaf_of_row, sample, n_rows, feature_mask, node_gain,
+                                          node_cover});
 }
 
 // Sum of the first n_trees trees' outputs for each row of a row-major [n, f] matrix of raw values. Trees are

@@ -43,6 +43,7 @@
 
 #include <algorithm>
 
+#include "gbdt_quant.h"  // the quantise stage (shared with csrc/gbdt_lossguide.hip), kThreads, Carver, add64
 #include "gbdt_sample.h"
 #include "gbdt_split.h"
 
@@ -52,9 +53,6 @@ constexpr int kMaxBins = 256;          // bins per feature
 constexpr int kSlots = kMaxBins + 1;   // LDS slots per feature: the bins and "missing"
 constexpr int kMaxDepth = 12;
 constexpr int kMaxFeatTile = 12;       // 12 * 257 * 20 B = 61,680 B of LDS
-constexpr int kThreads = 256;
-
-typedef unsigned long long u64;
 
 struct Level {  // the nodes of one depth, in the host learner's order (= ascending row ranges)
   int *id, *begin, *end;
@@ -88,17 +86,7 @@ struct Ws {
   int* hc;
   int* nsamp;  // [2] sampled rows: their count (k_amax_s), the compaction cursor (k_quant_s)
   size_t bytes;
-};
-
-struct Carver {
-  char* base;
-  size_t used = 0;
-  template <class T>
-  T* take(size_t count) {
-    T* r = base ? reinterpret_cast<T*>(base + used) : nullptr;
-    used += (count * sizeof(T) + 255) & ~(size_t)255;
-    return r;
-  }
+  Quant quant() const { return Quant{qg, qh, perm[0], amax, exps, nsamp, lv[0].qg, lv[0].qh, lv[0].end}; }
 };
 
 Ws carve(void* base, long n, int f, int max_depth, int hsize) {
@@ -136,8 +124,6 @@ Ws carve(void* base, long n, int f, int max_depth, int hsize) {
   w.bytes = c.used;
   return w;
 }
-
-__device__ __forceinline__ void add64(long long* p, long long v) { atomicAdd(reinterpret_cast<u64*>(p), (u64)v); }
 
 // ---- gradients: the formulas of XGBRegressor / XGBClassifier._grad_hess
 // wt (nullable): instance weights; the float32 pair times the float32 weight, one IEEE multiply each
@@ -192,168 +178,17 @@ __global__ void k_grad_softmax(const double* margin, const double* y, const floa
   }
 }
 
+// before the quantise stage (gbdt_quant.h): what it accumulates into, and the root's fixed fields
 __global__ void k_init(Ws w) {
   if (threadIdx.x < 2) w.amax[threadIdx.x] = 0u;
   if (threadIdx.x == 2) w.lv[0].qg[0] = 0;
   if (threadIdx.x == 3) w.lv[0].qh[0] = 0;
   if (threadIdx.x == 4 || threadIdx.x == 5) w.nsamp[threadIdx.x - 4] = 0;
-}
-
-// max |g|, max |h| as bit patterns: non-negative floats order like their bits, and a NaN sorts above infinity
-__global__ void k_amax(const float* g, const float* h, long n, unsigned* amax) {
-  unsigned mg = 0, mh = 0;
-  for (long i = blockIdx.x * (long)kThreads + threadIdx.x; i < n; i += (long)gridDim.x * kThreads) {
-    mg = max(mg, __float_as_uint(fabsf(g[i])));
-    mh = max(mh, __float_as_uint(fabsf(h[i])));
-  }
-  for (int o = 32; o; o >>= 1) {
-    mg = max(mg, (unsigned)__shfl_xor((int)mg, o));
-    mh = max(mh, (unsigned)__shfl_xor((int)mh, o));
-  }
-  if ((threadIdx.x & 63) == 0) {
-    atomicMax(amax, mg);
-    atomicMax(amax + 1, mh);
-  }
-}
-
-__global__ void k_quant(const float* g, const float* h, long n, Ws w) {
-  const int eg = mifx_gb_quant_exp((double)__uint_as_float(w.amax[0]), n);
-  const int eh = mifx_gb_quant_exp((double)__uint_as_float(w.amax[1]), n);
-  long long sg = 0, sh = 0;
-  for (long i = blockIdx.x * (long)kThreads + threadIdx.x; i < n; i += (long)gridDim.x * kThreads) {
-    const long long a = mifx_gb_quantise(g[i], eg), b = mifx_gb_quantise(h[i], eh);
-    w.qg[i] = a;
-    w.qh[i] = b;
-    w.perm[0][i] = (int)i;
-    sg += a;
-    sh += b;
-  }
-  for (int o = 32; o; o >>= 1) {
-    sg += __shfl_xor(sg, o);
-    sh += __shfl_xor(sh, o);
-  }
-  if ((threadIdx.x & 63) == 0) {
-    add64(w.lv[0].qg, sg);
-    add64(w.lv[0].qh, sh);
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    w.exps[0] = eg;
-    w.exps[1] = eh;
+  if (threadIdx.x == 6) {
     w.lv[0].id[0] = 0;
     w.lv[0].begin[0] = 0;
-    w.lv[0].end[0] = (int)n;
     w.lcount[0] = 1;
     *w.ncount = 1;
-  }
-}
-
-// ---- subsample < 1: the quantise stage over the sampled rows only. Row i is sampled iff mifx_gs_keep_row(key, i,
-// thr); both kernels hash (a few integer multiplies per row) instead of storing a mask. One atomic per workgroup and
-// word: the per-wave form of k_amax / k_quant runs at the same-address atomic rate (profiles/gbdt_gpu.md).
-constexpr int kWaves = kThreads / 64;
-
-__global__ __launch_bounds__(kThreads) void k_amax_s(const float* g, const float* h, long n, u64 key, u64 thr,
-                                                     unsigned* amax, int* nsamp) {
-  __shared__ unsigned s_g[kWaves], s_h[kWaves];
-  __shared__ int s_c[kWaves];
-  unsigned mg = 0, mh = 0;
-  int c = 0;
-  for (long i = blockIdx.x * (long)kThreads + threadIdx.x; i < n; i += (long)gridDim.x * kThreads)
-    if (mifx_gs_keep_row(key, (u64)i, thr)) {
-      mg = max(mg, __float_as_uint(fabsf(g[i])));
-      mh = max(mh, __float_as_uint(fabsf(h[i])));
-      ++c;
-    }
-  for (int o = 32; o; o >>= 1) {
-    mg = max(mg, (unsigned)__shfl_xor((int)mg, o));
-    mh = max(mh, (unsigned)__shfl_xor((int)mh, o));
-    c += __shfl_xor(c, o);
-  }
-  if ((threadIdx.x & 63) == 0) {
-    s_g[threadIdx.x >> 6] = mg;
-    s_h[threadIdx.x >> 6] = mh;
-    s_c[threadIdx.x >> 6] = c;
-  }
-  __syncthreads();
-  if (threadIdx.x != 0) return;
-  for (int v = 1; v < kWaves; ++v) {
-    mg = max(mg, s_g[v]);
-    mh = max(mh, s_h[v]);
-    c += s_c[v];
-  }
-  if (c == 0) return;
-  atomicMax(amax, mg);
-  atomicMax(amax + 1, mh);
-  atomicAdd(nsamp, c);
-}
-
-__global__ __launch_bounds__(kThreads) void k_quant_s(const float* g, const float* h, long n, u64 key, u64 thr, Ws w,
-                                                      int* leaf_of_row) {
-  __shared__ int s_c[kWaves], s_base;
-  __shared__ long long s_g[kWaves], s_h[kWaves];
-  const int ns = w.nsamp[0];
-  const int eg = mifx_gb_quant_exp((double)__uint_as_float(w.amax[0]), ns);
-  const int eh = mifx_gb_quant_exp((double)__uint_as_float(w.amax[1]), ns);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  // the workgroup's sampled rows over its grid-stride share, then ONE returning atomic for its range of perm[0]
-  int c = 0;
-  for (long i = blockIdx.x * (long)kThreads + threadIdx.x; i < n; i += (long)gridDim.x * kThreads)
-    c += mifx_gs_keep_row(key, (u64)i, thr);
-  for (int o = 32; o; o >>= 1) c += __shfl_xor(c, o);
-  if (lane == 0) s_c[wave] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int tot = 0;
-    for (int v = 0; v < kWaves; ++v) tot += s_c[v];
-    s_base = tot ? atomicAdd(&w.nsamp[1], tot) : 0;
-  }
-  __syncthreads();
-  int cur = s_base;  // uniform over the wave: where this wave's next sampled row goes
-  for (int v = 0; v < wave; ++v) cur += s_c[v];
-  long long sg = 0, sh = 0;
-  // the same rows as above, a wave at a time (the trip count is uniform over the wave: every lane reaches the ballot)
-  for (long i0 = blockIdx.x * (long)kThreads + wave * 64; i0 < n; i0 += (long)gridDim.x * kThreads) {
-    const long i = i0 + lane;
-    const bool kp = i < n && mifx_gs_keep_row(key, (u64)i, thr);
-    const u64 m = __ballot(kp);
-    if (kp) {
-      const long long a = mifx_gb_quantise(g[i], eg), b = mifx_gb_quantise(h[i], eh);
-      w.qg[i] = a;
-      w.qh[i] = b;
-      const int pos = cur + __popcll(m & (((u64)1 << lane) - 1));
-      if ((unsigned)pos < (unsigned long)n) w.perm[0][pos] = (int)i;
-      sg += a;
-      sh += b;
-    } else if (i < n) {
-      leaf_of_row[i] = -1;
-    }
-    cur += __popcll(m);
-  }
-  for (int o = 32; o; o >>= 1) {
-    sg += __shfl_xor(sg, o);
-    sh += __shfl_xor(sh, o);
-  }
-  if (lane == 0) {
-    s_g[wave] = sg;
-    s_h[wave] = sh;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int v = 1; v < kWaves; ++v) {
-      sg += s_g[v];
-      sh += s_h[v];
-    }
-    if (sg) add64(w.lv[0].qg, sg);
-    if (sh) add64(w.lv[0].qh, sh);
-    if (blockIdx.x == 0) {
-      w.exps[0] = eg;
-      w.exps[1] = eh;
-      w.lv[0].id[0] = 0;
-      w.lv[0].begin[0] = 0;
-      w.lv[0].end[0] = ns;
-      w.lcount[0] = 1;
-      *w.ncount = 1;
-    }
   }
 }
 
@@ -622,8 +457,6 @@ __global__ void k_apply(const uint16_t* bins, long m, int f, const int* nbins, T
   margin[i] += t.value[k];
 }
 
-int grid_for(long n, int cap = 4096) { return (int)std::max<long>(1, std::min<long>((n + kThreads - 1) / kThreads, cap)); }
-
 }  // namespace
 
 extern "C" {
@@ -694,14 +527,7 @@ int mifx_gbdt_gpu_grow_stats(const uint16_t* bins, long n, int f, const int* nbi
   const TreeOut t{feature, split_bin, default_left, left, right, value, node_gain, node_cover};
   const int cap = 1 << (max_depth + 1);
   k_init<<<1, 64, 0, stream>>>(w);
-  if (sampled) {
-    const u64 key = mifx_gs_key(seed, round, MIFX_GS_SITE_ROWS);
-    k_amax_s<<<grid_for(n), kThreads, 0, stream>>>(g, h, n, key, thr, w.amax, w.nsamp);
-    k_quant_s<<<grid_for(n), kThreads, 0, stream>>>(g, h, n, key, thr, w, leaf_of_row);
-  } else {
-    k_amax<<<grid_for(n), kThreads, 0, stream>>>(g, h, n, w.amax);
-    k_quant<<<grid_for(n), kThreads, 0, stream>>>(g, h, n, w);
-  }
+  launch_quant(g, h, n, seed, round, thr, w.quant(), leaf_of_row, stream);
   const unsigned row_blocks = (unsigned)((n + kThreads - 1) / kThreads);
   const dim3 hist_grid((unsigned)((n + rows_per_wg - 1) / rows_per_wg), (unsigned)((f + feat_tile - 1) / feat_tile));
   const size_t lds = (size_t)feat_tile * kSlots * (2 * sizeof(long long) + sizeof(int));

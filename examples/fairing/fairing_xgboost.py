@@ -28,10 +28,12 @@ def read_input(test_size=TEST_FRACTION_SIZE):
     return (X[:n], y[:n]), (X[n:], y[n:])
 
 
-def run_training_and_eval(device="cpu", subsample=1.0, colsample_bytree=1.0, colsample_bylevel=1.0, seed=0):
+def run_training_and_eval(device="cpu", subsample=1.0, colsample_bytree=1.0, colsample_bylevel=1.0, seed=0, max_leaves=0):
     (tx, ty), (vx, vy) = read_input()
+    policy = dict(grow_policy="lossguide", max_leaves=max_leaves, max_depth=0) if max_leaves else {}  # leaf-wise growth
     model = XGBRegressor(n_estimators=ESTIMATORS, learning_rate=LEARNING_RATE, device=device, subsample=subsample,
-                         colsample_bytree=colsample_bytree, colsample_bylevel=colsample_bylevel, random_state=seed)
+                         colsample_bytree=colsample_bytree, colsample_bylevel=colsample_bylevel, random_state=seed,
+                         **policy)
     model.fit(tx, ty, early_stopping_rounds=EARLY_STOPPING_ROUNDS, eval_set=[(vx, vy)])
     logging.info("Best RMSE on eval: %.2f with %d rounds", model.best_score, model.best_iteration + 1)
     mae = mean_absolute_error(model.predict(vx), vy)
@@ -57,8 +59,10 @@ if __name__ == "__main__":
     ap.add_argument("--colsample-bytree", type=float, default=1.0, help="features sampled per tree, in (0, 1]")
     ap.add_argument("--colsample-bylevel", type=float, default=1.0, help="features sampled per level, in (0, 1]")
     ap.add_argument("--seed", type=int, default=0, help="random_state of the draws")
+    ap.add_argument("--max-leaves", type=int, default=0,
+                    help="0 (default): depth-wise trees of depth 6; L >= 2: leaf-wise trees of L leaves (lossguide)")
     args = ap.parse_args()
     fairing.config.set_builder("append", base_image="rocm/pytorch:latest", registry="local", push=False)
     fairing.config.set_deployer("local")
     print(fairing.config.fn(run_training_and_eval)(args.device, args.subsample, args.colsample_bytree,
-                                                   args.colsample_bylevel, args.seed))
+                                                   args.colsample_bylevel, args.seed, args.max_leaves))

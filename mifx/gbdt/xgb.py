@@ -1,5 +1,5 @@
 """XGBoost-style gradient-boosted trees: XGBRegressor / XGBClassifier on the native histogram learner of
-csrc/gbdt.cpp (second-order split gain, learned missing-value directions, depth-wise growth).
+csrc/gbdt.cpp (second-order split gain, learned missing-value directions, depth-wise or leaf-wise growth).
 
 Reference usage: `kubeflow-pipelines/fairing/fairing_xgboost.py:69-87` (XGBRegressor(n_estimators, learning_rate),
 fit with `early_stopping_rounds` and `eval_set`, then `best_score`, `best_iteration`, `predict`). Semantics follow
@@ -50,7 +50,21 @@ TreeSHAP in margin space, on the host (csrc/gbdt.cpp) for host input and on the 
 tensor, the same bits. `predict_interactions(X)` is its `pred_interactions`: the (f + 1) x (f + 1) SHAP interaction
 values per row from the same path tables, one conditioned pass per feature over the leaves that hold it, on the host
 (mifx_gbdt_interactions) or on the GPU (csrc/gbdt_interactions.hip), the same bits. Approximate (Saabas)
-contributions are not implemented."""
+contributions are not implemented.
+
+Growth policy, on all three learners: `grow_policy="depthwise"` (the default: level by level to `max_depth`) or
+XGBoost's `grow_policy="lossguide"` with a leaf budget `max_leaves` >= 2 (LightGBM's default rule): the open leaf with
+the largest gain is split next, ties to the lowest node id, until `max_leaves` leaves exist or no leaf has a split
+left; children take the next two node ids, left then right, so tree arrays hold at most 2 * max_leaves - 1 nodes.
+`max_depth=0` then means no depth limit, `max_depth > 0` also closes a node at that depth. A node's candidate split
+is the depth-wise learners' (same histograms, same scan, same leaf test), so the tree is the best-first prefix of the
+depth-wise tree with the same depth limit, and with a budget that does not bind (`max_leaves = 2 ** max_depth`) every
+row gets the same leaf value. On the GPU (csrc/gbdt_lossguide.hip) a tree is max_leaves - 1 expansions of four
+launches, each histogramming only the smaller child and subtracting it from the parent's histogram in place (exact in
+int64, so the host twin `device="cpu", fixed_point=True` still equals the GPU model bit for bit); limits there:
+`max_leaves <= 4096`, `max_depth` 0 or <= 12. `max_leaves` under depth-wise growth and `colsample_bylevel < 1` under
+lossguide raise ValueError. Prediction, contributions and interactions walk child indices and do not change;
+TreeSHAP's limit of 12 distinct features on a path applies to deep chains too."""
 from __future__ import annotations
 
 import ctypes
@@ -86,6 +100,9 @@ def _lib():
     lib.mifx_gbdt_grow_fixed_ex.argtypes = lib.mifx_gbdt_grow_ex.argtypes
     lib.mifx_gbdt_grow_stats.argtypes = lib.mifx_gbdt_grow_ex.argtypes + [_D, _D]
     lib.mifx_gbdt_grow_fixed_stats.argtypes = lib.mifx_gbdt_grow_stats.argtypes
+    a = lib.mifx_gbdt_grow_stats.argtypes  # the leaf-wise growers: max_leaves follows max_depth, the mask is [f]
+    lib.mifx_gbdt_grow_lossguide_stats.argtypes = a[:7] + [ctypes.c_int] + a[7:]
+    lib.mifx_gbdt_grow_fixed_lossguide_stats.argtypes = lib.mifx_gbdt_grow_lossguide_stats.argtypes
     u64 = ctypes.c_uint64
     lib.mifx_gbdt_sample_rows.argtypes = [u64, u64, ctypes.c_double, ctypes.c_long, _U8]
     lib.mifx_gbdt_sample_rows.restype = ctypes.c_long
@@ -95,7 +112,8 @@ def _lib():
     for f in (lib.mifx_gbdt_cuts, lib.mifx_gbdt_bin, lib.mifx_gbdt_grow, lib.mifx_gbdt_predict,
               lib.mifx_gbdt_grow_fixed, lib.mifx_gbdt_quant_exp, lib.mifx_gbdt_grow_ex, lib.mifx_gbdt_grow_fixed_ex,
               lib.mifx_gbdt_sample_features, lib.mifx_gbdt_level_mask, lib.mifx_gbdt_grow_stats,
-              lib.mifx_gbdt_grow_fixed_stats):
+              lib.mifx_gbdt_grow_fixed_stats, lib.mifx_gbdt_grow_lossguide_stats,
+              lib.mifx_gbdt_grow_fixed_lossguide_stats):
         f.restype = ctypes.c_int
     return lib
 
@@ -160,13 +178,15 @@ class _Base:
                  base_score: float | None = None, n_jobs: int | None = None, random_state: int = 0,
                  verbosity: int = 0, device: str | None = None, fixed_point: bool | None = None,
                  subsample: float = 1.0, colsample_bytree: float = 1.0, colsample_bylevel: float = 1.0,
-                 importance_type: str = "gain"):
+                 importance_type: str = "gain", grow_policy: str = "depthwise", max_leaves: int = 0):
         self.n_estimators, self.learning_rate, self.max_depth = n_estimators, learning_rate, max_depth
         self.min_child_weight, self.reg_lambda, self.gamma, self.max_bins = min_child_weight, reg_lambda, gamma, max_bins
         self.base_score, self.n_jobs = base_score, n_jobs
         self.random_state, self.verbosity = random_state, verbosity  # random_state: the seed of every draw
         self.subsample, self.colsample_bytree, self.colsample_bylevel = subsample, colsample_bytree, colsample_bylevel
+        self.grow_policy, self.max_leaves = grow_policy, max_leaves
         self._check_rates()
+        self._check_policy()
         self.best_iteration, self.best_score, self.evals_result_ = None, None, {}
         self._trees: list[tuple] = []
         self._node_stats: list[tuple] = []  # per tree (gain, cover), parallel to _trees
@@ -183,6 +203,29 @@ class _Base:
         for name, r in zip(("subsample", "colsample_bytree", "colsample_bylevel"), self._rates()):
             if not 0.0 < r <= 1.0:  # (a NaN fails too)
                 raise ValueError(f"{name} must be in (0, 1], got {r}")
+
+    def _policy(self):
+        """(grow_policy, max_leaves); depth-wise for a model pickled before they existed."""
+        return str(getattr(self, "grow_policy", "depthwise")), int(getattr(self, "max_leaves", 0))
+
+    def _lossguide(self) -> bool:
+        return self._policy()[0] == "lossguide"
+
+    def _check_policy(self) -> None:
+        policy, leaves = self._policy()
+        if policy not in ("depthwise", "lossguide"):
+            raise ValueError(f"grow_policy must be 'depthwise' or 'lossguide', got {policy!r}")
+        if policy == "depthwise":
+            if leaves != 0:
+                raise ValueError(f"max_leaves={leaves} needs grow_policy='lossguide' (depth-wise growth has no leaf "
+                                 f"budget)")
+            return
+        if leaves < 2:
+            raise ValueError(f"grow_policy='lossguide' needs max_leaves >= 2, got {leaves}")
+        if int(self.max_depth) < 0:
+            raise ValueError(f"max_depth must be >= 0 (0: no depth limit), got {self.max_depth}")
+        if self._rates()[2] < 1.0:
+            raise ValueError("colsample_bylevel < 1 is not defined for grow_policy='lossguide' (use colsample_bytree)")
 
     def _seed(self) -> int:
         return int(getattr(self, "random_state", 0) or 0) & _M64
@@ -205,6 +248,8 @@ class _Base:
         """(rows, level_mask) of boosting round `it`: None where nothing is drawn."""
         sub, bytree, bylevel = self._rates()
         rows = sample_rows(self._seed(), it, sub, n) if sub < 1.0 else None
+        if self._lossguide():  # the tree's own feature set [f]: the one level of a depth-1 mask
+            return rows, level_mask(self._seed(), it, f, 1, bytree, 1.0)[0] if bytree < 1.0 else None
         mask = level_mask(self._seed(), it, f, int(self.max_depth), bytree, bylevel) \
             if (bytree < 1.0 or bylevel < 1.0) and int(self.max_depth) > 0 else None
         return rows, mask
@@ -296,14 +341,19 @@ class _Base:
         return self._grow_stats(bins, nbins, g, h, leaf_of_row, rows, level_mask)[0]
 
     def _grow_stats(self, bins, nbins, g, h, leaf_of_row, rows=None, level_mask=None):
-        """(_grow's tree, (gain, cover)): the tree and its nodes' statistics (float64 [nodes] each)."""
+        """(_grow's tree, (gain, cover)): the tree and its nodes' statistics (float64 [nodes] each). Under
+        grow_policy="lossguide" the tree is grown leaf-wise and level_mask is the tree's [f] feature mask."""
         n = bins.shape[1]
-        cap = 2 ** (self.max_depth + 1)
+        lossguide, leaves = self._lossguide(), self._policy()[1]
+        cap = 2 * leaves - 1 if lossguide else 2 ** (self.max_depth + 1)
         fe, sb, left, right = (np.empty(cap, np.int32) for _ in range(4))
         dl = np.empty(cap, np.uint8)
         val = np.empty(cap, np.float64)
         gain, cover = np.empty(cap, np.float64), np.empty(cap, np.float64)
         grow = _lib().mifx_gbdt_grow_fixed_stats if self._fixed() else _lib().mifx_gbdt_grow_stats
+        if lossguide:
+            fn = _lib().mifx_gbdt_grow_fixed_lossguide_stats if self._fixed() else _lib().mifx_gbdt_grow_lossguide_stats
+            grow = lambda *a: fn(*a[:7], leaves, *a[7:])  # noqa: E731
         if rows is not None:
             rows = np.ascontiguousarray(rows, np.int32)
         if level_mask is not None:
@@ -333,6 +383,7 @@ class _Base:
         self._dev_forest = self._paths = self._dev_paths = None
         gpu = self._gpu_index()
         self._check_rates()
+        self._check_policy()
         self._check_data_device(X, y, sample_weight, *(eval_set[-1] if eval_set else ()))
         y = self._check_y(_host(y).reshape(-1))
         X = X if _is_tensor(X) else np.asarray(X)
@@ -412,7 +463,11 @@ class _Base:
         from ..ops import gbdt_gpu as G
         from ..ops import gbdt_prep as P
 
-        G.check_limits(len(y), int(self.max_bins), int(self.max_depth))
+        lossguide, leaves = self._lossguide(), self._policy()[1]
+        if lossguide:
+            G.check_limits_lossguide(len(y), int(self.max_bins), int(self.max_depth), leaves)
+        else:
+            G.check_limits(len(y), int(self.max_bins), int(self.max_depth))
         if int(self.max_bins) < 2:
             raise ValueError("max_bins must be in [2, 65535]")
         dev = G.device_for(self._gpu_index())
@@ -426,12 +481,15 @@ class _Base:
         self._base_margin = self._intercept(y, w)
         rounds, K = int(self.n_estimators), self._num_class()  # K trees per round, tree it * K + k on margin row k
         sub, bytree, bylevel = self._rates()
-        masks = None
-        if (bytree < 1.0 or bylevel < 1.0) and int(self.max_depth) > 0 and rounds > 0:
+        masks, mask_kw = None, "feature_mask" if lossguide else "level_mask"
+        if lossguide and bytree < 1.0 and rounds > 0:  # one [f] set per tree
+            masks = np.stack([level_mask(self._seed(), t, self._nfeat, 1, bytree, 1.0)[0] for t in range(rounds * K)])
+        elif not lossguide and (bytree < 1.0 or bylevel < 1.0) and int(self.max_depth) > 0 and rounds > 0:
             masks = np.stack([level_mask(self._seed(), t, self._nfeat, int(self.max_depth), bytree, bylevel)
                               for t in range(rounds * K)])
         with torch.cuda.device(dev):
-            bst = G.Booster.from_device_bins(bins, nbins, int(self.max_depth))
+            bst = G.LossguideBooster.from_device_bins(bins, nbins, int(self.max_depth), leaves) if lossguide else \
+                G.Booster.from_device_bins(bins, nbins, int(self.max_depth))
             yd = torch.from_numpy(y).to(dev)
             wd = None if w is None else torch.from_numpy(w).to(dev)
             masks = None if masks is None else torch.from_numpy(masks).to(dev)
@@ -458,8 +516,8 @@ class _Base:
                     tree = tuple(t[it * K + k] for t in trees)
                     bst.grow(g[k], h[k], tree, self.min_child_weight, self.reg_lambda, self.gamma, self.learning_rate,
                              margin[k], subsample=sub, seed=self._seed(), round=it * K + k,
-                             level_mask=None if masks is None else masks[it * K + k],
-                             stats=tuple(s[it * K + k] for s in stats))
+                             stats=tuple(s[it * K + k] for s in stats),
+                             **{mask_kw: None if masks is None else masks[it * K + k]})
                     if ev is not None:
                         bst.apply(ev[0], tree, ev[2][k])
                 done = (it + 1) * K
@@ -479,7 +537,7 @@ class _Base:
             gain, cover = (s[:done].cpu().numpy() for s in stats)
         self._trees, self._node_stats = [], []
         for t in range(done):
-            c = int(cnt[t])
+            c = int(np.ravel(cnt[t])[0])  # (the leaf-wise grower's count comes with the tree's depth)
             thr = np.zeros(c, np.float64)
             for k in range(c):  # the split's cut value: bin <= b  <=>  x < cuts[b]
                 if fe[t, k] >= 0:

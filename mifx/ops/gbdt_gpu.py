@@ -11,7 +11,11 @@ mifx.gbdt.sample.level_mask); `grad_hess(weight=)` multiplies the float32 pair b
 
 Multi-class (multi:softprob): `grad_hess_softmax` computes the pairs of all K classes from class-major [K, n] margins
 in one launch; the round then calls `Booster.grow` (and `Booster.apply`) once per class on row k of g, h and the
-margins, with the tree index round * K + k as `round`."""
+margins, with the tree index round * K + k as `round`.
+
+Leaf-wise growth (grow_policy="lossguide", csrc/gbdt_lossguide.hip): `LossguideBooster` has Booster's interface with
+a leaf budget `max_leaves` (tree arrays of 2 * max_leaves - 1 entries), `max_depth` 0 meaning no depth limit, and one
+[f] `feature_mask` per tree in place of the level mask; `grow_lossguide_numpy` is its one-tree entry for the tests."""
 from __future__ import annotations
 
 import ctypes
@@ -51,6 +55,32 @@ def _fns():
         "apply": sig(lib, "mifx_gbdt_gpu_apply", [VP, LONG, I32, VP, VP, VP, VP, VP, VP, VP, I32, VP, VP]),
         "grad_softmax": sig(lib, "mifx_gbdt_gpu_grad_softmax", [VP, VP, VP, LONG, I32, VP, VP, VP]),
     }
+
+
+@functools.lru_cache(maxsize=None)
+def _lg_fns():
+    lib = _lib.load("gbdt_lossguide")
+    return {
+        "max_leaves": sig(lib, "mifx_gbdt_lg_max_leaves", []),
+        "max_depth": sig(lib, "mifx_gbdt_lg_max_depth", []),
+        "max_feat_tile": sig(lib, "mifx_gbdt_lg_max_feat_tile", []),
+        "ws_bytes": sig(lib, "mifx_gbdt_lg_ws_bytes", [LONG, I32, I32, I32], I64),
+        "grow": sig(lib, "mifx_gbdt_lg_grow", [VP, LONG, I32, VP, VP, I32, VP, VP, I32, I32, F64, F64, F64, F64, VP, I64,
+                                               VP, VP, VP, VP, VP, VP, VP, VP, VP, I32, I32, I32, U64, U64, U64, VP, VP,
+                                               VP, VP]),
+        "apply": sig(lib, "mifx_gbdt_lg_apply", [VP, LONG, I32, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP]),
+    }
+
+
+def check_limits_lossguide(n: int, max_bins: int, max_depth: int, max_leaves: int) -> None:
+    """The leaf-wise device path's limits, checked before anything is launched (and without a GPU)."""
+    fns = _lg_fns()
+    if not 2 <= max_leaves <= fns["max_leaves"]():
+        raise ValueError(f"device='gpu' supports 2 <= max_leaves <= {fns['max_leaves']()}, got {max_leaves}")
+    if not 0 <= max_depth <= fns["max_depth"]():
+        raise ValueError(f"device='gpu' supports max_depth 0 (no limit) or <= {fns['max_depth']()} under "
+                         f"grow_policy='lossguide', got {max_depth}")
+    check_limits(n, max_bins, 0)
 
 
 def check_limits(n: int, max_bins: int, max_depth: int) -> None:
@@ -137,21 +167,25 @@ class Booster:
         return self
 
     def _setup(self, n: int, f: int, nbins: np.ndarray, max_depth: int, dev: torch.device, device_bins) -> None:
+        check_limits(n, int(np.max(nbins)), max_depth)
+        self._setup_data(n, f, nbins, max_depth, dev, device_bins)
+        self.cap = 2 ** (self.max_depth + 1)
+        nbytes = _fns()["ws_bytes"](n, f, self.max_depth, self.hsize)
+        if nbytes < 0:
+            raise ValueError("shape outside the device learner's limits")
+        self.ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+
+    def _setup_data(self, n: int, f: int, nbins: np.ndarray, max_depth: int, dev: torch.device, device_bins) -> None:
+        """What every grower keeps resident: the bins, the bin counts and offsets, leaf_of_row."""
         nbins = np.asarray(nbins, np.int32)
-        check_limits(n, int(nbins.max()), max_depth)
         if nbins.min() < 1 or len(nbins) != f:
             raise ValueError("nbins must hold one count >= 1 per feature")
         self.n, self.f, self.max_depth, self.dev = n, f, int(max_depth), dev
-        self.cap = 2 ** (self.max_depth + 1)
         hoff = np.concatenate([[0], np.cumsum(nbins + 1)]).astype(np.int32)
         self.hsize = int(hoff[-1])
         self.bins = device_bins()
         self.nbins = torch.from_numpy(nbins).to(dev)
         self.hoff = torch.from_numpy(hoff[:-1].copy()).to(dev)
-        nbytes = _fns()["ws_bytes"](n, f, self.max_depth, self.hsize)
-        if nbytes < 0:
-            raise ValueError("shape outside the device learner's limits")
-        self.ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         self.leaf_of_row = torch.empty(n, dtype=torch.int32, device=dev)
 
     def new_trees(self, count: int):
@@ -229,6 +263,106 @@ class Booster:
         check(_fns()["apply"](ptr(ebins), len(ebins), self.f, ptr(self.nbins), ptr(fe), ptr(sb), ptr(dl), ptr(le),
                               ptr(ri), ptr(val), self.max_depth, ptr(emargin), stream_handle(self.dev)),
               "mifx_gbdt_gpu_apply")
+
+
+LG_GRID_X = 512  # workgroups along the rows of the leaf-wise grower's histogram and partition kernels
+
+
+class LossguideBooster(Booster):
+    """Booster for leaf-wise growth (csrc/gbdt_lossguide.hip): the same resident state, a workspace of
+
+        24 n + (2 max_leaves - 1) * 80 + 80 f + 20 * max_leaves * hsize   bytes (+ 256-byte rounding per array),
+
+    hsize = sum over features of nbins + 1: the quantised rows and two permutation arrays, the node table, one
+    expansion's per-feature candidates, and the pool of max_leaves histograms (int64 g, int64 h, int32 rows)."""
+
+    def __init__(self, bins: np.ndarray, nbins: np.ndarray, max_depth: int, max_leaves: int, dev: torch.device):
+        f, n = bins.shape
+        self.max_leaves = int(max_leaves)
+        self._setup(n, f, nbins, max_depth, dev, lambda: upload_bins(bins, dev))
+
+    @classmethod
+    def from_device_bins(cls, bins: torch.Tensor, nbins: np.ndarray, max_depth: int, max_leaves: int):
+        if not (bins.is_cuda and bins.dim() == 2 and bins.dtype == torch.int16 and bins.is_contiguous()):
+            raise ValueError("expected a contiguous [n, f] int16 tensor on the GPU")
+        self = cls.__new__(cls)
+        self.max_leaves = int(max_leaves)
+        self._setup(bins.shape[0], bins.shape[1], nbins, max_depth, bins.device, lambda: bins)
+        return self
+
+    def _setup(self, n, f, nbins, max_depth, dev, device_bins) -> None:
+        check_limits_lossguide(n, int(np.max(nbins)), int(max_depth), self.max_leaves)
+        self._setup_data(n, f, nbins, max_depth, dev, device_bins)
+        self.cap = 2 * self.max_leaves - 1
+        nbytes = _lg_fns()["ws_bytes"](n, f, self.max_leaves, self.hsize)
+        if nbytes < 0:
+            raise ValueError("shape outside the device learner's limits")
+        self.ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+
+    def new_trees(self, count: int):
+        """Booster.new_trees with [count, 2] in the last place: every tree's node count and depth."""
+        return super().new_trees(count)[:6] + (torch.zeros((count, 2), dtype=torch.int32, device=self.dev),)
+
+    def grow(self, g, h, tree, min_child_weight, reg_lambda, gamma, eta, margin=None, _rows_per_wg=None,
+             _feat_tile=None, subsample: float = 1.0, seed: int = 0, round: int = 0, feature_mask=None, stats=None,
+             _grid_x=None) -> None:
+        """Booster.grow, leaf-wise. `feature_mask`: [f] uint8 on the device, the features the tree may split on.
+        Every row's margin receives the tree's output (rows outside the sample by a walk of the finished tree). The
+        private arguments are launch geometry: the result does not depend on them."""
+        assert g.dtype == h.dtype == torch.float32 and len(g) == len(h) == self.n and g.is_contiguous()
+        assert h.is_contiguous() and all(t.is_contiguous() for t in tree) and tree[6].numel() == 2
+        assert margin is None or (margin.dtype == torch.float64 and len(margin) == self.n and margin.is_contiguous())
+        rows, tile, gx = int(_rows_per_wg or ROWS_PER_WG), int(_feat_tile or FEAT_TILE), int(_grid_x or LG_GRID_X)
+        if rows < 1 or not 1 <= tile <= _lg_fns()["max_feat_tile"]() or not 1 <= gx <= 65535:
+            raise ValueError("launch geometry out of range")
+        if feature_mask is not None and not (feature_mask.dtype == torch.uint8 and feature_mask.is_contiguous() and
+                                             feature_mask.device == self.dev and tuple(feature_mask.shape) == (self.f,)):
+            raise ValueError(f"feature_mask must be a contiguous uint8 [{self.f}] tensor on {self.dev}")
+        gain, cover = stats if stats is not None else (None, None)
+        for s in (gain, cover):
+            assert s is None or (s.dtype == torch.float64 and s.is_contiguous() and s.numel() == self.cap)
+        fe, sb, dl, le, ri, val, cnt = tree
+        m64 = 2 ** 64 - 1
+        check(_lg_fns()["grow"](ptr(self.bins), self.n, self.f, ptr(self.nbins), ptr(self.hoff), self.hsize, ptr(g),
+                                ptr(h), self.max_depth, self.max_leaves, float(min_child_weight), float(reg_lambda),
+                                float(gamma), float(eta), ptr(self.ws), self.ws.numel(), ptr(fe), ptr(sb), ptr(dl),
+                                ptr(le), ptr(ri), ptr(val), ptr(cnt), ptr(self.leaf_of_row), ptr(margin), rows, tile,
+                                gx, int(seed) & m64, int(round) & m64, row_threshold(subsample), ptr(feature_mask),
+                                ptr(gain), ptr(cover), stream_handle(self.dev)), "mifx_gbdt_lg_grow")
+
+    def apply(self, ebins: torch.Tensor, tree, emargin: torch.Tensor) -> None:
+        """emargin += tree(row) for a binned row-major [m, f] matrix; the walk is bounded by the tree's own depth."""
+        assert ebins.shape[1] == self.f and ebins.is_contiguous() and emargin.dtype == torch.float64
+        assert len(emargin) == len(ebins) and emargin.is_contiguous()
+        fe, sb, dl, le, ri, val, cnt = tree
+        check(_lg_fns()["apply"](ptr(ebins), len(ebins), self.f, ptr(self.nbins), ptr(fe), ptr(sb), ptr(dl), ptr(le),
+                                 ptr(ri), ptr(val), ptr(cnt), ptr(emargin), stream_handle(self.dev)),
+              "mifx_gbdt_lg_apply")
+
+
+def grow_lossguide_numpy(bins: np.ndarray, nbins: np.ndarray, g: np.ndarray, h: np.ndarray, max_depth: int,
+                         max_leaves: int, min_child_weight: float = 1.0, reg_lambda: float = 1.0, gamma: float = 0.0,
+                         eta: float = 0.3, device: int = 0, subsample: float = 1.0, seed: int = 0, round: int = 0,
+                         feature_mask: np.ndarray | None = None, margin: np.ndarray | None = None, **geometry):
+    """One leaf-wise tree on the device from host arrays: (feature, split_bin, default_left, left, right, value,
+    leaf_of_row, gain, cover), the outputs of the host's mifx_gbdt_grow_fixed_lossguide_stats (with subsample on the
+    rows sampled for (seed, round)); with `margin` (float64 [n]) the updated margins follow as a tenth array.
+    `geometry`: _rows_per_wg, _feat_tile, _grid_x."""
+    dev = device_for(device)
+    with torch.cuda.device(dev):
+        b = LossguideBooster(bins, nbins, max_depth, max_leaves, dev)
+        tree = tuple(t[0] for t in b.new_trees(1))
+        st = tuple(s[0] for s in b.new_stats(1))
+        gd = torch.from_numpy(np.ascontiguousarray(g, np.float32)).to(dev)
+        hd = torch.from_numpy(np.ascontiguousarray(h, np.float32)).to(dev)
+        fm = None if feature_mask is None else torch.from_numpy(np.ascontiguousarray(feature_mask, np.uint8)).to(dev)
+        md = None if margin is None else torch.from_numpy(np.ascontiguousarray(margin, np.float64)).to(dev)
+        b.grow(gd, hd, tree, min_child_weight, reg_lambda, gamma, eta, md, subsample=subsample, seed=seed, round=round,
+               feature_mask=fm, stats=st, **geometry)
+        cnt = int(tree[6][0].item())
+        out = tuple(t[:cnt].cpu().numpy() for t in tree[:6]) + (b.leaf_of_row.cpu().numpy(),)
+        out += tuple(s[:cnt].cpu().numpy() for s in st)
+        return out if md is None else out + (md.cpu().numpy(),)
 
 
 def grow_numpy(bins: np.ndarray, nbins: np.ndarray, g: np.ndarray, h: np.ndarray, max_depth: int,

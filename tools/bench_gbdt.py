@@ -12,10 +12,13 @@ per round), K >= 3 multi:softprob (one softmax gradient launch + K trees per rou
 The softmax gradient kernel is also timed alone, against the 16 K n bytes it must move at least (the float64 margins
 in, float32 g and h out). The default, 0, is the squared-error round.
 `--stats 0` grows the trees without recording the nodes' gain and cover (1, the default, is what `fit` does).
+`--grow-policy lossguide --max-leaves L` times the leaf-wise grower (csrc/gbdt_lossguide.hip; `--max-depth 0` = no
+depth limit) the same way; the record then also holds the kernel launches one tree enqueues.
 
   python tools/bench_gbdt.py --sizes 10000 100000 1000000 --out profiles/gbdt_gpu.jsonl
   python tools/bench_gbdt.py --sizes 1000000 --subsample 0.5 --host-rounds 1 --out profiles/gbdt_sample.jsonl
   python tools/bench_gbdt.py --sizes 1000000 --num-class 3 --host-rounds 1 --out profiles/gbdt_multiclass.jsonl
+  python tools/bench_gbdt.py --sizes 1000000 --grow-policy lossguide --max-leaves 64 --max-depth 0 --host-rounds 1
 """
 from __future__ import annotations
 
@@ -66,6 +69,8 @@ def main(argv=None) -> int:
                     help="0: squared error (default); 2: binary:logistic; K >= 3: multi:softprob, K trees per round")
     ap.add_argument("--stats", type=int, default=1, choices=[0, 1],
                     help="1 (default): the grower records every node's gain and cover, as fit does; 0: it does not")
+    ap.add_argument("--grow-policy", default="depthwise", choices=["depthwise", "lossguide"])
+    ap.add_argument("--max-leaves", type=int, default=0, help="the leaf budget of --grow-policy lossguide")
     ap.add_argument("--out", default=None, help="append one JSON line per size")
     a = ap.parse_args(argv)
 
@@ -80,7 +85,9 @@ def main(argv=None) -> int:
         X = r.standard_normal((n, a.features))
         y = X[:, 0] * X[:, 1] + np.abs(X[:, 2]) + 0.5 * X[:, 3] + r.normal(0, 0.1, n)
         kw = dict(max_bins=a.max_bins, max_depth=a.max_depth, n_jobs=a.threads, subsample=a.subsample,
-                  colsample_bytree=a.colsample_bytree, random_state=0)
+                  colsample_bytree=a.colsample_bytree, random_state=0, grow_policy=a.grow_policy,
+                  max_leaves=a.max_leaves)
+        lossguide = a.grow_policy == "lossguide"
         if a.num_class == 1 or a.num_class < 0:
             raise SystemExit("--num-class must be 0 or >= 2")
         if a.num_class:  # K quantile classes of the target, as class indices
@@ -105,16 +112,18 @@ def main(argv=None) -> int:
         del X
         total = a.warmup + a.rounds
         masks = None
-        if a.colsample_bytree < 1.0 and a.max_depth > 0:
+        if a.colsample_bytree < 1.0 and (a.max_depth > 0 or lossguide):
             from mifx.gbdt import xgb
 
-            masks = np.stack([xgb.level_mask(0, t, a.features, a.max_depth, a.colsample_bytree, 1.0)
+            masks = np.stack([xgb.level_mask(0, t, a.features, 1, a.colsample_bytree, 1.0)[0] if lossguide else
+                              xgb.level_mask(0, t, a.features, a.max_depth, a.colsample_bytree, 1.0)
                               for t in range(total * K)])
 
         with torch.cuda.device(dev):
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            bst = G.Booster(bins, nbins, a.max_depth, dev)
+            bst = G.LossguideBooster(bins, nbins, a.max_depth, a.max_leaves, dev) if lossguide else \
+                G.Booster(bins, nbins, a.max_depth, dev)
             yd = torch.from_numpy(y).to(dev)
             torch.cuda.synchronize()
             t_up = time.perf_counter() - t0
@@ -136,10 +145,12 @@ def main(argv=None) -> int:
                     grad()
                     for k in range(K):
                         t = it * K + k
+                        mask = None if md is None else md[t]
+                        route = dict(feature_mask=mask) if lossguide else \
+                            dict(level_mask=mask, _margin_route=a.margin_route)
                         bst.grow(g[k], h[k], tuple(x[t] for x in trees), 1.0, 1.0, 0.0, 0.3, margin[k],
-                                 subsample=a.subsample, seed=0, round=t, level_mask=None if md is None else md[t],
-                                 _margin_route=a.margin_route,
-                                 stats=None if stats is None else tuple(x[t] for x in stats))
+                                 subsample=a.subsample, seed=0, round=t,
+                                 stats=None if stats is None else tuple(x[t] for x in stats), **route)
                 torch.cuda.synchronize()
 
             run(0, a.warmup)
@@ -156,13 +167,18 @@ def main(argv=None) -> int:
                 grad()
             torch.cuda.synchronize()
             t_grad = (time.perf_counter() - t0) / reps
-            cnt = int(trees[6][0].item())
+            cnt = int(trees[6][0].flatten()[0].item())
             same = all(np.array_equal(trees[k][0, :cnt].cpu().numpy(), w) for k, w in
                        ((0, first_twin[0]), (2, first_twin[2]), (3, first_twin[3]), (4, first_twin[4]),
                         (5, first_twin[5])))
             del bst, yd, margin, g, h, trees, stats
             torch.cuda.empty_cache()
+        # launches one unsampled tree enqueues: the quantise stage (3) and, depth-wise, per level 3 memsets + 4 kernels
+        # (the last level 2 kernels) + the node count's copy; leaf-wise the root (3), per expansion 4 (the last 2), finish
+        launches = 3 + 3 + 4 * (a.max_leaves - 1) - 2 + 1 if lossguide else 3 + 7 * a.max_depth + 2 + 1
         rec = {"n": n, "features": a.features, "max_bins": a.max_bins, "max_depth": a.max_depth,
+               "grow_policy": a.grow_policy, "max_leaves": a.max_leaves, "launches_per_tree": launches,
+               "first_tree_nodes": cnt,
                "subsample": a.subsample, "colsample_bytree": a.colsample_bytree, "margin_route": a.margin_route,
                "host_threads": a.threads, "bin_s": round(t_bin, 4), "upload_s": round(t_up, 4),
                "host_round_s": [round(t, 5) for t in th], "host_fixed_round_s": [round(t, 5) for t in tt],
