@@ -30,6 +30,9 @@
 // table of gbdt_shap.h and mifx_gbdt_contribs evaluates path-dependent TreeSHAP from it (the device twin is k_contribs
 // in gbdt_prep.hip); mifx_gbdt_interactions gives the interaction values, one conditioned pass per feature over the
 // leaves that hold it (the device twin is k_interactions in gbdt_interactions.hip).
+//
+// Absolute / quantile error: mifx_gbdt_leaf_refresh replaces a finished tree's leaf values by exact weighted quantiles
+// of the residuals of each leaf's rows (the rule of gbdt_quantile.h; the device twin is gbdt_quantile.hip).
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -37,6 +40,7 @@
 #include <thread>
 #include <vector>
 
+#include "gbdt_quantile.h"
 #include "gbdt_sample.h"
 #include "gbdt_shap.h"
 #include "gbdt_split.h"
@@ -522,6 +526,51 @@ int mifx_gbdt_grow_fixed(const uint16_t* bins, long n, int f, const int* nbins, 
   return mifx_gbdt_grow_fixed_ex(bins, n, f, nbins, g, h, max_depth, min_child_weight, lambda, gamma, eta, threads,
                                  max_nodes, feature, split_bin, default_left, left, right, value, leaf_of_row, nullptr,
                                  0, nullptr);
+}
+
+// ---- the leaf refresh of reg:absoluteerror / reg:quantileerror (gbdt_quantile.h has the rule): value[l] of every leaf
+// l < nodes that holds rows becomes eta times the weighted lower alpha-quantile of resid over the rows with
+// leaf_of_row == l (-1: a row outside the sample). h [n]: the float32 hessians the tree was grown from; their integer
+// weights use the exponent of the rows with a leaf. A leaf of total weight 0 keeps its value. The leaves are
+// independent: the same bits for any thread count. Returns 0, or -1 for a leaf id outside [-1, nodes).
+int mifx_gbdt_leaf_refresh(const double* resid, const float* h, const int* leaf_of_row, long n, int nodes, double alpha,
+                           double eta, double* value, int threads) {
+  if (n < 0 || nodes < 1) return -1;
+  std::vector<long> off(nodes + 1, 0);
+  double amax = 0.0;
+  long ns = 0;
+  for (long i = 0; i < n; ++i) {
+    const int l = leaf_of_row[i];
+    if (l < -1 || l >= nodes) return -1;
+    if (l < 0) continue;
+    ++off[l + 1];
+    ++ns;
+    amax = std::max(amax, std::fabs((double)h[i]));
+  }
+  const int eh = mifx_gq_exp(amax, ns);
+  for (int l = 0; l < nodes; ++l) off[l + 1] += off[l];
+  struct Row {
+    uint64_t key;
+    long long q;
+  };
+  std::vector<Row> rows(ns);
+  std::vector<long> cur(off.begin(), off.end() - 1);
+  for (long i = 0; i < n; ++i)
+    if (leaf_of_row[i] >= 0) rows[cur[leaf_of_row[i]]++] = Row{mifx_sort_key(resid[i]), mifx_gq_weight(h[i], eh)};
+  parallel_for(nodes, ns > 100000 ? threads : 1, [&](int l) {
+    Row *b = rows.data() + off[l], *e = rows.data() + off[l + 1];
+    long long Q = 0;
+    for (Row* r = b; r < e; ++r) Q += r->q;
+    if (Q <= 0) return;
+    std::sort(b, e, [](const Row& x, const Row& y) { return x.key < y.key; });
+    long long left = mifx_gq_threshold(alpha, Q);
+    for (Row* r = b; r < e; ++r)
+      if ((left -= r->q) <= 0) {  // equal keys are adjacent: the first row that reaches T carries the selected key
+        value[l] = mifx_gq_value(r->key, eta);
+        return;
+      }
+  });
+  return 0;
 }
 
 }  // extern "C"

@@ -64,7 +64,28 @@ launches, each histogramming only the smaller child and subtracting it from the 
 int64, so the host twin `device="cpu", fixed_point=True` still equals the GPU model bit for bit); limits there:
 `max_leaves <= 4096`, `max_depth` 0 or <= 12. `max_leaves` under depth-wise growth and `colsample_bylevel < 1` under
 lossguide raise ValueError. Prediction, contributions and interactions walk child indices and do not change;
-TreeSHAP's limit of 12 distinct features on a path applies to deep chains too."""
+TreeSHAP's limit of 12 distinct features on a path applies to deep chains too.
+
+Robust loss and prediction intervals, on all three learners: `XGBRegressor(objective="reg:absoluteerror")` and
+`objective="reg:quantileerror", quantile_alpha=a` (one scalar a in (0, 1); absolute error is a = 0.5), XGBoost's
+objectives with its "adaptive tree". With d = margin - y in double the pair is g = +1 / 0 / -1 for d > 0 / = 0 / < 0
+(absolute error) or g = float32(1 - a) for d >= 0 and float32(-a) below (quantile error), h = 1.0f, each times the
+float32 weight as above; the unchanged growers grow the tree from these pairs. The hessian is constant, so the Newton
+leaf value means nothing: once the tree is complete, and before any margin moves, every leaf is REFRESHED to
+learning_rate times the weighted lower a-quantile of the residuals r_i = y_i - margin_i (double) of the rows in it.
+The rule (csrc/gbdt_quantile.h, the one copy for host and device) is exact: row i weighs the integer q_i, its hessian
+quantised by the fixed-point rule with the exponent of the tree's rows (the integers the fixed-point histograms
+summed; the double learner quantises for the refresh only); a leaf's Q is the sum of its q_i over the sampled rows,
+T = ceil(a * (double)Q) clamped to [1, Q], and the quantile is the smallest residual r of the leaf whose rows with
+r_i <= r weigh at least T (numeric order, -0.0 before +0.0). A leaf with Q = 0 keeps the grower's value. Then every
+row's margin, sampled or not, and the eval set's receive the refreshed tree's output. XGBoost interpolates between two
+neighbouring residuals in the unweighted case; ours is the lower of them, so a leaf value differs from XGBoost's by
+less than learning_rate times one gap between adjacent residuals of the leaf. Sums and comparisons are on integers,
+so the GPU (csrc/gbdt_quantile.hip: a segmented weighted radix select over the leaves, nothing read back) equals the
+host twin bit for bit, for any launch geometry. With `base_score=None` the intercept is the same lower weighted
+a-quantile of y (float32 weights accumulated in double over the sorted labels). The eval metric is "mae" or "quantile"
+(the mean pinball loss at a), unweighted. `gain` and `cover` stay the grower's. Several quantiles in one model,
+XGBoost's interpolation and reg:pseudohubererror are not implemented."""
 from __future__ import annotations
 
 import ctypes
@@ -109,11 +130,13 @@ def _lib():
     lib.mifx_gbdt_sample_features.argtypes = [u64, u64, u64, ctypes.c_double, _U8, ctypes.c_int, _U8]
     lib.mifx_gbdt_level_mask.argtypes = [u64, u64, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, _U8,
                                          _U8]
+    lib.mifx_gbdt_leaf_refresh.argtypes = [_D, _F, _I, ctypes.c_long, ctypes.c_int, ctypes.c_double, ctypes.c_double,
+                                           _D, ctypes.c_int]
     for f in (lib.mifx_gbdt_cuts, lib.mifx_gbdt_bin, lib.mifx_gbdt_grow, lib.mifx_gbdt_predict,
               lib.mifx_gbdt_grow_fixed, lib.mifx_gbdt_quant_exp, lib.mifx_gbdt_grow_ex, lib.mifx_gbdt_grow_fixed_ex,
               lib.mifx_gbdt_sample_features, lib.mifx_gbdt_level_mask, lib.mifx_gbdt_grow_stats,
               lib.mifx_gbdt_grow_fixed_stats, lib.mifx_gbdt_grow_lossguide_stats,
-              lib.mifx_gbdt_grow_fixed_lossguide_stats):
+              lib.mifx_gbdt_grow_fixed_lossguide_stats, lib.mifx_gbdt_leaf_refresh):
         f.restype = ctypes.c_int
     return lib
 
@@ -164,6 +187,19 @@ def level_mask(seed: int, round: int, f: int, max_depth: int, colsample_bytree: 
 
 
 _M64 = (1 << 64) - 1
+
+
+def leaf_refresh(resid: np.ndarray, h: np.ndarray, leaf_of_row: np.ndarray, value: np.ndarray, alpha: float,
+                 eta: float, threads: int = 1) -> None:
+    """mifx_gbdt_leaf_refresh (csrc/gbdt.cpp), in place on `value` (float64, contiguous): value[l] becomes eta times the
+    weighted lower alpha-quantile of resid (float64) over the rows with leaf_of_row == l (int32; -1 takes no part),
+    the rows weighing their float32 hessians h as the integers of csrc/gbdt_quantile.h."""
+    n = len(resid)
+    assert resid.dtype == value.dtype == np.float64 and h.dtype == np.float32 and leaf_of_row.dtype == np.int32
+    assert len(h) == len(leaf_of_row) == n and all(a.flags.c_contiguous for a in (resid, h, leaf_of_row, value))
+    if _lib().mifx_gbdt_leaf_refresh(_p(resid, _D), _p(h, _F), _p(leaf_of_row, _I), n, len(value), float(alpha),
+                                     float(eta), _p(value, _D), int(threads)) != 0:
+        raise ValueError("leaf_of_row holds a leaf outside the tree")
 
 
 def _threads() -> int:
@@ -301,6 +337,10 @@ class _Base:
         g, h = self._grad_hess(margin, y)
         return (g, h) if w is None else (g * w, h * w)
 
+    def _refresh_alpha(self):
+        """The quantile every finished tree's leaves are refreshed to (absolute / quantile error); None: no refresh."""
+        return None
+
     def _metric_name(self) -> str:
         return "rmse"
 
@@ -412,12 +452,16 @@ class _Base:
             ev = (ex, ey, ev_margin)
         self._trees, self._node_stats = [], []
         best, best_it, since, hist = None, 0, 0, []
+        alpha = self._refresh_alpha()
         for it in range(int(self.n_estimators)):
             g, h = self._weighted_grad_hess(margin if K > 1 else margin[0], y, w)
             g, h = g.reshape(K, -1), h.reshape(K, -1)
             for k in range(K):
                 rows, mask = self._round_draws(it * K + k, len(y), self._nfeat)
                 tree, stats = self._grow_stats(bins, nbins, g[k], h[k], leaf_of_row, rows, mask)
+                if alpha is not None:  # the leaves' exact quantiles of the residuals, before any margin moves
+                    leaf_refresh(y - margin[k], np.ascontiguousarray(h[k]), leaf_of_row, tree[5], alpha,
+                                 float(self.learning_rate), self._nthreads())
                 self._trees.append(tree)
                 self._node_stats.append(stats)
                 if rows is None:
@@ -457,7 +501,9 @@ class _Base:
         Sampling: the rows are drawn on the device inside the grower; the feature masks of all trees (pure functions
         of the seed, [trees, max_depth, f] bytes) are computed by the host and uploaded once before the first round.
         Multi-class: margins, g and h are [K, n] on the device; a round is one softmax gradient launch and K calls of
-        the grower (and of the eval update), each on one class's row."""
+        the grower (and of the eval update), each on one class's row. Absolute / quantile error: the grower leaves
+        the margins alone, the leaf refresh (csrc/gbdt_quantile.hip) rewrites the tree's leaf values from them, and
+        the refreshed tree is then applied to every training row as it is to the eval set."""
         import torch
 
         from ..ops import gbdt_gpu as G
@@ -507,17 +553,22 @@ class _Base:
                 ev = (P.device_bins(P.as_device_matrix(ex, dev), tables), ey,
                       torch.full((K, len(ey)), self._base_margin, dtype=torch.float64, device=dev))
             best, best_it, since, hist, done = None, 0, 0, [], 0
+            alpha = self._refresh_alpha()
+            refresh = None if alpha is None else G.LeafRefresh(len(y), bst.cap, dev)
             for it in range(rounds):
                 if K > 1:  # every class's pair from the margins at the start of the round, one launch
                     G.grad_hess_softmax(margin, yd, g, h, wd)
                 else:
-                    G.grad_hess(self._objective, margin[0], yd, g[0], h[0], wd)
+                    G.grad_hess(self._objective, margin[0], yd, g[0], h[0], wd, alpha=0.5 if alpha is None else alpha)
                 for k in range(K):
                     tree = tuple(t[it * K + k] for t in trees)
                     bst.grow(g[k], h[k], tree, self.min_child_weight, self.reg_lambda, self.gamma, self.learning_rate,
-                             margin[k], subsample=sub, seed=self._seed(), round=it * K + k,
-                             stats=tuple(s[it * K + k] for s in stats),
+                             margin[k] if refresh is None else None, subsample=sub, seed=self._seed(),
+                             round=it * K + k, stats=tuple(s[it * K + k] for s in stats),
                              **{mask_kw: None if masks is None else masks[it * K + k]})
+                    if refresh is not None:  # the margins are still the ones the residuals are taken from
+                        refresh(bst.leaf_of_row, tree[5], margin[k], yd, h[k], alpha, float(self.learning_rate))
+                        bst.apply(bst.bins, tree, margin[k])
                     if ev is not None:
                         bst.apply(ev[0], tree, ev[2][k])
                 done = (it + 1) * K
@@ -742,7 +793,75 @@ class _Base:
 
 
 class XGBRegressor(_Base):
-    """Squared-error regression (objective reg:squarederror)."""
+    """Regression: squared error (objective "reg:squarederror", the default), absolute error ("reg:absoluteerror")
+    or the pinball loss of one quantile ("reg:quantileerror" at `quantile_alpha`); the latter two refresh every
+    finished tree's leaves to exact weighted quantiles of the residuals (the module docstring has the rule)."""
+    _OBJECTIVES = ("reg:squarederror", "reg:absoluteerror", "reg:quantileerror")
+
+    def __init__(self, *args, objective: str = "reg:squarederror", quantile_alpha: float = 0.5, **kwargs):
+        """The parameters of _Base, the objective and, for reg:quantileerror, the quantile in (0, 1)."""
+        super().__init__(*args, **kwargs)
+        self.objective, self.quantile_alpha = objective, quantile_alpha
+        self._refresh_alpha()
+
+    @property
+    def _objective(self) -> str:
+        """squared error for a model pickled before the argument existed"""
+        return getattr(self, "objective", "reg:squarederror")
+
+    def _refresh_alpha(self):
+        obj, alpha = self._objective, getattr(self, "quantile_alpha", 0.5)
+        if obj not in self._OBJECTIVES:
+            raise ValueError(f"objective must be one of {self._OBJECTIVES}, got {obj!r}")
+        if np.ndim(alpha) != 0:
+            raise ValueError("quantile_alpha must be one scalar: multi-quantile models are not implemented")
+        alpha = float(alpha)
+        if not 0.0 < alpha < 1.0:
+            raise ValueError(f"quantile_alpha must be in (0, 1), got {alpha}")
+        if obj == "reg:absoluteerror" and alpha != 0.5:
+            raise ValueError(f"reg:absoluteerror is the quantile 0.5: quantile_alpha={alpha} needs reg:quantileerror")
+        return None if obj == "reg:squarederror" else alpha
+
+    def fit(self, X, y, eval_set=None, early_stopping_rounds: int | None = None, verbose: bool = False, *,
+            sample_weight=None):
+        self._refresh_alpha()
+        return super().fit(X, y, eval_set, early_stopping_rounds, verbose, sample_weight=sample_weight)
+
+    def _base(self, y: np.ndarray, w: np.ndarray | None = None) -> float:
+        """The training mean, or the lower weighted alpha-quantile of y: the smallest label at which the weights of
+        the labels up to it, accumulated in double over the sorted labels, reach alpha times their total."""
+        alpha = self._refresh_alpha()
+        if alpha is None:
+            return super()._base(y, w)
+        order = np.argsort(y, kind="stable")
+        cum = np.cumsum(np.ones(len(y)) if w is None else w[order].astype(np.float64))
+        return float(y[order[min(int(np.searchsorted(cum, alpha * cum[-1], side="left")), len(y) - 1)]])
+
+    def _intercept(self, y: np.ndarray, w: np.ndarray | None) -> float:
+        return self._base(y, w) if self.base_score is None else float(self.base_score)
+
+    def _grad_hess(self, margin: np.ndarray, y: np.ndarray):
+        alpha = self._refresh_alpha()
+        if alpha is None:
+            return super()._grad_hess(margin, y)
+        d = margin - y
+        if self._objective == "reg:absoluteerror":
+            g = (d > 0).astype(np.float32) - (d < 0).astype(np.float32)
+        else:
+            g = np.where(d >= 0, np.float32(1.0 - alpha), np.float32(-alpha)).astype(np.float32)
+        return g, np.ones(len(y), np.float32)
+
+    def _metric_name(self) -> str:
+        return {"reg:squarederror": "rmse", "reg:absoluteerror": "mae", "reg:quantileerror": "quantile"}[self._objective]
+
+    def _metric(self, margin: np.ndarray, y: np.ndarray) -> float:
+        alpha = self._refresh_alpha()
+        if alpha is None:
+            return super()._metric(margin, y)
+        if self._objective == "reg:absoluteerror":
+            return float(np.mean(np.abs(margin - y)))
+        r = y - margin
+        return float(np.mean(np.maximum(alpha * r, (alpha - 1.0) * r)))
 
     def predict(self, X):
         """Margins: a numpy array for host input, a tensor on the input's device for a tensor on a GPU."""

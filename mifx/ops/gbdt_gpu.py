@@ -15,7 +15,13 @@ margins, with the tree index round * K + k as `round`.
 
 Leaf-wise growth (grow_policy="lossguide", csrc/gbdt_lossguide.hip): `LossguideBooster` has Booster's interface with
 a leaf budget `max_leaves` (tree arrays of 2 * max_leaves - 1 entries), `max_depth` 0 meaning no depth limit, and one
-[f] `feature_mask` per tree in place of the level mask; `grow_lossguide_numpy` is its one-tree entry for the tests."""
+[f] `feature_mask` per tree in place of the level mask; `grow_lossguide_numpy` is its one-tree entry for the tests.
+
+Absolute-error and quantile objectives (csrc/gbdt_quantile.hip): `grad_hess` knows "reg:absoluteerror" and
+"reg:quantileerror" (`alpha=`), and `leaf_refresh` replaces the leaf values of a finished tree by eta times the exact
+weighted alpha-quantile of the residuals of each leaf's rows (the rule of csrc/gbdt_quantile.h), from `leaf_of_row`,
+the margins from before the tree, y and the hessians. A round is grad_hess, `grow(..., margin=None)`, `leaf_refresh`,
+then `apply` on the training bins."""
 from __future__ import annotations
 
 import ctypes
@@ -72,6 +78,19 @@ def _lg_fns():
     }
 
 
+@functools.lru_cache(maxsize=None)
+def _q_fns():
+    lib = _lib.load("gbdt_quantile")
+    return {
+        "max_nodes": sig(lib, "mifx_gbdt_q_max_nodes", []),
+        "rows_per_wg": sig(lib, "mifx_gbdt_q_rows_per_wg", []),
+        "ws_bytes": sig(lib, "mifx_gbdt_q_ws_bytes", [LONG, I32, I32], I64),
+        "grad": sig(lib, "mifx_gbdt_q_grad", [VP, VP, VP, LONG, F64, VP, VP, VP]),
+        "refresh": sig(lib, "mifx_gbdt_q_refresh", [VP, VP, VP, VP, VP, LONG, I32, F64, F64, VP, I64, I32, VP]),
+        "stats": sig(lib, "mifx_gbdt_q_stats", [VP, LONG, I32, I32, VP, VP]),
+    }
+
+
 def check_limits_lossguide(n: int, max_bins: int, max_depth: int, max_leaves: int) -> None:
     """The leaf-wise device path's limits, checked before anything is launched (and without a GPU)."""
     fns = _lg_fns()
@@ -108,19 +127,28 @@ def upload_bins(bins: np.ndarray, dev: torch.device) -> torch.Tensor:
 
 
 def grad_hess(objective: str, margin: torch.Tensor, y: torch.Tensor, g: torch.Tensor, h: torch.Tensor,
-              weight: torch.Tensor | None = None) -> None:
+              weight: torch.Tensor | None = None, alpha: float = 0.5) -> None:
     """g, h (float32) of "reg:squarederror" or "binary:logistic" from float64 margins and labels; with `weight`
-    (float32 [n] on the device) each is the unweighted float32 value times the weight, one float32 multiply."""
-    obj = {"reg:squarederror": 0, "binary:logistic": 1}[objective]
+    (float32 [n] on the device) each is the unweighted float32 value times the weight, one float32 multiply.
+    "reg:absoluteerror" and "reg:quantileerror" (at `alpha`) are csrc/gbdt_quantile.h's pair: the sign of margin - y,
+    or float32(1 - alpha) / float32(-alpha) at and above / below y, with h = 1."""
+    obj = {"reg:squarederror": 0, "binary:logistic": 1, "reg:absoluteerror": 2, "reg:quantileerror": 3}[objective]
     assert margin.dtype == y.dtype == torch.float64 and g.dtype == h.dtype == torch.float32
     assert margin.is_contiguous() and y.is_contiguous() and g.is_contiguous() and h.is_contiguous()
     assert len(margin) == len(y) == len(g) == len(h)
+    if weight is not None:
+        assert weight.dtype == torch.float32 and weight.is_contiguous() and len(weight) == len(y)
+        assert weight.device == margin.device
+    if obj >= 2:
+        if obj == 3 and not 0.0 < alpha < 1.0:
+            raise ValueError(f"alpha must be in (0, 1), got {alpha}")
+        check(_q_fns()["grad"](ptr(margin), ptr(y), ptr(weight), len(y), float(alpha) if obj == 3 else -1.0, ptr(g),
+                               ptr(h), stream_handle(margin.device)), "mifx_gbdt_q_grad")
+        return
     if weight is None:
         check(_fns()["grad"](obj, ptr(margin), ptr(y), len(y), ptr(g), ptr(h), stream_handle(margin.device)),
               "mifx_gbdt_gpu_grad")
         return
-    assert weight.dtype == torch.float32 and weight.is_contiguous() and len(weight) == len(y)
-    assert weight.device == margin.device
     check(_fns()["grad_w"](obj, ptr(margin), ptr(y), ptr(weight), len(y), ptr(g), ptr(h),
                            stream_handle(margin.device)), "mifx_gbdt_gpu_grad_w")
 
@@ -140,6 +168,48 @@ def grad_hess_softmax(margin: torch.Tensor, y: torch.Tensor, g: torch.Tensor, h:
     K, n = margin.shape
     check(_fns()["grad_softmax"](ptr(margin), ptr(y), ptr(weight), n, K, ptr(g), ptr(h),
                                  stream_handle(margin.device)), "mifx_gbdt_gpu_grad_softmax")
+
+
+class LeafRefresh:
+    """The leaf refresh of the absolute-error / quantile objectives for trees over n rows with tree arrays of `cap`
+    node ids (csrc/gbdt_quantile.hip): holds the workspace (16 n bytes and small change). `_rows_per_wg` is launch
+    geometry -- the rows of a large segment that one workgroup takes per pass; a segment of at most
+    min(4096, _rows_per_wg) rows is selected by one workgroup out of LDS -- and changes no bit of the result."""
+
+    def __init__(self, n: int, cap: int, dev: torch.device, _rows_per_wg: int | None = None):
+        fns = _q_fns()
+        if not 1 <= cap <= fns["max_nodes"]():
+            raise ValueError(f"the leaf refresh supports trees of up to {fns['max_nodes']()} node ids, got {cap}")
+        self.n, self.cap, self.dev = int(n), int(cap), dev
+        self.rows = int(_rows_per_wg or fns["rows_per_wg"]())
+        nbytes = fns["ws_bytes"](self.n, self.cap, self.rows)
+        if nbytes < 0:
+            raise ValueError("shape or launch geometry outside the leaf refresh's limits")
+        self.ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+
+    def __call__(self, leaf_of_row: torch.Tensor, value: torch.Tensor, margin: torch.Tensor, y: torch.Tensor,
+                 h: torch.Tensor, alpha: float, eta: float) -> None:
+        """value[l] = eta * (weighted lower alpha-quantile of y - margin over the rows with leaf_of_row == l) for
+        every leaf l whose integer weights (the quantised h) sum to more than zero; everything else in `value` is
+        left alone. leaf_of_row int32 [n] (-1: not in the tree's sample), value float64 [cap], margin and y float64
+        [n], h float32 [n], all on the device; runs on the current stream and reads nothing back."""
+        assert leaf_of_row.dtype == torch.int32 and value.dtype == margin.dtype == y.dtype == torch.float64
+        assert h.dtype == torch.float32 and value.numel() == self.cap
+        assert len(leaf_of_row) == len(margin) == len(y) == len(h) == self.n
+        for t in (leaf_of_row, value, margin, y, h):
+            assert t.is_contiguous() and t.device == self.ws.device
+        if not 0.0 < alpha < 1.0:
+            raise ValueError(f"alpha must be in (0, 1), got {alpha}")
+        check(_q_fns()["refresh"](ptr(leaf_of_row), ptr(value), ptr(margin), ptr(y), ptr(h), self.n, self.cap,
+                                  float(alpha), float(eta), ptr(self.ws), self.ws.numel(), self.rows,
+                                  stream_handle(self.dev)), "mifx_gbdt_q_refresh")
+
+    def stats(self) -> tuple[int, int]:
+        """(select passes run, leaves refreshed) of the last call: for measurements, synchronises."""
+        out = (ctypes.c_int * 2)()
+        check(_q_fns()["stats"](ptr(self.ws), self.n, self.cap, self.rows, ctypes.cast(out, VP),
+                                stream_handle(self.dev)), "mifx_gbdt_q_stats")
+        return int(out[0]), int(out[1])
 
 
 def row_threshold(subsample: float) -> int:
