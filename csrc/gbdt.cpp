@@ -33,6 +33,9 @@
 //
 // Absolute / quantile error: mifx_gbdt_leaf_refresh replaces a finished tree's leaf values by exact weighted quantiles
 // of the residuals of each leaf's rows (the rule of gbdt_quantile.h; the device twin is gbdt_quantile.hip).
+//
+// Ranking: mifx_gbdt_rank_grad is the LambdaMART gradient pair of rank:pairwise / rank:ndcg over contiguous query
+// groups (the rule of gbdt_rank.h; the device twin is gbdt_rank.hip).
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -41,6 +44,7 @@
 #include <vector>
 
 #include "gbdt_quantile.h"
+#include "gbdt_rank.h"
 #include "gbdt_sample.h"
 #include "gbdt_shap.h"
 #include "gbdt_split.h"
@@ -569,6 +573,44 @@ int mifx_gbdt_leaf_refresh(const double* resid, const float* h, const int* leaf_
         value[l] = mifx_gq_value(r->key, eta);
         return;
       }
+  });
+  return 0;
+}
+
+// ---- the LambdaMART pair of rank:pairwise (objective 0) / rank:ndcg (objective 1), gbdt_rank.h has the rule. margin
+// [n], y [n] (integer labels in [0, 31] as doubles), gptr [G + 1] the groups' row offsets, D and P the discount table
+// and its prefix sums (each longer than the largest group), topk 0 for every pair. A plain sort per group, then every
+// row walks its partners in rank order. The groups are independent: the same bits for any thread count. Returns 0, or
+// -1 for offsets that do not cover [0, n] in order or a label outside [0, 31].
+int mifx_gbdt_rank_grad(int objective, const double* margin, const double* y, const long* gptr, long G, const double* D,
+                        const double* P, int topk, float* g, float* h, int threads) {
+  if (objective < 0 || objective > 1 || G < 0 || topk < 0 || gptr[0] != 0) return -1;
+  for (long q = 0; q < G; ++q)
+    if (gptr[q + 1] < gptr[q] || gptr[q + 1] - gptr[q] > 0x7FFFFFFF) return -1;
+  for (long i = 0; i < gptr[G]; ++i)
+    if (!(y[i] >= 0.0 && y[i] < (double)kMifxRankLabels) || y[i] != (double)(int)y[i]) return -1;
+  parallel_for((int)std::min<long>(G, 0x7FFFFFFF), gptr[G] > 2000 ? threads : 1, [&](int q) {
+    const long b = gptr[q];
+    const int m = (int)(gptr[q + 1] - b);
+    std::vector<uint64_t> key(m);
+    std::vector<int> at(m), label(m), cnt(kMifxRankLabels, 0);
+    for (int i = 0; i < m; ++i) {
+      key[i] = mifx_sort_key(margin[b + i]);
+      at[i] = i;
+      ++cnt[label[i] = (int)y[b + i]];
+    }
+    std::sort(at.begin(), at.end(), [&](int i, int j) { return mifx_rk_before(key[i], i, key[j], j); });
+    const double idcg = objective ? mifx_rk_idcg(cnt.data(), P) : 0.0;
+    for (int ra = 0; ra < m; ++ra) {
+      const int a = at[ra], end = mifx_rk_partner_end(ra, m, topk);
+      double gs = 0.0, hs = 0.0;
+      for (int r = 0; r < end; ++r)
+        if (label[at[r]] != label[a])
+          mifx_rk_accum(objective != 0, idcg, margin[b + a], label[a], D[ra], margin[b + at[r]], label[at[r]], D[r],
+                        &gs, &hs);
+      g[b + a] = (float)gs;
+      h[b + a] = (float)hs;
+    }
   });
   return 0;
 }

@@ -85,7 +85,26 @@ so the GPU (csrc/gbdt_quantile.hip: a segmented weighted radix select over the l
 host twin bit for bit, for any launch geometry. With `base_score=None` the intercept is the same lower weighted
 a-quantile of y (float32 weights accumulated in double over the sorted labels). The eval metric is "mae" or "quantile"
 (the mean pinball loss at a), unweighted. `gain` and `cover` stay the grower's. Several quantiles in one model,
-XGBoost's interpolation and reg:pseudohubererror are not implemented."""
+XGBoost's interpolation and reg:pseudohubererror are not implemented.
+
+Learning to rank, on all three learners: `XGBRanker(objective="rank:ndcg" | "rank:pairwise")`, LambdaMART over query
+groups given to `fit` as `qid` (non-decreasing, one per row) or `group` (sizes). The gradient pair is not a row's own:
+inside a group the rows are ranked by margin, descending (on the integer key of csrc/gbdt_sort_key.h, ties to the
+lower row), and every pair (i, j) with label_i > label_j adds, with s = m_i - m_j and rho = 1 / (1 + exp(s)),
+lambda = rho * delta to g_j and -lambda to g_i, and eta = 2 max(rho (1 - rho), 1e-16) delta to both hessians; delta is
+1 (rank:pairwise) or |(2^l_i - 2^l_j) (D[r_i] - D[r_j])| / IDCG with D[r] = 1 / log2(r + 2) (rank:ndcg). Labels are
+integers in [0, 31]. `lambdarank_pair_method="all"` (our default) counts every such pair, "topk" with
+`lambdarank_num_pair_per_sample=k` those with a row ranked above k. The rule has one copy, csrc/gbdt_rank.h: a row's
+sums run in double over its partners in rank order, so they depend on no thread count or launch geometry; the host
+function is `rank_grad` (mifx_gbdt_rank_grad), the device path csrc/gbdt_rank.hip (one wave per group of up to 64 rows,
+one workgroup with a bitonic sort in LDS per group of up to 4096; a longer group raises ValueError on the device, there
+is no host fallback). Host and device differ only in exp (a few double ulps per term): the first tree, grown from
+equal margins, is equal bit for bit, later ones are not promised to be. Everything downstream is unchanged: sampling,
+both growth policies, `predict` (margins), contributions, interactions and importances. The intercept is `base_score`
+or 0.0. The eval metric is "ndcg" or "ndcg@k" (the mean over groups, a group without a relevant row scores 1.0) and is
+MAXIMISED by early stopping. Not implemented: group and row weights (`sample_weight` raises), rank:map,
+`lambdarank_normalization` and XGBoost's score-difference normalisation, "mean" pair sampling (XGBoost's default pair
+method is "topk": pass it explicitly to follow it), unbiased LambdaMART."""
 from __future__ import annotations
 
 import ctypes
@@ -132,11 +151,13 @@ def _lib():
                                          _U8]
     lib.mifx_gbdt_leaf_refresh.argtypes = [_D, _F, _I, ctypes.c_long, ctypes.c_int, ctypes.c_double, ctypes.c_double,
                                            _D, ctypes.c_int]
+    lib.mifx_gbdt_rank_grad.argtypes = [ctypes.c_int, _D, _D, ctypes.POINTER(ctypes.c_long), ctypes.c_long, _D, _D,
+                                        ctypes.c_int, _F, _F, ctypes.c_int]
     for f in (lib.mifx_gbdt_cuts, lib.mifx_gbdt_bin, lib.mifx_gbdt_grow, lib.mifx_gbdt_predict,
               lib.mifx_gbdt_grow_fixed, lib.mifx_gbdt_quant_exp, lib.mifx_gbdt_grow_ex, lib.mifx_gbdt_grow_fixed_ex,
               lib.mifx_gbdt_sample_features, lib.mifx_gbdt_level_mask, lib.mifx_gbdt_grow_stats,
               lib.mifx_gbdt_grow_fixed_stats, lib.mifx_gbdt_grow_lossguide_stats,
-              lib.mifx_gbdt_grow_fixed_lossguide_stats, lib.mifx_gbdt_leaf_refresh):
+              lib.mifx_gbdt_grow_fixed_lossguide_stats, lib.mifx_gbdt_leaf_refresh, lib.mifx_gbdt_rank_grad):
         f.restype = ctypes.c_int
     return lib
 
@@ -200,6 +221,59 @@ def leaf_refresh(resid: np.ndarray, h: np.ndarray, leaf_of_row: np.ndarray, valu
     if _lib().mifx_gbdt_leaf_refresh(_p(resid, _D), _p(h, _F), _p(leaf_of_row, _I), n, len(value), float(alpha),
                                      float(eta), _p(value, _D), int(threads)) != 0:
         raise ValueError("leaf_of_row holds a leaf outside the tree")
+
+
+_RANK_OBJECTIVES = {"rank:pairwise": 0, "rank:ndcg": 1}
+
+
+def discount_tables(max_size: int):
+    """(D, P) of csrc/gbdt_rank.h, float64 [max_size + 1] each: D[r] = 1 / log2(r + 2) and its exclusive prefix sums,
+    summed sequentially. The one place they are computed: the host function and the device kernels read these bits."""
+    D = 1.0 / np.log2(np.arange(max_size + 1, dtype=np.float64) + 2.0)
+    P = np.zeros(max_size + 1, np.float64)
+    np.cumsum(D[:-1], out=P[1:])
+    return D, P
+
+
+def rank_grad(objective: str, margin: np.ndarray, y: np.ndarray, gptr: np.ndarray, topk: int = 0, threads: int = 1):
+    """mifx_gbdt_rank_grad (csrc/gbdt.cpp): the float32 LambdaMART pair (g, h) of "rank:pairwise" or "rank:ndcg" from
+    float64 margins and labels (integers in [0, 31]) over the contiguous query groups with row offsets gptr [G + 1];
+    topk = k >= 1 keeps the pairs with a row ranked above k, 0 all of them. The rule is csrc/gbdt_rank.h."""
+    margin, y = np.ascontiguousarray(margin, np.float64), np.ascontiguousarray(y, np.float64)
+    gptr = np.ascontiguousarray(gptr, np.int64)
+    if len(gptr) < 1 or gptr[-1] != len(y) or len(margin) != len(y):
+        raise ValueError("gptr must cover every row: one margin and one label per row")
+    D, P = discount_tables(int(np.diff(gptr).max()) if len(gptr) > 1 else 0)
+    g, h = np.empty(len(y), np.float32), np.empty(len(y), np.float32)
+    if _lib().mifx_gbdt_rank_grad(_RANK_OBJECTIVES[objective], _p(margin, _D), _p(y, _D),
+                                  _p(gptr, ctypes.POINTER(ctypes.c_long)), len(gptr) - 1, _p(D, _D), _p(P, _D),
+                                  int(topk), _p(g, _F), _p(h, _F), int(threads)) != 0:
+        raise ValueError("gptr must ascend from 0, labels must be integers in [0, 31] and topk >= 0")
+    return g, h
+
+
+def _rank_order(margin: np.ndarray, gid: np.ndarray) -> np.ndarray:
+    """Row ids group by group, each group in the rank order of csrc/gbdt_rank.h: margin descending on the integer
+    key of csrc/gbdt_sort_key.h (+0.0 above -0.0), ties to the lower row."""
+    b = np.ascontiguousarray(margin, np.float64).view(np.uint64)
+    key = np.where(b >> np.uint64(63), ~b, b | np.uint64(1 << 63))
+    return np.lexsort((~key, gid))  # (stable: equal keys keep their row order)
+
+
+def ndcg(margin: np.ndarray, y: np.ndarray, gptr: np.ndarray, k: int = 0) -> float:
+    """Mean NDCG over the groups (XGBoost's "ndcg", "ndcg@k" for k >= 1): gains 2^label - 1, discounts
+    1 / log2(rank + 2), @k truncating both DCG and IDCG; a group without a relevant row scores 1.0."""
+    G = len(gptr) - 1
+    sizes = np.diff(gptr)
+    gid = np.repeat(np.arange(G), sizes)
+    pos = np.arange(len(y)) - np.repeat(gptr[:-1], sizes)
+    disc = 1.0 / np.log2(pos + 2.0)
+    if k > 0:
+        disc = np.where(pos < k, disc, 0.0)
+    gain = np.exp2(y) - 1.0
+    dcg = np.bincount(gid, gain[_rank_order(margin, gid)] * disc, minlength=G)
+    idcg = np.bincount(gid, gain[np.lexsort((-y, gid))] * disc, minlength=G)
+    return float(np.mean(np.where(idcg > 0, dcg / np.where(idcg > 0, idcg, 1.0), 1.0))) if G else 1.0
 
 
 def _threads() -> int:
@@ -347,8 +421,16 @@ class _Base:
     def _metric(self, margin: np.ndarray, y: np.ndarray) -> float:
         return float(np.sqrt(np.mean((margin - y) ** 2)))
 
+    def _better(self, score: float, best: float) -> bool:
+        """Whether an eval score improves on the best so far: every metric but the ranker's is minimised."""
+        return score < best
+
     def _check_y(self, y: np.ndarray) -> np.ndarray:
         return y.astype(np.float64)
+
+    def _device_grad(self, G, margin, yd, g, h, wd, alpha) -> None:
+        """The single-margin gradient launch of the device loop (the ranker has its own kernel)."""
+        G.grad_hess(self._objective, margin, yd, g, h, wd, alpha=0.5 if alpha is None else alpha)
 
     # ---- training
     def _bin_matrix(self, X: np.ndarray):
@@ -475,7 +557,7 @@ class _Base:
                 hist.append(score)
                 if verbose:
                     logging.info("[%d]\tvalidation_0-%s:%.5f", it, self._metric_name(), score)
-                if best is None or score < best:
+                if best is None or self._better(score, best):
                     best, best_it, since = score, it, 0
                 else:
                     since += 1
@@ -559,7 +641,7 @@ class _Base:
                 if K > 1:  # every class's pair from the margins at the start of the round, one launch
                     G.grad_hess_softmax(margin, yd, g, h, wd)
                 else:
-                    G.grad_hess(self._objective, margin[0], yd, g[0], h[0], wd, alpha=0.5 if alpha is None else alpha)
+                    self._device_grad(G, margin[0], yd, g[0], h[0], wd, alpha)
                 for k in range(K):
                     tree = tuple(t[it * K + k] for t in trees)
                     bst.grow(g[k], h[k], tree, self.min_child_weight, self.reg_lambda, self.gamma, self.learning_rate,
@@ -578,7 +660,7 @@ class _Base:
                     hist.append(score)
                     if verbose:
                         logging.info("[%d]\tvalidation_0-%s:%.5f", it, self._metric_name(), score)
-                    if best is None or score < best:
+                    if best is None or self._better(score, best):
                         best, best_it, since = score, it, 0
                     else:
                         since += 1
@@ -1004,3 +1086,128 @@ class XGBClassifier(_Base):
             k = torch.arange(len(m), device=m.device)[:, None]  # the lowest class among the largest margins
             return self.classes_[_host(torch.where(m == m.max(0).values, k, len(m)).min(0).values)]
         return self.classes_[_host(self.predict_proba(X)[:, 1] > 0.5).astype(int)]
+
+
+class XGBRanker(_Base):
+    """Learning to rank: LambdaMART on "rank:ndcg" (the default) or "rank:pairwise" over query groups given by `qid`
+    or `group`; `predict` returns margins (the module docstring has the rule)."""
+    _OBJECTIVES = tuple(_RANK_OBJECTIVES)
+
+    def __init__(self, *args, objective: str = "rank:ndcg", lambdarank_pair_method: str = "all",
+                 lambdarank_num_pair_per_sample: int | None = None, eval_metric: str = "ndcg", **kwargs):
+        """The parameters of _Base, the objective, the pair method ("all": every pair of a group with different
+        labels, our default; "topk" with lambdarank_num_pair_per_sample = k >= 1: the pairs with a row ranked above k)
+        and the eval metric ("ndcg" or "ndcg@k")."""
+        super().__init__(*args, **kwargs)
+        self.objective, self.eval_metric = objective, eval_metric
+        self.lambdarank_pair_method = lambdarank_pair_method
+        self.lambdarank_num_pair_per_sample = lambdarank_num_pair_per_sample
+        self._topk()
+        self._metric_k()
+
+    @property
+    def _objective(self) -> str:
+        return self.objective
+
+    def _topk(self) -> int:
+        """The k of the pair rule (0: every pair), after the constructor arguments are checked."""
+        if self.objective not in self._OBJECTIVES:
+            raise ValueError(f"objective must be one of {self._OBJECTIVES}, got {self.objective!r}")
+        method, k = self.lambdarank_pair_method, self.lambdarank_num_pair_per_sample
+        if method == "all":
+            if k is not None:
+                raise ValueError("lambdarank_num_pair_per_sample needs lambdarank_pair_method='topk'")
+            return 0
+        if method != "topk":
+            raise ValueError(f"lambdarank_pair_method must be 'all' or 'topk' ('mean' is not implemented), got "
+                             f"{method!r}")
+        if k is None or int(k) != k or int(k) < 1:
+            raise ValueError(f"lambdarank_pair_method='topk' needs lambdarank_num_pair_per_sample >= 1, got {k!r}")
+        return int(k)
+
+    def _metric_k(self) -> int:
+        name = str(self.eval_metric)
+        if name == "ndcg":
+            return 0
+        if name.startswith("ndcg@") and name[5:].isdigit() and int(name[5:]) >= 1:
+            return int(name[5:])
+        raise ValueError(f"eval_metric must be 'ndcg' or 'ndcg@k' with k >= 1, got {name!r}")
+
+    @staticmethod
+    def _group_ptr(n: int, qid, group, what: str) -> np.ndarray:
+        """int64 [G + 1] row offsets from exactly one of qid (non-decreasing, one per row) and group (sizes)."""
+        if (qid is None) == (group is None):
+            raise ValueError(f"{what}: exactly one of qid and group must be given")
+        if group is not None:
+            sizes = np.asarray(_host(group)).reshape(-1)
+            if (sizes < 0).any() or (sizes != sizes.astype(np.int64)).any() or int(sizes.sum()) != n:
+                raise ValueError(f"{what}: group must hold non-negative sizes that sum to the number of rows ({n})")
+            return np.concatenate([[0], np.cumsum(sizes.astype(np.int64))]).astype(np.int64)
+        qid = np.asarray(_host(qid)).reshape(-1)
+        if len(qid) != n:
+            raise ValueError(f"{what}: qid must hold one id per row ({n}), got {len(qid)}")
+        if n and (qid[1:] < qid[:-1]).any():
+            raise ValueError(f"{what}: qid must be non-decreasing (sort the rows by query)")
+        return np.concatenate([[0], np.flatnonzero(qid[1:] != qid[:-1]) + 1, [n]]).astype(np.int64)
+
+    def fit(self, X, y, *, qid=None, group=None, eval_set=None, eval_qid=None, eval_group=None,
+            early_stopping_rounds: int | None = None, verbose: bool = False, sample_weight=None):
+        """Fit the ranker. Exactly one of `qid` (one non-decreasing query id per row) and `group` (the groups' sizes,
+        in row order) names the query groups; the LAST eval set takes its groups from the last entry of `eval_qid` or
+        `eval_group`. Labels are integers in [0, 31]. Data may be where _Base.fit takes it. `sample_weight` (group or
+        row weights) is not implemented and raises ValueError. With device="gpu" a group of more than
+        mifx.ops.gbdt_rank.max_group() rows raises ValueError before anything is launched."""
+        self._topk()
+        self._metric_k()
+        if sample_weight is not None:
+            raise ValueError("XGBRanker: sample_weight (group and row weights) is not implemented")
+        self._check_data_device(X, y)
+        n = len(_host(y).reshape(-1))
+        ctx = {"gptr": self._group_ptr(n, qid, group, "fit")}
+        if eval_set:
+            eq, eg = (None if v is None else v[-1] for v in (eval_qid, eval_group))
+            if eq is None and eg is None:
+                raise ValueError("an eval set needs its query groups: eval_qid or eval_group, one entry per eval set")
+            ctx["eval_gptr"] = self._group_ptr(len(_host(eval_set[-1][1]).reshape(-1)), eq, eg, "eval set")
+        if self._gpu_index() is not None:
+            from ..ops import gbdt_rank as R
+
+            R.check_groups(ctx["gptr"])
+        self._fit_ctx = ctx
+        try:
+            return super().fit(X, y, eval_set, early_stopping_rounds, verbose)
+        finally:
+            del self._fit_ctx  # the groups and the device plan belong to the fit, not to the model
+
+    def _check_y(self, y: np.ndarray) -> np.ndarray:
+        y = np.asarray(y)
+        if y.dtype.kind not in "biuf" or not np.isin(y, np.arange(32)).all():
+            raise ValueError("XGBRanker: labels must be integers in [0, 31] (relevance grades)")
+        return y.astype(np.float64)
+
+    def _intercept(self, y: np.ndarray, w: np.ndarray | None) -> float:
+        return 0.0 if self.base_score is None else float(self.base_score)
+
+    def _grad_hess(self, margin: np.ndarray, y: np.ndarray):
+        return rank_grad(self.objective, margin, y, self._fit_ctx["gptr"], self._topk(), self._nthreads())
+
+    def _device_grad(self, G, margin, yd, g, h, wd, alpha) -> None:
+        from ..ops import gbdt_rank as R
+
+        if "plan" not in self._fit_ctx:  # once per fit: the groups do not change between rounds
+            self._fit_ctx["plan"] = R.RankPlan(self._fit_ctx["gptr"], margin.device)
+        R.grad_hess_rank(self.objective, margin, yd, self._fit_ctx["plan"], g, h, self._topk())
+
+    def _metric_name(self) -> str:
+        return str(self.eval_metric)
+
+    def _metric(self, margin: np.ndarray, y: np.ndarray) -> float:
+        return ndcg(margin, y, self._fit_ctx["eval_gptr"], self._metric_k())
+
+    def _better(self, score: float, best: float) -> bool:
+        return score > best  # NDCG is maximised
+
+    def predict(self, X):
+        """Margins (the ranking scores): a numpy array for host input, a tensor on the input's device for a tensor on
+        a GPU."""
+        return self._margin(X)
