@@ -36,6 +36,9 @@
 //
 // Ranking: mifx_gbdt_rank_grad is the LambdaMART gradient pair of rank:pairwise / rank:ndcg over contiguous query
 // groups (the rule of gbdt_rank.h; the device twin is gbdt_rank.hip).
+//
+// eval_metric="auc": mifx_gbdt_auc gives the exact integer pair counts of the one-vs-rest AUC per class (the rule of
+// gbdt_auc.h; the device twin is gbdt_auc.hip).
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -43,6 +46,7 @@
 #include <thread>
 #include <vector>
 
+#include "gbdt_auc.h"
 #include "gbdt_quantile.h"
 #include "gbdt_rank.h"
 #include "gbdt_sample.h"
@@ -611,6 +615,32 @@ int mifx_gbdt_rank_grad(int objective, const double* margin, const double* y, co
       g[b + a] = (float)gs;
       h[b + a] = (float)hs;
     }
+  });
+  return 0;
+}
+
+// ---- the integers of eval_metric="auc", gbdt_auc.h has the rule. margin [K, m] class-major, y [m] the class index as
+// a double (K = 1: 0.0 / 1.0, class 0's margins scored against y == 1; K >= 2: row k against y == k). out [K, 3]:
+// (U2, P, N) per class. The 2 K (class, side) lists sort side by side, then one merge walk per class: integer counts,
+// the same for any thread count. Returns 0, -1 for bad arguments, -2 for a margin that is not finite.
+int mifx_gbdt_auc(const double* margin, const double* y, long m, int K, long long* out, int threads) {
+  if (m < 0 || m >= (1L << 31) || K < 1) return -1;
+  for (long i = 0; i < (long)K * m; ++i)
+    if (!std::isfinite(margin[i])) return -2;
+  std::vector<std::vector<double>> side(2 * (size_t)K);
+  parallel_for(2 * K, (long)K * m > 20000 ? threads : 1, [&](int s) {
+    const int k = s >> 1;
+    const double want = K == 1 ? 1.0 : (double)k;
+    std::vector<double>& v = side[s];
+    for (long i = 0; i < m; ++i)
+      if ((y[i] == want) == (bool)(s & 1)) v.push_back(margin[(size_t)k * m + i]);
+    std::sort(v.begin(), v.end());
+  });
+  parallel_for(K, (long)K * m > 20000 ? threads : 1, [&](int k) {
+    const std::vector<double>&neg = side[2 * k], &pos = side[2 * k + 1];
+    out[3 * k + 0] = mifx_auc_merge(neg.data(), (long)neg.size(), pos.data(), (long)pos.size());
+    out[3 * k + 1] = (long long)pos.size();
+    out[3 * k + 2] = (long long)neg.size();
   });
   return 0;
 }

@@ -3,8 +3,8 @@ csrc/gbdt.cpp (second-order split gain, learned missing-value directions, depth-
 
 Reference usage: `kubeflow-pipelines/fairing/fairing_xgboost.py:69-87` (XGBRegressor(n_estimators, learning_rate),
 fit with `early_stopping_rounds` and `eval_set`, then `best_score`, `best_iteration`, `predict`). Semantics follow
-XGBoost's scikit-learn API: the eval metric is RMSE (regression), logloss (two classes) or mlogloss (more) on the LAST
-eval set; with early stopping, training stops after `early_stopping_rounds` rounds without improvement and
+XGBoost's scikit-learn API: the eval metric is RMSE (regression), logloss (two classes) or mlogloss (more), or the
+classifier's `eval_metric="auc"` (below), on the LAST eval set; with early stopping, training stops after `early_stopping_rounds` rounds without improvement and
 `predict` uses the trees up to `best_iteration` (XGBoost >= 1.4's default `iteration_range`). Defaults are
 XGBoost >= 1.0's (learning_rate 0.3, max_depth 6, reg_lambda 1, min_child_weight 1, gamma 0, 256 bins); the
 intercept is the training mean (regression) or its log-odds (classification), XGBoost 2's `base_score` estimate.
@@ -104,7 +104,25 @@ both growth policies, `predict` (margins), contributions, interactions and impor
 or 0.0. The eval metric is "ndcg" or "ndcg@k" (the mean over groups, a group without a relevant row scores 1.0) and is
 MAXIMISED by early stopping. Not implemented: group and row weights (`sample_weight` raises), rank:map,
 `lambdarank_normalization` and XGBoost's score-difference normalisation, "mean" pair sampling (XGBoost's default pair
-method is "topk": pass it explicitly to follow it), unbiased LambdaMART."""
+method is "topk": pass it explicitly to follow it), unbiased LambdaMART.
+
+Validation AUC, on all three learners: `XGBClassifier(eval_metric="auc")`; `eval_metric=None` (the default) keeps
+logloss / mlogloss, which may also be named; anything else, or a name that does not fit the number of classes, raises
+ValueError. `evals_result_["validation_0"]["auc"]` holds the history and early stopping MAXIMISES it. The rule has one
+copy, csrc/gbdt_auc.h: unweighted, margins compared numerically as doubles (-0.0 ties +0.0), and per class the int64
+U2 = sum over positives i of (2 #{negatives below m_i} + #{negatives equal to m_i}) <= 2 P N. The score is formed from
+the integers by `auc_score`, the one function both learners call, in exact rational arithmetic rounded once:
+U2 / (2 P N) for two classes, XGBoost's one-vs-rest average weighted by prevalence, sum_k P_k auc_k / sum_k P_k with
+class k's margin row scored against y == k, for K >= 3. The host function is `auc` (mifx_gbdt_auc: a sort per class
+and side, one merge walk); with device="gpu" the eval margins are NOT read back: mifx/ops/gbdt_auc.py fills a
+[m, 2 K] table (a class's negatives and positives as two NaN-padded columns), sorts all columns at once with the
+batched radix sort of the cuts (csrc/gbdt_sort.hip) and counts the pairs in csrc/gbdt_auc.hip (one workgroup per tile
+of sorted positives, its span of the sorted negatives staged through LDS, integer adds only), and K integers come
+back per round. Equal integers give equal bits, so the device score equals the host twin's for any launch geometry.
+An eval set in which some class has no positive or no negative row raises ValueError in `fit`, before the first
+round; the host function refuses margins that are not finite (the device path does not check: a fit's margins are
+finite by construction); the device path takes up to 256 classes. Not implemented: weighted AUC, aucpr, error, map,
+AUC for XGBRanker; the other metrics keep their host path (their margins are read back once per round)."""
 from __future__ import annotations
 
 import ctypes
@@ -153,11 +171,13 @@ def _lib():
                                            _D, ctypes.c_int]
     lib.mifx_gbdt_rank_grad.argtypes = [ctypes.c_int, _D, _D, ctypes.POINTER(ctypes.c_long), ctypes.c_long, _D, _D,
                                         ctypes.c_int, _F, _F, ctypes.c_int]
+    lib.mifx_gbdt_auc.argtypes = [_D, _D, ctypes.c_long, ctypes.c_int, ctypes.POINTER(ctypes.c_longlong), ctypes.c_int]
     for f in (lib.mifx_gbdt_cuts, lib.mifx_gbdt_bin, lib.mifx_gbdt_grow, lib.mifx_gbdt_predict,
               lib.mifx_gbdt_grow_fixed, lib.mifx_gbdt_quant_exp, lib.mifx_gbdt_grow_ex, lib.mifx_gbdt_grow_fixed_ex,
               lib.mifx_gbdt_sample_features, lib.mifx_gbdt_level_mask, lib.mifx_gbdt_grow_stats,
               lib.mifx_gbdt_grow_fixed_stats, lib.mifx_gbdt_grow_lossguide_stats,
-              lib.mifx_gbdt_grow_fixed_lossguide_stats, lib.mifx_gbdt_leaf_refresh, lib.mifx_gbdt_rank_grad):
+              lib.mifx_gbdt_grow_fixed_lossguide_stats, lib.mifx_gbdt_leaf_refresh, lib.mifx_gbdt_rank_grad,
+              lib.mifx_gbdt_auc):
         f.restype = ctypes.c_int
     return lib
 
@@ -278,6 +298,47 @@ def ndcg(margin: np.ndarray, y: np.ndarray, gptr: np.ndarray, k: int = 0) -> flo
 
 def _threads() -> int:
     return max(1, min(16, int(os.environ.get("OMP_NUM_THREADS", os.cpu_count() or 1))))
+
+
+def auc_counts(margin: np.ndarray, y: np.ndarray, threads: int | None = None):
+    """mifx_gbdt_auc (csrc/gbdt.cpp; the rule is csrc/gbdt_auc.h): (U2, P, N), int64 [K] each, of margins [n] (K = 1:
+    y is 0 / 1, 1 the positive) or class-major [K, n] (y the class index, row k scored against y == k). U2_k counts 2
+    for every (negative, positive) pair of class k with the positive's margin above and 1 for every tied pair, margins
+    compared as doubles. Refuses margins that are not finite."""
+    margin = np.ascontiguousarray(margin, np.float64)
+    margin = margin[None] if margin.ndim == 1 else margin
+    y = np.ascontiguousarray(np.asarray(y).reshape(-1), np.float64)
+    K, m = margin.shape[0], margin.shape[-1]
+    if margin.ndim != 2 or len(y) != m or m >= 2 ** 31:
+        raise ValueError("auc: margins must be [n] or [K, n] with one label per row (n < 2^31)")
+    if ((y != np.floor(y)) | (y < 0) | (y >= max(K, 2))).any():
+        raise ValueError(f"auc: labels must be class indices in [0, {max(K, 2)})")
+    out = np.zeros((K, 3), np.int64)
+    rc = _lib().mifx_gbdt_auc(_p(margin, _D), _p(y, _D), m, K, _p(out, ctypes.POINTER(ctypes.c_longlong)),
+                              int(threads or _threads()))
+    if rc != 0:
+        raise ValueError("auc: the margins must be finite" if rc == -2 else "auc: bad arguments")
+    return out[:, 0].copy(), out[:, 1].copy(), out[:, 2].copy()
+
+
+def auc_score(U2, P, N) -> float:
+    """The AUC from the integers of `auc_counts` or of the device kernels (mifx.ops.gbdt_auc), the one place it is
+    formed: U2 / (2 P N) for one class, XGBoost's one-vs-rest average weighted by prevalence, sum_k P_k auc_k / sum_k
+    P_k, for several -- exact rational arithmetic, rounded once. A class without a positive or a negative row raises."""
+    from fractions import Fraction
+
+    U2, P, N = ([int(v) for v in np.ravel(a)] for a in (U2, P, N))
+    if not P or any(p <= 0 for p in P) or any(n <= 0 for n in N):
+        raise ValueError("auc is undefined on an eval set in which a class has no positive or no negative row")
+    return float(sum(Fraction(u, 2 * n) for u, n in zip(U2, N)) / sum(P))
+
+
+def auc(margin: np.ndarray, y: np.ndarray, threads: int | None = None, return_counts: bool = False):
+    """Unweighted AUC of margins [n] against 0 / 1 labels, or of class-major margins [K, n] against class indices
+    (one-vs-rest, weighted by prevalence): `auc_score` of `auc_counts`. With return_counts, (score, (U2, P, N))."""
+    counts = auc_counts(margin, y, threads)
+    score = auc_score(*counts)
+    return (score, counts) if return_counts else score
 
 
 class _Base:
@@ -422,11 +483,19 @@ class _Base:
         return float(np.sqrt(np.mean((margin - y) ** 2)))
 
     def _better(self, score: float, best: float) -> bool:
-        """Whether an eval score improves on the best so far: every metric but the ranker's is minimised."""
+        """Whether an eval score improves on the best so far: every metric but NDCG and AUC is minimised."""
         return score < best
 
     def _check_y(self, y: np.ndarray) -> np.ndarray:
         return y.astype(np.float64)
+
+    def _check_eval(self, ey: np.ndarray) -> None:
+        """Refuses, before the first round, an eval set the metric is not defined on (the classifier's AUC)."""
+
+    def _device_metric(self, ey: np.ndarray, dev):
+        """A callable scoring the eval margins on the device ([K, m] tensor -> float), built once per fit, or None:
+        the margins are then read back and scored by _metric on the host."""
+        return None
 
     def _device_grad(self, G, margin, yd, g, h, wd, alpha) -> None:
         """The single-margin gradient launch of the device loop (the ranker has its own kernel)."""
@@ -530,6 +599,7 @@ class _Base:
             ex, ey = eval_set[-1]
             ex = np.ascontiguousarray(np.asarray(ex, dtype=np.float64))
             ey = self._check_y(np.asarray(ey).reshape(-1))
+            self._check_eval(ey)
             ev_margin = np.full((K, len(ey)), self._base_margin)
             ev = (ex, ey, ev_margin)
         self._trees, self._node_stats = [], []
@@ -632,11 +702,13 @@ class _Base:
                 ey = self._check_y(_host(ey).reshape(-1))
                 if ex.ndim != 2 or ex.shape[1] != self._nfeat or len(ex) != len(ey) or not len(ey):
                     raise ValueError(f"the eval set must be [m, {self._nfeat}] with one label per row")
+                self._check_eval(ey)
                 ev = (P.device_bins(P.as_device_matrix(ex, dev), tables), ey,
                       torch.full((K, len(ey)), self._base_margin, dtype=torch.float64, device=dev))
             best, best_it, since, hist, done = None, 0, 0, [], 0
             alpha = self._refresh_alpha()
             refresh = None if alpha is None else G.LeafRefresh(len(y), bst.cap, dev)
+            dev_metric = None if ev is None else self._device_metric(ev[1], dev)
             for it in range(rounds):
                 if K > 1:  # every class's pair from the margins at the start of the round, one launch
                     G.grad_hess_softmax(margin, yd, g, h, wd)
@@ -655,8 +727,11 @@ class _Base:
                         bst.apply(ev[0], tree, ev[2][k])
                 done = (it + 1) * K
                 if ev is not None:
-                    em = ev[2].cpu().numpy()  # the round's one read-back
-                    score = self._metric(em if K > 1 else em[0], ev[1])
+                    if dev_metric is not None:  # scored where the margins are: only the metric's integers come back
+                        score = dev_metric(ev[2])
+                    else:
+                        em = ev[2].cpu().numpy()  # the round's one read-back
+                        score = self._metric(em if K > 1 else em[0], ev[1])
                     hist.append(score)
                     if verbose:
                         logging.info("[%d]\tvalidation_0-%s:%.5f", it, self._metric_name(), score)
@@ -955,11 +1030,34 @@ class XGBClassifier(_Base):
     tree t for class t % K). Labels are any sortable values (classes_ sorted)."""
     _objective = "binary:logistic"
 
-    def __init__(self, *args, scale_pos_weight: float = 1.0, **kwargs):
-        """The parameters of XGBRegressor, and scale_pos_weight (> 0): a factor on the weights of class-1 rows."""
+    _EVAL_METRICS = (None, "logloss", "mlogloss", "auc")
+
+    def __init__(self, *args, scale_pos_weight: float = 1.0, eval_metric: str | None = None, **kwargs):
+        """The parameters of _Base, scale_pos_weight (> 0): a factor on the weights of class-1 rows, and eval_metric:
+        None (the default: logloss for two classes, mlogloss for more), that default by name, or "auc"."""
         super().__init__(*args, **kwargs)
-        self.scale_pos_weight = scale_pos_weight
+        self.scale_pos_weight, self.eval_metric = scale_pos_weight, eval_metric
         self._check_spw()
+        self._auc()
+
+    def _auc(self) -> bool:
+        """Whether the eval metric is AUC, after the argument is checked (None for a model pickled before it existed)."""
+        name = getattr(self, "eval_metric", None)
+        if name not in self._EVAL_METRICS:
+            raise ValueError(f"eval_metric must be one of {self._EVAL_METRICS}, got {name!r}")
+        return name == "auc"
+
+    def _check_eval(self, ey: np.ndarray) -> None:
+        if self._auc():  # (raises for a class without a positive or a negative row)
+            P = np.bincount(ey.astype(np.int64), minlength=max(2, self._num_class()))[-self._num_class():]
+            auc_score(np.zeros_like(P), P, len(ey) - P)
+
+    def _device_metric(self, ey: np.ndarray, dev):
+        if not self._auc():
+            return None
+        from ..ops import gbdt_auc as A
+
+        return A.AucPlan(ey, self._num_class(), dev).score
 
     def _check_spw(self) -> float:
         spw = float(getattr(self, "scale_pos_weight", 1.0))
@@ -1003,6 +1101,10 @@ class XGBClassifier(_Base):
         y = _host(y).reshape(-1)
         self._check_y(y)  # classes from the training labels
         self._fitting = False
+        name, default = getattr(self, "eval_metric", None), "mlogloss" if self._num_class() > 1 else "logloss"
+        if not self._auc() and name not in (None, default):
+            raise ValueError(f"eval_metric={name!r} does not fit {len(self.classes_)} classes: their metric is "
+                             f"{default!r} (or 'auc')")
         return super().fit(X, y, eval_set, early_stopping_rounds, verbose, sample_weight=sample_weight)
 
     def _base(self, y: np.ndarray, w: np.ndarray | None = None) -> float:
@@ -1035,9 +1137,16 @@ class XGBClassifier(_Base):
         return (p - y).astype(np.float32), np.maximum(p * (1 - p), 1e-16).astype(np.float32)
 
     def _metric_name(self) -> str:
+        if self._auc():
+            return "auc"
         return "mlogloss" if self._num_class() > 1 else "logloss"
 
+    def _better(self, score: float, best: float) -> bool:
+        return score > best if self._auc() else score < best
+
     def _metric(self, margin: np.ndarray, y: np.ndarray) -> float:
+        if self._auc():
+            return auc(margin, y, self._nthreads())
         if margin.ndim == 2:  # mlogloss from [K, m] margins
             p = self._softmax(margin)[y.astype(np.int64), np.arange(len(y))]
             return float(-np.mean(np.log(np.clip(p, 1e-15, 1 - 1e-15))))
