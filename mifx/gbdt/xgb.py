@@ -102,7 +102,16 @@ is no host fallback). Host and device differ only in exp (a few double ulps per 
 equal margins, is equal bit for bit, later ones are not promised to be. Everything downstream is unchanged: sampling,
 both growth policies, `predict` (margins), contributions, interactions and importances. The intercept is `base_score`
 or 0.0. The eval metric is "ndcg" or "ndcg@k" (the mean over groups, a group without a relevant row scores 1.0) and is
-MAXIMISED by early stopping. Not implemented: group and row weights (`sample_weight` raises), rank:map,
+MAXIMISED by early stopping. The host function is `ndcg`; with device="gpu" the eval margins are NOT read back:
+mifx/ops/gbdt_ndcg.py scores the groups in csrc/gbdt_ndcg.hip -- one wave per group of up to 64 rows; a longer group, of
+any size, in tiles of 256 rows that COUNT each row's rank against the group's keys streamed through LDS, so the
+gradient path's 4096-row limit does not apply to eval groups -- with the discount table and the per-group IDCG
+(`ndcg_idcg`, computed once per fit) uploaded by the host, and one double per group comes back per round, their mean
+taken by `ndcg_mean`, the host function's own expression. Every term is one IEEE multiply and every sum one IEEE add
+per term in rank order, so the history is the host's bit for bit, for any launch geometry. Limits of the device
+metric: fewer than 2^31 eval rows; counting is O(m^2) per group, so with an eval group of more than
+mifx.ops.gbdt_ndcg.max_group() = 2^20 rows (the largest size measured, profiles/gbdt_ndcg.md) the fit keeps the host
+path, the same scores. Not implemented: group and row weights (`sample_weight` raises), rank:map,
 `lambdarank_normalization` and XGBoost's score-difference normalisation, "mean" pair sampling (XGBoost's default pair
 method is "topk": pass it explicitly to follow it), unbiased LambdaMART.
 
@@ -122,7 +131,8 @@ back per round. Equal integers give equal bits, so the device score equals the h
 An eval set in which some class has no positive or no negative row raises ValueError in `fit`, before the first
 round; the host function refuses margins that are not finite (the device path does not check: a fit's margins are
 finite by construction); the device path takes up to 256 classes. Not implemented: weighted AUC, aucpr, error, map,
-AUC for XGBRanker; the other metrics keep their host path (their margins are read back once per round)."""
+AUC for XGBRanker; beside AUC and the ranker's ndcg / ndcg@k (above) the metrics keep their host path: rmse, mae,
+quantile, logloss and mlogloss have their margins read back once per round."""
 from __future__ import annotations
 
 import ctypes
@@ -280,20 +290,38 @@ def _rank_order(margin: np.ndarray, gid: np.ndarray) -> np.ndarray:
     return np.lexsort((~key, gid))  # (stable: equal keys keep their row order)
 
 
-def ndcg(margin: np.ndarray, y: np.ndarray, gptr: np.ndarray, k: int = 0) -> float:
-    """Mean NDCG over the groups (XGBoost's "ndcg", "ndcg@k" for k >= 1): gains 2^label - 1, discounts
-    1 / log2(rank + 2), @k truncating both DCG and IDCG; a group without a relevant row scores 1.0."""
-    G = len(gptr) - 1
+def _ndcg_terms(y: np.ndarray, gptr: np.ndarray, k: int):
+    """(gid, gain, disc) of ndcg, one entry per row: the row's group, its gain 2^label - 1 and the discount of its
+    POSITION inside the group, 0.0 at and below the cutoff k >= 1."""
     sizes = np.diff(gptr)
-    gid = np.repeat(np.arange(G), sizes)
+    gid = np.repeat(np.arange(len(gptr) - 1), sizes)
     pos = np.arange(len(y)) - np.repeat(gptr[:-1], sizes)
     disc = 1.0 / np.log2(pos + 2.0)
     if k > 0:
         disc = np.where(pos < k, disc, 0.0)
-    gain = np.exp2(y) - 1.0
+    return gid, np.exp2(y) - 1.0, disc
+
+
+def ndcg_idcg(y: np.ndarray, gptr: np.ndarray, k: int = 0, _terms=None) -> np.ndarray:
+    """IDCG float64 [G] of ndcg: per group the gains sorted descending times the discounts, summed in that order and
+    truncated at k. Labels and groups only, so the device metric (mifx.ops.gbdt_ndcg) computes it once per fit."""
+    gid, gain, disc = _terms or _ndcg_terms(y, gptr, k)
+    return np.bincount(gid, gain[np.lexsort((-y, gid))] * disc, minlength=len(gptr) - 1)
+
+
+def ndcg_mean(scores: np.ndarray) -> float:
+    """The metric from the groups' scores: the one expression the host function and the device path share."""
+    return float(np.mean(scores)) if len(scores) else 1.0
+
+
+def ndcg(margin: np.ndarray, y: np.ndarray, gptr: np.ndarray, k: int = 0) -> float:
+    """Mean NDCG over the groups (XGBoost's "ndcg", "ndcg@k" for k >= 1): gains 2^label - 1, discounts
+    1 / log2(rank + 2), @k truncating both DCG and IDCG; a group without a relevant row scores 1.0."""
+    G = len(gptr) - 1
+    gid, gain, disc = terms = _ndcg_terms(y, gptr, k)
     dcg = np.bincount(gid, gain[_rank_order(margin, gid)] * disc, minlength=G)
-    idcg = np.bincount(gid, gain[np.lexsort((-y, gid))] * disc, minlength=G)
-    return float(np.mean(np.where(idcg > 0, dcg / np.where(idcg > 0, idcg, 1.0), 1.0))) if G else 1.0
+    idcg = ndcg_idcg(y, gptr, k, terms)
+    return ndcg_mean(np.where(idcg > 0, dcg / np.where(idcg > 0, idcg, 1.0), 1.0))
 
 
 def _threads() -> int:
@@ -1312,6 +1340,14 @@ class XGBRanker(_Base):
 
     def _metric(self, margin: np.ndarray, y: np.ndarray) -> float:
         return ndcg(margin, y, self._fit_ctx["eval_gptr"], self._metric_k())
+
+    def _device_metric(self, ey: np.ndarray, dev):
+        from ..ops import gbdt_ndcg as N
+
+        gptr = self._fit_ctx["eval_gptr"]
+        if len(gptr) > 1 and int(np.diff(gptr).max()) > N.max_group():
+            return None  # counting is O(m^2): above the measured limit the read-back and the host function are faster
+        return N.NdcgPlan(gptr, ey, self._metric_k(), dev).score
 
     def _better(self, score: float, best: float) -> bool:
         return score > best  # NDCG is maximised
