@@ -73,6 +73,7 @@ struct Node {
   int begin, end, depth, id;
   double g, h;
   std::vector<Hist> hist;  // [features][nbins + 1], the last slot is "missing"
+  double lo, hi;           // the weight interval of monotone_constraints (gbdt_split.h)
 };
 
 template <class F>
@@ -97,6 +98,14 @@ bool rows_ok(const int* rows, long n_rows, long n) {
   if (n_rows < 0 || n_rows > n) return false;
   for (long k = 0; k < n_rows; ++k)
     if (rows[k] < 0 || rows[k] >= n || (k > 0 && rows[k] <= rows[k - 1])) return false;
+  return true;
+}
+
+// the *_mono entries' directions: one of -1, 0, +1 per feature
+bool mono_ok(const int* mono, int f) {
+  if (!mono) return false;
+  for (int j = 0; j < f; ++j)
+    if (mono[j] < -1 || mono[j] > 1) return false;
   return true;
 }
 
@@ -203,12 +212,16 @@ int mifx_gbdt_bin(const double* X, long n, int f, const double* cuts, const int*
 // node_gain / node_cover (nullable, max_nodes doubles each): per node the gain the learner maximised,
 // 0.5 * (score_L + score_R - score_parent) - gamma (0.0 at a leaf), and the node's hessian sum over the rows the tree
 // was grown on. The tree does not depend on whether they are asked for.
-int mifx_gbdt_grow_stats(const uint16_t* bins, long n, int f, const int* nbins, const float* g, const float* h,
-                         int max_depth, double min_child_weight, double lambda, double gamma, double eta, int threads,
-                         int max_nodes, int* feature, int* split_bin, uint8_t* default_left, int* left, int* right,
-                         double* value, int* leaf_of_row, const int* sample, long n_rows, const uint8_t* level_mask,
-                         double* node_gain, double* node_cover) {
+//
+// mono (null = unconstrained, and then every expression is the one it always was): [f] directions in {-1, 0, +1}, the
+// monotone_constraints rule of gbdt_split.h; every node carries its weight interval.
+static int grow_double(const uint16_t* bins, long n, int f, const int* nbins, const float* g, const float* h,
+                       int max_depth, double min_child_weight, double lambda, double gamma, double eta, int threads,
+                       int max_nodes, int* feature, int* split_bin, uint8_t* default_left, int* left, int* right,
+                       double* value, int* leaf_of_row, const int* sample, long n_rows, const uint8_t* level_mask,
+                       double* node_gain, double* node_cover, const int* mono) {
   if (!rows_ok(sample, n_rows, n)) return -2;
+  const MifxGbParams prm{lambda, gamma, min_child_weight, eta};
   std::vector<int> off(f + 1, 0);
   for (int j = 0; j < f; ++j) off[j + 1] = off[j] + nbins[j] + 1;
   const int hsize = off[f];
@@ -237,7 +250,7 @@ int mifx_gbdt_grow_stats(const uint16_t* bins, long n, int f, const int* nbins, 
   auto score = [&](double G, double H) { return G * G / (H + lambda); };
   auto best_split = [&](const Node& nd) {
     std::vector<Split> per(f);
-    const double parent = score(nd.g, nd.h);
+    const double parent = mono ? mifx_gb_mono_parent(nd.g, nd.h, lambda, nd.lo, nd.hi) : score(nd.g, nd.h);
     parallel_for(f, th, [&](int j) {
       const Hist* hj = nd.hist.data() + off[j];
       const int nb = level_mask && !level_mask[(size_t)nd.depth * f + j] ? 1 : nbins[j];
@@ -252,7 +265,9 @@ int mifx_gbdt_grow_stats(const uint16_t* bins, long n, int f, const int* nbins, 
           const double GL = gl + (dir ? gm : 0.0), HL = hl + (dir ? hm : 0.0);
           const double GR = nd.g - GL, HR = nd.h - HL;
           if (HL < min_child_weight || HR < min_child_weight) continue;
-          const double gain = 0.5 * (score(GL, HL) + score(GR, HR) - parent) - gamma;
+          double gain;
+          if (!mono) gain = 0.5 * (score(GL, HL) + score(GR, HR) - parent) - gamma;
+          else if (!mifx_gb_mono_gain(GL, HL, GR, HR, prm, parent, mono[j], nd.lo, nd.hi, &gain)) continue;
           if (gain > bs.gain) {
             bs.gain = gain;
             bs.feature = j;
@@ -282,7 +297,7 @@ int mifx_gbdt_grow_stats(const uint16_t* bins, long n, int f, const int* nbins, 
     if (node_cover) node_cover[count] = 0.0;
     return count++;
   };
-  Node root{0, (int)ns, 0, new_node(), 0.0, 0.0, {}};
+  Node root{0, (int)ns, 0, new_node(), 0.0, 0.0, {}, -INFINITY, INFINITY};
   if (root.id < 0) return -1;
   if (ns == 0) return count;  // nothing sampled: the root alone, value +0.0
   for (long i = 0; i < ns; ++i) {
@@ -293,7 +308,7 @@ int mifx_gbdt_grow_stats(const uint16_t* bins, long n, int f, const int* nbins, 
   std::vector<Node> level;
   level.push_back(std::move(root));
   auto make_leaf = [&](const Node& nd) {
-    value[nd.id] = -eta * nd.g / (nd.h + lambda);
+    value[nd.id] = mono ? eta * mifx_gb_mono_weight(nd.g, nd.h, lambda, nd.lo, nd.hi) : -eta * nd.g / (nd.h + lambda);
     for (int k = nd.begin; k < nd.end; ++k) leaf_of_row[rows[k]] = nd.id;
   };
   while (!level.empty()) {
@@ -322,8 +337,10 @@ int mifx_gbdt_grow_stats(const uint16_t* bins, long n, int f, const int* nbins, 
       default_left[nd.id] = s.default_left;
       left[nd.id] = li;
       right[nd.id] = ri;
-      Node L{nd.begin, mid, nd.depth + 1, li, s.gl, s.hl, {}};
-      Node R{mid, nd.end, nd.depth + 1, ri, s.gr, s.hr, {}};
+      double b[4] = {nd.lo, nd.hi, nd.lo, nd.hi};  // the children's intervals
+      if (mono) mifx_gb_mono_children(s.gl, s.hl, s.gr, s.hr, lambda, mono[s.feature], nd.lo, nd.hi, b);
+      Node L{nd.begin, mid, nd.depth + 1, li, s.gl, s.hl, {}, b[0], b[1]};
+      Node R{mid, nd.end, nd.depth + 1, ri, s.gr, s.hr, {}, b[2], b[3]};
       const bool grow_more = nd.depth + 1 < max_depth;
       if (grow_more) {  // smaller child built, larger = parent - smaller
         Node& small = (L.end - L.begin) <= (R.end - R.begin) ? L : R;
@@ -341,6 +358,28 @@ int mifx_gbdt_grow_stats(const uint16_t* bins, long n, int f, const int* nbins, 
     level = std::move(next);
   }
   return count;
+}
+
+int mifx_gbdt_grow_stats(const uint16_t* bins, long n, int f, const int* nbins, const float* g, const float* h,
+                         int max_depth, double min_child_weight, double lambda, double gamma, double eta, int threads,
+                         int max_nodes, int* feature, int* split_bin, uint8_t* default_left, int* left, int* right,
+                         double* value, int* leaf_of_row, const int* sample, long n_rows, const uint8_t* level_mask,
+                         double* node_gain, double* node_cover) {
+  return grow_double(bins, n, f, nbins, g, h, max_depth, min_child_weight, lambda, gamma, eta, threads, max_nodes,
+                     feature, split_bin, default_left, left, right, value, leaf_of_row, sample, n_rows, level_mask,
+                     node_gain, node_cover, nullptr);
+}
+
+// mifx_gbdt_grow_stats under monotone_constraints: mono [f] in {-1, 0, +1} (-3: anything else, or null)
+int mifx_gbdt_grow_mono(const uint16_t* bins, long n, int f, const int* nbins, const float* g, const float* h,
+                        int max_depth, double min_child_weight, double lambda, double gamma, double eta, int threads,
+                        int max_nodes, int* feature, int* split_bin, uint8_t* default_left, int* left, int* right,
+                        double* value, int* leaf_of_row, const int* sample, long n_rows, const uint8_t* level_mask,
+                        double* node_gain, double* node_cover, const int* mono) {
+  if (!mono_ok(mono, f)) return -3;
+  return grow_double(bins, n, f, nbins, g, h, max_depth, min_child_weight, lambda, gamma, eta, threads, max_nodes,
+                     feature, split_bin, default_left, left, right, value, leaf_of_row, sample, n_rows, level_mask,
+                     node_gain, node_cover, mono);
 }
 
 int mifx_gbdt_grow_ex(const uint16_t* bins, long n, int f, const int* nbins, const float* g, const float* h,
@@ -371,17 +410,19 @@ int mifx_gbdt_quant_exp(double amax, long n) { return mifx_gb_quant_exp(amax, n)
 // sample / level_mask: as in mifx_gbdt_grow_ex; the exponents come from the sampled rows alone (their largest
 // magnitudes and their count).
 // node_gain / node_cover: as in mifx_gbdt_grow_stats; the gain is MifxGbSplit::gain, the cover mifx_gb_dequant(Qh, eh).
-int mifx_gbdt_grow_fixed_stats(const uint16_t* bins, long n, int f, const int* nbins, const float* g, const float* h,
-                               int max_depth, double min_child_weight, double lambda, double gamma, double eta,
-                               int threads, int max_nodes, int* feature, int* split_bin, uint8_t* default_left,
-                               int* left, int* right, double* value, int* leaf_of_row, const int* sample, long n_rows,
-                               const uint8_t* level_mask, double* node_gain, double* node_cover) {
+// mono (null = unconstrained): as in grow_double, the scan is then mifx_gb_scan_mono.
+static int grow_fixed(const uint16_t* bins, long n, int f, const int* nbins, const float* g, const float* h,
+                      int max_depth, double min_child_weight, double lambda, double gamma, double eta, int threads,
+                      int max_nodes, int* feature, int* split_bin, uint8_t* default_left, int* left, int* right,
+                      double* value, int* leaf_of_row, const int* sample, long n_rows, const uint8_t* level_mask,
+                      double* node_gain, double* node_cover, const int* mono) {
   if (!rows_ok(sample, n_rows, n)) return -2;
   struct QNode {
     int begin, end, depth, id;
     long long g, h;
     std::vector<long long> hg, hh;  // [features][nbins + 1], the last slot is "missing"
     std::vector<int> hc;            // rows per slot
+    double lo, hi;                  // the weight interval of monotone_constraints
   };
   const MifxGbParams prm{lambda, gamma, min_child_weight, eta};
   std::vector<int> off(f + 1, 0);
@@ -431,10 +472,16 @@ int mifx_gbdt_grow_fixed_stats(const uint16_t* bins, long n, int f, const int* n
   };
   auto best_split = [&](const QNode& nd) {
     std::vector<MifxGbSplit> per(f);
-    const double parent = mifx_gb_parent_score(nd.g, nd.h, eg, eh, prm);
+    const double parent = mono ? mifx_gb_mono_parent(mifx_gb_dequant(nd.g, eg), mifx_gb_dequant(nd.h, eh), lambda,
+                                                     nd.lo, nd.hi)
+                               : mifx_gb_parent_score(nd.g, nd.h, eg, eh, prm);
     parallel_for(f, th, [&](int j) {
       MifxGbSplit bs = mifx_gb_no_split();
-      if (!level_mask || level_mask[(size_t)nd.depth * f + j])
+      const bool live = !level_mask || level_mask[(size_t)nd.depth * f + j];
+      if (live && mono)
+        mifx_gb_scan_mono(nd.hg.data() + off[j], nd.hh.data() + off[j], nd.hc.data() + off[j], nbins[j], 0, nbins[j],
+                          0, 0, 0, nd.g, nd.h, eg, eh, j, prm, parent, mono[j], nd.lo, nd.hi, &bs);
+      else if (live)
         mifx_gb_scan(nd.hg.data() + off[j], nd.hh.data() + off[j], nd.hc.data() + off[j], nbins[j], 0, nbins[j], 0,
                      0, 0, nd.g, nd.h, eg, eh, j, prm, parent, &bs);
       per[j] = bs;
@@ -457,7 +504,7 @@ int mifx_gbdt_grow_fixed_stats(const uint16_t* bins, long n, int f, const int* n
     if (node_cover) node_cover[count] = 0.0;
     return count++;
   };
-  QNode root{0, (int)ns, 0, new_node(), 0, 0, {}, {}, {}};
+  QNode root{0, (int)ns, 0, new_node(), 0, 0, {}, {}, {}, -INFINITY, INFINITY};
   if (root.id < 0) return -1;
   if (ns == 0) return count;  // nothing sampled: the root alone, value +0.0
   for (long i = 0; i < ns; ++i) {
@@ -474,7 +521,8 @@ int mifx_gbdt_grow_fixed_stats(const uint16_t* bins, long n, int f, const int* n
       if (nd.depth < max_depth && nd.end - nd.begin >= 2) s = best_split(nd);
       if (node_cover) node_cover[nd.id] = mifx_gb_dequant(nd.h, eh);
       if (mifx_gb_is_leaf(s)) {
-        value[nd.id] = mifx_gb_leaf_value(nd.g, nd.h, eg, eh, prm);
+        value[nd.id] = mono ? mifx_gb_mono_leaf_value(nd.g, nd.h, eg, eh, prm, nd.lo, nd.hi)
+                            : mifx_gb_leaf_value(nd.g, nd.h, eg, eh, prm);
         for (int k = nd.begin; k < nd.end; ++k) leaf_of_row[rows[k]] = nd.id;
         continue;
       }
@@ -494,8 +542,10 @@ int mifx_gbdt_grow_fixed_stats(const uint16_t* bins, long n, int f, const int* n
       default_left[nd.id] = (uint8_t)s.default_left;
       left[nd.id] = li;
       right[nd.id] = ri;
-      QNode L{nd.begin, mid, nd.depth + 1, li, s.gl, s.hl, {}, {}, {}};
-      QNode R{mid, nd.end, nd.depth + 1, ri, nd.g - s.gl, nd.h - s.hl, {}, {}, {}};
+      double b[4] = {nd.lo, nd.hi, nd.lo, nd.hi};  // the children's intervals
+      if (mono) mifx_gb_mono_children_q(s, nd.g, nd.h, eg, eh, prm, mono[s.feature], nd.lo, nd.hi, b);
+      QNode L{nd.begin, mid, nd.depth + 1, li, s.gl, s.hl, {}, {}, {}, b[0], b[1]};
+      QNode R{mid, nd.end, nd.depth + 1, ri, nd.g - s.gl, nd.h - s.hl, {}, {}, {}, b[2], b[3]};
       if (nd.depth + 1 < max_depth) {  // smaller child built, larger = parent - smaller (identical in integers)
         QNode& small = (L.end - L.begin) <= (R.end - R.begin) ? L : R;
         QNode& large = &small == &L ? R : L;
@@ -515,6 +565,28 @@ int mifx_gbdt_grow_fixed_stats(const uint16_t* bins, long n, int f, const int* n
     level = std::move(next);
   }
   return count;
+}
+
+int mifx_gbdt_grow_fixed_stats(const uint16_t* bins, long n, int f, const int* nbins, const float* g, const float* h,
+                               int max_depth, double min_child_weight, double lambda, double gamma, double eta,
+                               int threads, int max_nodes, int* feature, int* split_bin, uint8_t* default_left,
+                               int* left, int* right, double* value, int* leaf_of_row, const int* sample, long n_rows,
+                               const uint8_t* level_mask, double* node_gain, double* node_cover) {
+  return grow_fixed(bins, n, f, nbins, g, h, max_depth, min_child_weight, lambda, gamma, eta, threads, max_nodes,
+                    feature, split_bin, default_left, left, right, value, leaf_of_row, sample, n_rows, level_mask,
+                    node_gain, node_cover, nullptr);
+}
+
+// mifx_gbdt_grow_fixed_stats under monotone_constraints: the host twin of mifx_gbdt_gpu_grow_mono
+int mifx_gbdt_grow_fixed_mono(const uint16_t* bins, long n, int f, const int* nbins, const float* g, const float* h,
+                              int max_depth, double min_child_weight, double lambda, double gamma, double eta,
+                              int threads, int max_nodes, int* feature, int* split_bin, uint8_t* default_left,
+                              int* left, int* right, double* value, int* leaf_of_row, const int* sample, long n_rows,
+                              const uint8_t* level_mask, double* node_gain, double* node_cover, const int* mono) {
+  if (!mono_ok(mono, f)) return -3;
+  return grow_fixed(bins, n, f, nbins, g, h, max_depth, min_child_weight, lambda, gamma, eta, threads, max_nodes,
+                    feature, split_bin, default_left, left, right, value, leaf_of_row, sample, n_rows, level_mask,
+                    node_gain, node_cover, mono);
 }
 
 int mifx_gbdt_grow_fixed_ex(const uint16_t* bins, long n, int f, const int* nbins, const float* g, const float* h,
@@ -671,6 +743,7 @@ struct LgArgs {
   long n_rows;
   const uint8_t* feature_mask;  // [f], null = all
   double *node_gain, *node_cover;
+  const int* mono = nullptr;  // [f] monotone_constraints (gbdt_split.h), null = unconstrained
 };
 
 struct LgCand {  // a node's candidate in either arithmetic
@@ -686,6 +759,7 @@ struct DoubleCore {
     LgCand cand;
     double g = 0, h = 0, gl = 0, hl = 0;  // sums; the candidate's left sums
     std::vector<Hist> hist;
+    double lo = -INFINITY, hi = INFINITY;  // the weight interval of monotone_constraints
   };
   const LgArgs& a;
   const std::vector<int>& off;
@@ -721,7 +795,8 @@ struct DoubleCore {
   void search(Node& nd) {
     std::vector<Split> per(a.f);
     auto score = [&](double G, double H) { return G * G / (H + a.lambda); };
-    const double parent = score(nd.g, nd.h);
+    const MifxGbParams prm{a.lambda, a.gamma, a.min_child_weight, a.eta};
+    const double parent = a.mono ? mifx_gb_mono_parent(nd.g, nd.h, a.lambda, nd.lo, nd.hi) : score(nd.g, nd.h);
     parallel_for(a.f, th, [&](int j) {
       const Hist* hj = nd.hist.data() + off[j];
       const int nb = a.feature_mask && !a.feature_mask[j] ? 1 : a.nbins[j];
@@ -736,7 +811,9 @@ struct DoubleCore {
           const double GL = gl + (dir ? gm : 0.0), HL = hl + (dir ? hm : 0.0);
           const double GR = nd.g - GL, HR = nd.h - HL;
           if (HL < a.min_child_weight || HR < a.min_child_weight) continue;
-          const double gain = 0.5 * (score(GL, HL) + score(GR, HR) - parent) - a.gamma;
+          double gain;
+          if (!a.mono) gain = 0.5 * (score(GL, HL) + score(GR, HR) - parent) - a.gamma;
+          else if (!mifx_gb_mono_gain(GL, HL, GR, HR, prm, parent, a.mono[j], nd.lo, nd.hi, &gain)) continue;
           if (gain > bs.gain) {
             bs.gain = gain, bs.feature = j, bs.bin = b, bs.default_left = dir == 1;
             bs.gl = GL, bs.hl = HL, bs.gr = GR, bs.hr = HR;
@@ -758,8 +835,14 @@ struct DoubleCore {
   void children(const Node& p, Node& L, Node& R) const {
     L.g = p.gl, L.h = p.hl;
     R.g = p.g - p.gl, R.h = p.h - p.hl;  // (the depth-wise learner's GR, HR)
+    if (!a.mono) return;
+    double b[4];
+    mifx_gb_mono_children(L.g, L.h, R.g, R.h, a.lambda, a.mono[p.cand.feature], p.lo, p.hi, b);
+    L.lo = b[0], L.hi = b[1], R.lo = b[2], R.hi = b[3];
   }
-  double value(const Node& nd) const { return -a.eta * nd.g / (nd.h + a.lambda); }
+  double value(const Node& nd) const {
+    return a.mono ? a.eta * mifx_gb_mono_weight(nd.g, nd.h, a.lambda, nd.lo, nd.hi) : -a.eta * nd.g / (nd.h + a.lambda);
+  }
   double cover(const Node& nd) const { return nd.h; }
 };
 
@@ -771,6 +854,7 @@ struct FixedCore {
     long long g = 0, h = 0, gl = 0, hl = 0;
     std::vector<long long> hg, hh;
     std::vector<int> hc;
+    double lo = -INFINITY, hi = INFINITY;  // the weight interval of monotone_constraints
   };
   const LgArgs& a;
   const std::vector<int>& off;
@@ -825,10 +909,16 @@ struct FixedCore {
   }
   void search(Node& nd) {
     std::vector<MifxGbSplit> per(a.f);
-    const double parent = mifx_gb_parent_score(nd.g, nd.h, eg, eh, prm);
+    const double parent = a.mono ? mifx_gb_mono_parent(mifx_gb_dequant(nd.g, eg), mifx_gb_dequant(nd.h, eh), a.lambda,
+                                                       nd.lo, nd.hi)
+                                 : mifx_gb_parent_score(nd.g, nd.h, eg, eh, prm);
     parallel_for(a.f, th, [&](int j) {
       MifxGbSplit bs = mifx_gb_no_split();
-      if (!a.feature_mask || a.feature_mask[j])
+      const bool live = !a.feature_mask || a.feature_mask[j];
+      if (live && a.mono)
+        mifx_gb_scan_mono(nd.hg.data() + off[j], nd.hh.data() + off[j], nd.hc.data() + off[j], a.nbins[j], 0,
+                          a.nbins[j], 0, 0, 0, nd.g, nd.h, eg, eh, j, prm, parent, a.mono[j], nd.lo, nd.hi, &bs);
+      else if (live)
         mifx_gb_scan(nd.hg.data() + off[j], nd.hh.data() + off[j], nd.hc.data() + off[j], a.nbins[j], 0, a.nbins[j], 0,
                      0, 0, nd.g, nd.h, eg, eh, j, prm, parent, &bs);
       per[j] = bs;
@@ -846,8 +936,17 @@ struct FixedCore {
   void children(const Node& p, Node& L, Node& R) const {
     L.g = p.gl, L.h = p.hl;
     R.g = p.g - p.gl, R.h = p.h - p.hl;
+    if (!a.mono) return;
+    MifxGbSplit s = mifx_gb_no_split();
+    s.gl = p.gl, s.hl = p.hl;
+    double b[4];
+    mifx_gb_mono_children_q(s, p.g, p.h, eg, eh, prm, a.mono[p.cand.feature], p.lo, p.hi, b);
+    L.lo = b[0], L.hi = b[1], R.lo = b[2], R.hi = b[3];
   }
-  double value(const Node& nd) const { return mifx_gb_leaf_value(nd.g, nd.h, eg, eh, prm); }
+  double value(const Node& nd) const {
+    return a.mono ? mifx_gb_mono_leaf_value(nd.g, nd.h, eg, eh, prm, nd.lo, nd.hi)
+                  : mifx_gb_leaf_value(nd.g, nd.h, eg, eh, prm);
+  }
   double cover(const Node& nd) const { return mifx_gb_dequant(nd.h, eh); }
 };
 
@@ -971,6 +1070,35 @@ int mifx_gbdt_grow_fixed_lossguide_stats(const uint16_t* bins, long n, int f, co
                                           gamma, eta, threads, max_nodes, feature, split_bin, default_left, left,
                                           right, value, leaf_of_row, sample, n_rows, feature_mask, node_gain,
                                           node_cover});
+}
+
+// The two leaf-wise growers under monotone_constraints: the arguments above and mono [f] in {-1, 0, +1} (-3: anything
+// else, or null). mifx_gbdt_grow_fixed_lossguide_mono is the host twin of mifx_gbdt_lg_grow_mono.
+int mifx_gbdt_grow_lossguide_mono(const uint16_t* bins, long n, int f, const int* nbins, const float* g, const float* h,
+                                  int max_depth, int max_leaves, double min_child_weight, double lambda, double gamma,
+                                  double eta, int threads, int max_nodes, int* feature, int* split_bin,
+                                  uint8_t* default_left, int* left, int* right, double* value, int* leaf_of_row,
+                                  const int* sample, long n_rows, const uint8_t* feature_mask, double* node_gain,
+                                  double* node_cover, const int* mono) {
+  if (!mono_ok(mono, f)) return -3;
+  return grow_lossguide<DoubleCore>(LgArgs{bins, n, f, nbins, g, h, max_depth, max_leaves, min_child_weight, lambda,
+                                           gamma, eta, threads, max_nodes, feature, split_bin, default_left, left,
+                                           right, value, leaf_of_row, sample, n_rows, feature_mask, node_gain,
+                                           node_cover, mono});
+}
+
+int mifx_gbdt_grow_fixed_lossguide_mono(const uint16_t* bins, long n, int f, const int* nbins, const float* g,
+                                        const float* h, int max_depth, int max_leaves, double min_child_weight,
+                                        double lambda, double gamma, double eta, int threads, int max_nodes,
+                                        int* feature, int* split_bin, uint8_t* default_left, int* left, int* right,
+                                        double* value, int* leaf_of_row, const int* sample, long n_rows,
+                                        const uint8_t* feature_mask, double* node_gain, double* node_cover,
+                                        const int* mono) {
+  if (!mono_ok(mono, f)) return -3;
+  return grow_lossguide<FixedCore>(LgArgs{bins, n, f, nbins, g, h, max_depth, max_leaves, min_child_weight, lambda,
+                                          gamma, eta, threads, max_nodes, feature, split_bin, default_left, left,
+                                          right, value, leaf_of_row, sample, n_rows, feature_mask, node_gain,
+                                          node_cover, mono});
 }
 
 // Sum of the first n_trees trees' outputs for each row of a row-major [n, f] matrix of raw values. Trees are

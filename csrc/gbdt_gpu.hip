@@ -35,6 +35,12 @@
 //   features  a [max_depth, f] uint8 mask computed by the host: k_split gives no candidate for a masked (level,
 //             feature), k_hist skips a feature tile that is masked entirely.
 //
+// monotone_constraints (mifx_gbdt_gpu_grow_mono; the rule is gbdt_split.h's, the host twin mifx_gbdt_grow_fixed_mono):
+// k_split_mono and k_decide_mono take the places of k_split and k_decide. Every node carries a weight interval in a
+// second pair of level tables (two doubles per node); the search clamps the candidates' weights into it and drops the
+// candidates that order the children against the feature's direction, the decision writes the clamped leaf value and
+// the children's intervals. k_hist and k_partition are the same kernels.
+//
 // Multi-class (multi:softprob, K >= 3 classes): k_grad_softmax computes all K gradient pairs of a round in one launch
 // from class-major [K, n] margins; the round then grows K trees with the grower above, tree k on row k of g, h and
 // the margins. The grower itself knows nothing about classes.
@@ -46,6 +52,7 @@
 #include "gbdt_quant.h"  // the quantise stage (shared with csrc/gbdt_lossguide.hip), kThreads, Carver, add64
 #include "gbdt_sample.h"
 #include "gbdt_split.h"
+#include "gbdt_wave.h"
 
 namespace {
 
@@ -63,6 +70,10 @@ struct Decision {  // per node of the current level
   int *feat, *bin, *dl, *cl;  // feat < 0: leaf
   long long *gl, *hl;
   double* val;
+};
+
+struct Bounds {  // monotone_constraints: the weight interval of every node of one depth (the root's is never read)
+  double *lo, *hi;
 };
 
 struct TreeOut {
@@ -85,11 +96,12 @@ struct Ws {
   long long *hg, *hh;
   int* hc;
   int* nsamp;  // [2] sampled rows: their count (k_amax_s), the compaction cursor (k_quant_s)
+  Bounds bd[2];  // (constrained growth only) beside lv[2]
   size_t bytes;
   Quant quant() const { return Quant{qg, qh, perm[0], amax, exps, nsamp, lv[0].qg, lv[0].qh, lv[0].end}; }
 };
 
-Ws carve(void* base, long n, int f, int max_depth, int hsize) {
+Ws carve(void* base, long n, int f, int max_depth, int hsize, bool mono = false) {
   Carver c{static_cast<char*>(base)};
   const size_t maxl = (size_t)1 << max_depth, maxh = max_depth > 0 ? (size_t)1 << (max_depth - 1) : 1;
   Ws w;
@@ -121,6 +133,10 @@ Ws carve(void* base, long n, int f, int max_depth, int hsize) {
   w.hh = c.take<long long>(maxh * hsize);
   w.hc = c.take<int>(maxh * hsize);
   w.nsamp = c.take<int>(2);
+  for (int i = 0; i < 2; ++i) {  // two doubles per node, after everything the unconstrained grower lays out
+    w.bd[i].lo = mono ? c.take<double>(maxl) : nullptr;
+    w.bd[i].hi = mono ? c.take<double>(maxl) : nullptr;
+  }
   w.bytes = c.used;
   return w;
 }
@@ -375,6 +391,125 @@ __global__ __launch_bounds__(kThreads) void k_decide(Level lv, Level nx, int* lc
   *ncount = base + 2 * s;
 }
 
+// ---- monotone_constraints (the rule is gbdt_split.h's, the wave search gbdt_wave.h's): k_split and k_decide under a
+// constraint vector mono [f]. Every node of a level has its weight interval in bd (level d) / nbd (level d + 1), indexed
+// as lv / nx are; the root's is [-inf, +inf] and is not stored.
+
+// one wave per (node, feature). The node, the feature, the interval and the direction are the wave's: the wave index
+// goes through readfirstlane, so they sit in scalar registers and are loaded once, not per lane.
+__global__ __launch_bounds__(kThreads) void k_split_mono(Level lv, Bounds bd, const int* lcount, int d, int f,
+                                                         const int* nbins, const int* hoff, int hsize,
+                                                         const long long* hg, const long long* hh, const int* hc,
+                                                         const int* exps, MifxGbParams prm, MifxGbSplit* cand,
+                                                         const uint8_t* lmask, const int* mono) {
+  const long wave = (blockIdx.x * (long)kThreads + threadIdx.x) >> 6;
+  const int lane = threadIdx.x & 63;
+  const int cnt = min(lcount[d], 1 << d);
+  const int k = __builtin_amdgcn_readfirstlane((int)(wave / f)), j = __builtin_amdgcn_readfirstlane((int)(wave % f));
+  if (k >= cnt) return;  // uniform over the wave
+  MifxGbSplit bs = mifx_gb_no_split();
+  if (lv.end[k] - lv.begin[k] >= 2 && (!lmask || lmask[j])) {  // a masked feature yields no candidate at this level
+    const int nb = min(nbins[j], kMaxBins);
+    const size_t o = (size_t)k * hsize + hoff[j];
+    const double lo = d ? bd.lo[k] : -INFINITY, hi = d ? bd.hi[k] : INFINITY;
+    bs = wave_search_mono(hg + o, hh + o, hc + o, nb, lane, lv.qg[k], lv.qh[k], exps[0], exps[1], j, prm, mono[j], lo,
+                          hi);
+  }
+  if (lane == 0) cand[(size_t)k * f + j] = bs;
+}
+
+// one workgroup, three phases. (1) per node, in parallel: the features in order, the leaf test, the leaf value from the
+// clamped weight. (2) one thread numbers the children as k_decide does and notes every split's place in the next
+// level. (3) per node, in parallel again: the children's intervals, written where (2) put the children -- the two
+// divisions per split stay off the serial walk.
+__global__ __launch_bounds__(kThreads) void k_decide_mono(Level lv, Level nx, Bounds bd, Bounds nbd, int* lcount, int d,
+                                                          int force_leaf, int f, const MifxGbSplit* cand,
+                                                          const int* exps, MifxGbParams prm, Decision dec, int* cur,
+                                                          TreeOut t, int cap, int* ncount, const int* mono) {
+  __shared__ int s_place[1 << kMaxDepth];  // per node of this level: its children are nx[2 s], nx[2 s + 1]; -1: a leaf
+  const int cnt = min(lcount[d], 1 << d);
+  const int eg = exps[0], eh = exps[1];
+  for (int k = threadIdx.x; k < cnt; k += kThreads) {
+    MifxGbSplit best = mifx_gb_no_split();
+    if (!force_leaf)
+      for (int j = 0; j < f; ++j) {
+        const MifxGbSplit c = cand[(size_t)k * f + j];
+        if (mifx_gb_feature_wins(c, best)) best = c;
+      }
+    const bool leaf = force_leaf || mifx_gb_is_leaf(best);
+    dec.feat[k] = leaf ? -1 : best.feature;
+    dec.bin[k] = best.bin;
+    dec.dl[k] = best.default_left;
+    dec.cl[k] = best.cl;
+    dec.gl[k] = best.gl;
+    dec.hl[k] = best.hl;
+    const double lo = d ? bd.lo[k] : -INFINITY, hi = d ? bd.hi[k] : INFINITY;
+    // every node gets its leaf value (phase 2 may still turn a split into a leaf); the root of an empty sample: +0.0
+    const bool empty = d == 0 && lv.end[k] <= lv.begin[k];
+    dec.val[k] = empty ? 0.0 : mifx_gb_mono_leaf_value(lv.qg[k], lv.qh[k], eg, eh, prm, lo, hi);
+    const int nid = lv.id[k];
+    if (t.gain && nid >= 0 && nid < cap) {
+      t.gain[nid] = leaf ? 0.0 : best.gain;
+      t.cover[nid] = mifx_gb_dequant(lv.qh[k], eh);
+    }
+    cur[2 * k] = 0;
+    cur[2 * k + 1] = 0;
+    s_place[k] = -1;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int base = *ncount;
+    int s = 0;  // splits so far in this level: children are numbered in the order of their parents
+    for (int k = 0; k < cnt; ++k) {
+      const int id = lv.id[k];
+      if (id < 0 || id >= cap) continue;
+      if (dec.feat[k] >= 0 && base + 2 * s + 1 >= cap) {  // cannot happen with cap = 2^(max_depth + 1)
+        dec.feat[k] = -1;
+        if (t.gain) t.gain[id] = 0.0;
+      }
+      const bool leaf = dec.feat[k] < 0;
+      const int li = leaf ? -1 : base + 2 * s, ri = leaf ? -1 : li + 1;
+      t.feature[id] = dec.feat[k];
+      t.split_bin[id] = leaf ? -1 : dec.bin[k];
+      t.default_left[id] = leaf ? 0 : (uint8_t)dec.dl[k];
+      t.left[id] = li;
+      t.right[id] = ri;
+      t.value[id] = leaf ? dec.val[k] : 0.0;
+      if (leaf) continue;
+      const int b = lv.begin[k], e = lv.end[k], mid = min(e, b + max(dec.cl[k], 0));
+      dec.cl[k] = mid - b;
+      nx.id[2 * s] = li;
+      nx.begin[2 * s] = b;
+      nx.end[2 * s] = mid;
+      nx.qg[2 * s] = dec.gl[k];
+      nx.qh[2 * s] = dec.hl[k];
+      nx.id[2 * s + 1] = ri;
+      nx.begin[2 * s + 1] = mid;
+      nx.end[2 * s + 1] = e;
+      nx.qg[2 * s + 1] = lv.qg[k] - dec.gl[k];
+      nx.qh[2 * s + 1] = lv.qh[k] - dec.hl[k];
+      s_place[k] = s++;
+    }
+    lcount[d + 1] = 2 * s;
+    *ncount = base + 2 * s;
+  }
+  __syncthreads();
+  for (int k = threadIdx.x; k < cnt; k += kThreads) {
+    const int s = s_place[k];
+    if (s < 0) continue;  // (a split's children exist only below max_depth: nbd has room for 2 s + 1 < 2^(d + 1))
+    MifxGbSplit c = mifx_gb_no_split();
+    c.gl = dec.gl[k];
+    c.hl = dec.hl[k];
+    double b[4];
+    mifx_gb_mono_children_q(c, lv.qg[k], lv.qh[k], eg, eh, prm, mono[dec.feat[k]], d ? bd.lo[k] : -INFINITY,
+                            d ? bd.hi[k] : INFINITY, b);
+    nbd.lo[2 * s] = b[0];
+    nbd.hi[2 * s] = b[1];
+    nbd.lo[2 * s + 1] = b[2];
+    nbd.hi[2 * s + 1] = b[3];
+  }
+}
+
 __global__ __launch_bounds__(kThreads) void k_partition(Level lv, const int* lcount, int d, Decision dec, int* cur,
                                                         const uint16_t* bins, const int* nbins, long n, int f,
                                                         const int* perm_in, int* perm_out, int* leaf_of_row,
@@ -457,6 +592,15 @@ __global__ void k_apply(const uint16_t* bins, long m, int f, const int* nbins, T
   margin[i] += t.value[k];
 }
 
+// the grower behind every mifx_gbdt_gpu_grow* entry; mono (device, null = unconstrained): [f] directions, the workspace
+// then has the constrained layout
+int grow_tree(const uint16_t* bins, long n, int f, const int* nbins, const int* hoff, int hsize, const float* g,
+              const float* h, int max_depth, double min_child_weight, double lambda, double gamma, double eta, void* ws,
+              long long ws_bytes, int* feature, int* split_bin, uint8_t* default_left, int* left, int* right,
+              double* value, int* node_count, int* leaf_of_row, double* margin, int rows_per_wg, int feat_tile,
+              unsigned long long seed, unsigned long long round, unsigned long long thr, const uint8_t* level_mask,
+              int margin_route, double* node_gain, double* node_cover, const int* mono, hipStream_t stream);
+
 }  // namespace
 
 extern "C" {
@@ -471,6 +615,12 @@ long long mifx_gbdt_gpu_ws_bytes(long n, int f, int max_depth, int hsize) {
       hsize > f * kSlots)
     return -1;
   return (long long)carve(nullptr, n, f, max_depth, hsize).bytes;
+}
+
+// the same for mifx_gbdt_gpu_grow_mono: two more doubles per node of the two level tables
+long long mifx_gbdt_gpu_ws_bytes_mono(long n, int f, int max_depth, int hsize) {
+  if (mifx_gbdt_gpu_ws_bytes(n, f, max_depth, hsize) < 0) return -1;
+  return (long long)carve(nullptr, n, f, max_depth, hsize, true).bytes;
 }
 
 int mifx_gbdt_gpu_grad(int objective, const double* margin, const double* y, long n, float* g, float* h,
@@ -516,13 +666,46 @@ int mifx_gbdt_gpu_grow_stats(const uint16_t* bins, long n, int f, const int* nbi
                              int* leaf_of_row, double* margin, int rows_per_wg, int feat_tile, unsigned long long seed,
                              unsigned long long round, unsigned long long thr, const uint8_t* level_mask,
                              int margin_route, double* node_gain, double* node_cover, hipStream_t stream) {
+  return grow_tree(bins, n, f, nbins, hoff, hsize, g, h, max_depth, min_child_weight, lambda, gamma, eta, ws, ws_bytes,
+                   feature, split_bin, default_left, left, right, value, node_count, leaf_of_row, margin, rows_per_wg,
+                   feat_tile, seed, round, thr, level_mask, margin_route, node_gain, node_cover, nullptr, stream);
+}
+
+// mifx_gbdt_gpu_grow_stats under monotone_constraints: mono (device) [f] ints in {-1, 0, +1}, the rule of gbdt_split.h;
+// ws holds mifx_gbdt_gpu_ws_bytes_mono bytes. The host twin is mifx_gbdt_grow_fixed_mono. The split search and the
+// decision are k_split_mono / k_decide_mono; the histogram and partition kernels are the unconstrained grower's.
+int mifx_gbdt_gpu_grow_mono(const uint16_t* bins, long n, int f, const int* nbins, const int* hoff, int hsize,
+                            const float* g, const float* h, int max_depth, double min_child_weight, double lambda,
+                            double gamma, double eta, void* ws, long long ws_bytes, int* feature, int* split_bin,
+                            uint8_t* default_left, int* left, int* right, double* value, int* node_count,
+                            int* leaf_of_row, double* margin, int rows_per_wg, int feat_tile, unsigned long long seed,
+                            unsigned long long round, unsigned long long thr, const uint8_t* level_mask,
+                            int margin_route, double* node_gain, double* node_cover, const int* mono,
+                            hipStream_t stream) {
+  if (!mono) return -1;
+  return grow_tree(bins, n, f, nbins, hoff, hsize, g, h, max_depth, min_child_weight, lambda, gamma, eta, ws, ws_bytes,
+                   feature, split_bin, default_left, left, right, value, node_count, leaf_of_row, margin, rows_per_wg,
+                   feat_tile, seed, round, thr, level_mask, margin_route, node_gain, node_cover, mono, stream);
+}
+
+}  // extern "C"
+
+namespace {
+
+int grow_tree(const uint16_t* bins, long n, int f, const int* nbins, const int* hoff, int hsize, const float* g,
+              const float* h, int max_depth, double min_child_weight, double lambda, double gamma, double eta, void* ws,
+              long long ws_bytes, int* feature, int* split_bin, uint8_t* default_left, int* left, int* right,
+              double* value, int* node_count, int* leaf_of_row, double* margin, int rows_per_wg, int feat_tile,
+              unsigned long long seed, unsigned long long round, unsigned long long thr, const uint8_t* level_mask,
+              int margin_route, double* node_gain, double* node_cover, const int* mono, hipStream_t stream) {
   if ((node_gain == nullptr) != (node_cover == nullptr)) return -1;
-  const long long need = mifx_gbdt_gpu_ws_bytes(n, f, max_depth, hsize);
+  const long long need = mono ? mifx_gbdt_gpu_ws_bytes_mono(n, f, max_depth, hsize)
+                              : mifx_gbdt_gpu_ws_bytes(n, f, max_depth, hsize);
   if (need < 0 || ws_bytes < need || rows_per_wg < 1 || feat_tile < 1 || feat_tile > kMaxFeatTile) return -1;
   if (margin_route < 0 || margin_route > 1) return -1;
   const bool sampled = thr < MIFX_GS_KEEP_ALL;
   double* part_margin = sampled && margin_route == 1 ? nullptr : margin;
-  Ws w = carve(ws, n, f, max_depth, hsize);
+  Ws w = carve(ws, n, f, max_depth, hsize, mono != nullptr);
   const MifxGbParams prm{lambda, gamma, min_child_weight, eta};
   const TreeOut t{feature, split_bin, default_left, left, right, value, node_gain, node_cover};
   const int cap = 1 << (max_depth + 1);
@@ -543,11 +726,20 @@ int mifx_gbdt_gpu_grow_stats(const uint16_t* bins, long n, int f, const int* nbi
       k_hist<<<hist_grid, kThreads, lds, stream>>>(lv, w.lcount, d, bins, w.perm[d & 1], w.qg, w.qh, n, f, nbins, hoff,
                                                    hsize, w.hg, w.hh, w.hc, rows_per_wg, feat_tile, lmask);
       const long waves = ((long)1 << d) * f;
-      k_split<<<(unsigned)((waves + 3) / 4), kThreads, 0, stream>>>(lv, w.lcount, d, f, nbins, hoff, hsize, w.hg, w.hh,
-                                                                    w.hc, w.exps, prm, w.cand, lmask);
+      if (mono)
+        k_split_mono<<<(unsigned)((waves + 3) / 4), kThreads, 0, stream>>>(lv, w.bd[d & 1], w.lcount, d, f, nbins, hoff,
+                                                                           hsize, w.hg, w.hh, w.hc, w.exps, prm, w.cand,
+                                                                           lmask, mono);
+      else
+        k_split<<<(unsigned)((waves + 3) / 4), kThreads, 0, stream>>>(lv, w.lcount, d, f, nbins, hoff, hsize, w.hg,
+                                                                      w.hh, w.hc, w.exps, prm, w.cand, lmask);
     }
-    k_decide<<<1, kThreads, 0, stream>>>(lv, nx, w.lcount, d, d == max_depth, f, w.cand, w.exps, prm, w.dec, w.cur, t,
-                                         cap, w.ncount);
+    if (mono)
+      k_decide_mono<<<1, kThreads, 0, stream>>>(lv, nx, w.bd[d & 1], w.bd[(d + 1) & 1], w.lcount, d, d == max_depth, f,
+                                                w.cand, w.exps, prm, w.dec, w.cur, t, cap, w.ncount, mono);
+    else
+      k_decide<<<1, kThreads, 0, stream>>>(lv, nx, w.lcount, d, d == max_depth, f, w.cand, w.exps, prm, w.dec, w.cur,
+                                           t, cap, w.ncount);
     k_partition<<<row_blocks, kThreads, 0, stream>>>(lv, w.lcount, d, w.dec, w.cur, bins, nbins, n, f, w.perm[d & 1],
                                                      w.perm[(d + 1) & 1], leaf_of_row, part_margin);
     const hipError_t e = hipGetLastError();
@@ -561,6 +753,10 @@ int mifx_gbdt_gpu_grow_stats(const uint16_t* bins, long n, int f, const int* nbi
   }
   return (int)hipMemcpyAsync(node_count, w.ncount, sizeof(int), hipMemcpyDeviceToDevice, stream);
 }
+
+}  // namespace
+
+extern "C" {
 
 int mifx_gbdt_gpu_grow_ex(const uint16_t* bins, long n, int f, const int* nbins, const int* hoff, int hsize,
                           const float* g, const float* h, int max_depth, double min_child_weight, double lambda,

@@ -37,6 +37,10 @@
 // same k_hist and k_split with "smaller child" = root. k_finish gives every row of a leaf its leaf_of_row and
 // margin += value; rows outside the sample are walked through the finished tree (k_walk), at most the tree's real
 // depth steps. colsample_bytree reaches k_hist / k_split as one [f] uint8 mask per tree.
+//
+// monotone_constraints (mifx_gbdt_lg_grow_mono; the rule is gbdt_split.h's, the host twin
+// mifx_gbdt_grow_fixed_lossguide_mono): the node table holds every node's weight interval (two doubles more per node);
+// k_root and k_pick write it and clamp the leaf entries, k_split_mono takes k_split's place.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -45,6 +49,7 @@
 #include "gbdt_quant.h"
 #include "gbdt_sample.h"
 #include "gbdt_split.h"
+#include "gbdt_wave.h"
 
 namespace {
 
@@ -70,6 +75,7 @@ struct Nodes {
   int *begin, *end, *side, *depth, *slot, *state;
   long long *qg, *qh;
   MifxGbSplit* cand;
+  double *lo, *hi;  // monotone_constraints: the node's weight interval (null in an unconstrained tree)
 };
 
 struct Ws {
@@ -85,7 +91,7 @@ struct Ws {
   Quant quant() const { return Quant{qg, qh, perm[0], amax, exps, nsamp, nd.qg, nd.qh, nd.end}; }
 };
 
-Ws carve(void* base, long n, int f, int max_leaves, int hsize) {
+Ws carve(void* base, long n, int f, int max_leaves, int hsize, bool mono = false) {
   Carver c{static_cast<char*>(base)};
   const size_t cap = 2 * (size_t)max_leaves - 1, pool = (size_t)max_leaves * hsize;
   Ws w;
@@ -110,6 +116,8 @@ Ws carve(void* base, long n, int f, int max_leaves, int hsize) {
   w.hg = c.take<long long>(pool);
   w.hh = c.take<long long>(pool);
   w.hc = c.take<int>(pool);
+  w.nd.lo = mono ? c.take<double>(cap) : nullptr;  // after everything the unconstrained grower lays out
+  w.nd.hi = mono ? c.take<double>(cap) : nullptr;
   w.bytes = c.used;
   return w;
 }
@@ -128,7 +136,11 @@ __device__ void leaf_entry(const Ws& w, const TreeOut& t, int k, const MifxGbPar
   t.default_left[k] = 0;
   t.left[k] = -1;
   t.right[k] = -1;
-  t.value[k] = empty ? 0.0 : mifx_gb_leaf_value(w.nd.qg[k], w.nd.qh[k], w.exps[0], w.exps[1], prm);
+  if (w.nd.lo)  // constrained: eta times the weight clamped into the node's interval
+    t.value[k] = empty ? 0.0 : mifx_gb_mono_leaf_value(w.nd.qg[k], w.nd.qh[k], w.exps[0], w.exps[1], prm, w.nd.lo[k],
+                                                       w.nd.hi[k]);
+  else
+    t.value[k] = empty ? 0.0 : mifx_gb_leaf_value(w.nd.qg[k], w.nd.qh[k], w.exps[0], w.exps[1], prm);
   if (t.gain) {
     t.gain[k] = 0.0;
     t.cover[k] = mifx_gb_dequant(w.nd.qh[k], w.exps[1]);
@@ -154,6 +166,7 @@ __global__ __launch_bounds__(kThreads) void k_root(Ws w, TreeOut t, MifxGbParams
     w.nd.slot[0] = 0;
     w.nd.state[0] = grow ? PENDING : CLOSED;
     w.nd.cand[0] = mifx_gb_no_split();
+    if (w.nd.lo) w.nd.lo[0] = -INFINITY, w.nd.hi[0] = INFINITY;
     leaf_entry(w, t, 0, prm);
     w.ctrl[C_DONE] = !grow;
     w.ctrl[C_NODES] = 1;
@@ -166,8 +179,9 @@ __global__ __launch_bounds__(kThreads) void k_root(Ws w, TreeOut t, MifxGbParams
   if (grow) zero_slot(w, 0, hsize);
 }
 
+// mono (nullable): the constraint vector; the children then inherit their intervals here, before their leaf entries
 __global__ __launch_bounds__(kThreads) void k_pick(Ws w, TreeOut t, MifxGbParams prm, int max_depth, int max_leaves,
-                                                   int hsize) {
+                                                   int hsize, const int* mono) {
   __shared__ double s_gain[kWaves];
   __shared__ int s_id[kWaves], s_fresh;
   int* ctrl = w.ctrl;
@@ -209,8 +223,13 @@ __global__ __launch_bounds__(kThreads) void k_pick(Ws w, TreeOut t, MifxGbParams
       t.right[p] = ri;
       t.value[p] = 0.0;
       if (t.gain) t.gain[p] = c.gain;
+      double bd[4];
+      if (mono)
+        mifx_gb_mono_children_q(c, w.nd.qg[p], w.nd.qh[p], w.exps[0], w.exps[1], prm, mono[c.feature], w.nd.lo[p],
+                                w.nd.hi[p], bd);
       for (int s = 0; s < 2; ++s) {
         const int k = li + s;
+        if (mono) w.nd.lo[k] = bd[2 * s], w.nd.hi[k] = bd[2 * s + 1];
         w.nd.begin[k] = s ? mid : b;
         w.nd.end[k] = s ? e : mid;
         w.nd.side[k] = 1 - w.nd.side[p];
@@ -414,6 +433,61 @@ __global__ __launch_bounds__(kSplitWaves * 64) void k_split(Ws w, int f, const i
   w.nd.state[k] = mifx_gb_is_leaf(best) ? CLOSED : OPEN;
 }
 
+// k_split under monotone_constraints (the rule is gbdt_split.h's, the wave search gbdt_wave.h's): the same two
+// workgroups, staging and in-place subtraction; the child's interval comes from the node table (k_pick wrote it), once
+// per workgroup, and every wave searches its feature with the feature's direction.
+__global__ __launch_bounds__(kSplitWaves * 64) void k_split_mono(Ws w, int f, const int* nbins, const int* hoff,
+                                                                 int hsize, MifxGbParams prm, const uint8_t* mask,
+                                                                 const int* mono) {
+  __shared__ long long s_g[kSplitWaves][kSlots], s_h[kSplitWaves][kSlots];
+  __shared__ int s_c[kSplitWaves][kSlots];
+  const int small = w.ctrl[C_SMALL], k = blockIdx.x == 0 ? small : w.ctrl[C_LARGE];
+  if (k < 0) return;  // uniform over the workgroup
+  const bool subtract = blockIdx.x == 1;
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const bool scan = w.nd.end[k] - w.nd.begin[k] >= 2;  // fewer rows: a leaf whatever its histogram
+  const int eg = w.exps[0], eh = w.exps[1];
+  const long long Qg = w.nd.qg[k], Qh = w.nd.qh[k];
+  const double lo = w.nd.lo[k], hi = w.nd.hi[k];
+  const size_t mine = (size_t)w.nd.slot[k] * hsize, other = (size_t)w.nd.slot[small] * hsize;
+  MifxGbSplit* fc = w.fcand + (size_t)blockIdx.x * f;
+  for (int jb = 0; jb < f; jb += kSplitWaves) {  // every thread takes every trip: the barriers are uniform
+    const int j = jb + wave;
+    const bool live = scan && j < f && (!mask || mask[j]);  // uniform over the wave
+    const int nb = live ? min(nbins[j], kMaxBins) : 0;
+    if (live)
+      for (int s = lane; s <= nb; s += 64) {
+        const size_t o = mine + hoff[j] + s;
+        long long a = w.hg[o], b = w.hh[o];
+        int c = w.hc[o];
+        if (subtract) {  // this slot still holds the parent: parent - smaller, kept for the child's own descendants
+          const size_t q = other + hoff[j] + s;
+          w.hg[o] = a -= w.hg[q];
+          w.hh[o] = b -= w.hh[q];
+          w.hc[o] = c -= w.hc[q];
+        }
+        s_g[wave][s] = a;
+        s_h[wave][s] = b;
+        s_c[wave][s] = c;
+      }
+    __syncthreads();
+    if (live) {
+      const MifxGbSplit bs = wave_search_mono(s_g[wave], s_h[wave], s_c[wave], nb, lane, Qg, Qh, eg, eh, j, prm, mono[j],
+                                              lo, hi);
+      if (lane == 0) fc[j] = bs;
+    } else if (j < f && lane == 0) {
+      fc[j] = mifx_gb_no_split();
+    }
+    __syncthreads();  // the staging rows are rewritten by the next trip; fc is complete after the last one
+  }
+  if (threadIdx.x != 0) return;
+  MifxGbSplit best = mifx_gb_no_split();
+  for (int j = 0; j < f; ++j)
+    if (mifx_gb_feature_wins(fc[j], best)) best = fc[j];
+  w.nd.cand[k] = best;
+  w.nd.state[k] = mifx_gb_is_leaf(best) ? CLOSED : OPEN;
+}
+
 // every row of a leaf: leaf_of_row and margin += value. y strides over the nodes, x over a node's rows.
 __global__ __launch_bounds__(kThreads) void k_finish(Ws w, TreeOut t, long n, int* leaf_of_row, double* margin,
                                                      int* node_count) {
@@ -459,6 +533,15 @@ __global__ void k_walk(const uint16_t* bins, long m, int f, const int* nbins, Tr
   margin[i] += t.value[k];
 }
 
+// the grower behind mifx_gbdt_lg_grow and mifx_gbdt_lg_grow_mono; mono (device, null = unconstrained): [f] directions,
+// the workspace then has the constrained layout
+int grow_tree(const uint16_t* bins, long n, int f, const int* nbins, const int* hoff, int hsize, const float* g,
+              const float* h, int max_depth, int max_leaves, double min_child_weight, double lambda, double gamma,
+              double eta, void* ws, long long ws_bytes, int* feature, int* split_bin, uint8_t* default_left, int* left,
+              int* right, double* value, int* node_count, int* leaf_of_row, double* margin, int rows_per_wg,
+              int feat_tile, int grid_x, unsigned long long seed, unsigned long long round, unsigned long long thr,
+              const uint8_t* feature_mask, double* node_gain, double* node_cover, const int* mono, hipStream_t stream);
+
 }  // namespace
 
 extern "C" {
@@ -481,6 +564,12 @@ long long mifx_gbdt_lg_ws_bytes(long n, int f, int max_leaves, int hsize) {
   return (long long)carve(nullptr, n, f, max_leaves, hsize).bytes;
 }
 
+// the same for mifx_gbdt_lg_grow_mono: (2 max_leaves - 1) * 16 more, the node table's two doubles per node
+long long mifx_gbdt_lg_ws_bytes_mono(long n, int f, int max_leaves, int hsize) {
+  if (mifx_gbdt_lg_ws_bytes(n, f, max_leaves, hsize) < 0) return -1;
+  return (long long)carve(nullptr, n, f, max_leaves, hsize, true).bytes;
+}
+
 // Grow one tree leaf-wise. bins: row-major [n, f]; nbins [f] and hoff [f] (exclusive prefix of nbins + 1) on the
 // device, the tree arrays (2 * max_leaves - 1 entries each) too. node_count [2] (device) receives the node count and
 // the tree's depth. leaf_of_row [n]; margin (nullable) [n] receives margin[row] += the tree's output, for every row.
@@ -498,11 +587,45 @@ int mifx_gbdt_lg_grow(const uint16_t* bins, long n, int f, const int* nbins, con
                       double* margin, int rows_per_wg, int feat_tile, int grid_x, unsigned long long seed,
                       unsigned long long round, unsigned long long thr, const uint8_t* feature_mask, double* node_gain,
                       double* node_cover, hipStream_t stream) {
+  return grow_tree(bins, n, f, nbins, hoff, hsize, g, h, max_depth, max_leaves, min_child_weight, lambda, gamma, eta, ws,
+                   ws_bytes, feature, split_bin, default_left, left, right, value, node_count, leaf_of_row, margin,
+                   rows_per_wg, feat_tile, grid_x, seed, round, thr, feature_mask, node_gain, node_cover, nullptr,
+                   stream);
+}
+
+// mifx_gbdt_lg_grow under monotone_constraints: mono (device) [f] ints in {-1, 0, +1}, the rule of gbdt_split.h; ws
+// holds mifx_gbdt_lg_ws_bytes_mono bytes. The host twin is mifx_gbdt_grow_fixed_lossguide_mono. Every node's interval
+// is in the node table: k_root and k_pick write it and clamp the leaf entries, k_split_mono searches under it.
+int mifx_gbdt_lg_grow_mono(const uint16_t* bins, long n, int f, const int* nbins, const int* hoff, int hsize,
+                           const float* g, const float* h, int max_depth, int max_leaves, double min_child_weight,
+                           double lambda, double gamma, double eta, void* ws, long long ws_bytes, int* feature,
+                           int* split_bin, uint8_t* default_left, int* left, int* right, double* value, int* node_count,
+                           int* leaf_of_row, double* margin, int rows_per_wg, int feat_tile, int grid_x,
+                           unsigned long long seed, unsigned long long round, unsigned long long thr,
+                           const uint8_t* feature_mask, double* node_gain, double* node_cover, const int* mono,
+                           hipStream_t stream) {
+  if (!mono) return -1;
+  return grow_tree(bins, n, f, nbins, hoff, hsize, g, h, max_depth, max_leaves, min_child_weight, lambda, gamma, eta, ws,
+                   ws_bytes, feature, split_bin, default_left, left, right, value, node_count, leaf_of_row, margin,
+                   rows_per_wg, feat_tile, grid_x, seed, round, thr, feature_mask, node_gain, node_cover, mono, stream);
+}
+
+}  // extern "C"
+
+namespace {
+
+int grow_tree(const uint16_t* bins, long n, int f, const int* nbins, const int* hoff, int hsize, const float* g,
+              const float* h, int max_depth, int max_leaves, double min_child_weight, double lambda, double gamma,
+              double eta, void* ws, long long ws_bytes, int* feature, int* split_bin, uint8_t* default_left, int* left,
+              int* right, double* value, int* node_count, int* leaf_of_row, double* margin, int rows_per_wg,
+              int feat_tile, int grid_x, unsigned long long seed, unsigned long long round, unsigned long long thr,
+              const uint8_t* feature_mask, double* node_gain, double* node_cover, const int* mono, hipStream_t stream) {
   if ((node_gain == nullptr) != (node_cover == nullptr)) return -1;
-  const long long need = mifx_gbdt_lg_ws_bytes(n, f, max_leaves, hsize);
+  const long long need = mono ? mifx_gbdt_lg_ws_bytes_mono(n, f, max_leaves, hsize)
+                              : mifx_gbdt_lg_ws_bytes(n, f, max_leaves, hsize);
   if (need < 0 || ws_bytes < need || max_depth < 0 || max_depth > kMaxDepth) return -1;
   if (rows_per_wg < 1 || feat_tile < 1 || feat_tile > kMaxFeatTile || grid_x < 1 || grid_x > 65535) return -1;
-  Ws w = carve(ws, n, f, max_leaves, hsize);
+  Ws w = carve(ws, n, f, max_leaves, hsize, mono != nullptr);
   const MifxGbParams prm{lambda, gamma, min_child_weight, eta};
   const TreeOut t{feature, split_bin, default_left, left, right, value, node_gain, node_cover};
   const dim3 hist_grid((unsigned)std::min<long>((n + rows_per_wg - 1) / rows_per_wg, grid_x),
@@ -514,13 +637,16 @@ int mifx_gbdt_lg_grow(const uint16_t* bins, long n, int f, const int* nbins, con
   k_root<<<1, kThreads, 0, stream>>>(w, t, prm, max_leaves, hsize);
   for (int x = 0; x < max_leaves; ++x) {  // x = 0: the root's candidate; then max_leaves - 1 expansions
     if (x > 0) {
-      k_pick<<<1, kThreads, 0, stream>>>(w, t, prm, max_depth, max_leaves, hsize);
+      k_pick<<<1, kThreads, 0, stream>>>(w, t, prm, max_depth, max_leaves, hsize, mono);
       k_part<<<part_grid, kThreads, 0, stream>>>(w, t, bins, nbins, n, f);
     }
     if (x + 1 < max_leaves) {  // the last expansion's children are never split
       k_hist<<<hist_grid, kThreads, lds, stream>>>(w, bins, n, f, nbins, hoff, hsize, rows_per_wg, feat_tile,
                                                    feature_mask);
-      k_split<<<2, kSplitWaves * 64, 0, stream>>>(w, f, nbins, hoff, hsize, prm, feature_mask);
+      if (mono)
+        k_split_mono<<<2, kSplitWaves * 64, 0, stream>>>(w, f, nbins, hoff, hsize, prm, feature_mask, mono);
+      else
+        k_split<<<2, kSplitWaves * 64, 0, stream>>>(w, f, nbins, hoff, hsize, prm, feature_mask);
     }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
@@ -531,6 +657,10 @@ int mifx_gbdt_lg_grow(const uint16_t* bins, long n, int f, const int* nbins, con
                                                                                leaf_of_row);
   return (int)hipGetLastError();
 }
+
+}  // namespace
+
+extern "C" {
 
 // margin[i] += tree(row i) for a binned row-major [m, f] matrix (the eval set's margins); node_count: the [2] that
 // mifx_gbdt_lg_grow wrote for this tree

@@ -126,3 +126,91 @@ MIFX_GB_HD bool mifx_gb_feature_wins(const MifxGbSplit& c, const MifxGbSplit& be
 }
 
 MIFX_GB_HD bool mifx_gb_is_leaf(const MifxGbSplit& s) { return s.feature < 0 || s.gain <= 1e-6; }
+
+// ---- monotone_constraints: the rule of the constrained growers, entered only when some feature's direction c_j is
+// not 0 (so nothing here needs to equal the expressions above, and nothing above changes). Every node carries an
+// interval [lo, hi] of weights (before eta), the root [-inf, +inf]:
+//  * weight w(G, H) = -G / (H + lambda) clamped into the node's interval; leaf value eta * w;
+//  * score with a weight: -(2 G w + (H + lambda) w w), for the parent and for both children;
+//  * a candidate on a feature with c = +1 is dropped when wl > wr, with c = -1 when wl < wr;
+//  * after a split on a feature with c != 0 and mid = 0.5 (wl + wr): c = +1 gives the left child [lo, mid] and the right
+//    [mid, hi], c = -1 the other way round; c = 0 hands [lo, hi] to both.
+// Candidate order, the strict >, the 1e-12 feature rule and the leaf test are the ones above. All of it takes doubles,
+// so the double learner of gbdt.cpp calls the same functions as the fixed-point ones.
+MIFX_GB_HD double mifx_gb_mono_weight(double G, double H, double lambda, double lo, double hi) {
+  const double w = -G / (H + lambda);
+  return w < lo ? lo : (w > hi ? hi : w);
+}
+
+MIFX_GB_HD double mifx_gb_mono_score(double G, double H, double lambda, double w) {
+  return -(2.0 * G * w + (H + lambda) * w * w);
+}
+
+MIFX_GB_HD double mifx_gb_mono_parent(double G, double H, double lambda, double lo, double hi) {
+  return mifx_gb_mono_score(G, H, lambda, mifx_gb_mono_weight(G, H, lambda, lo, hi));
+}
+
+// one candidate: false when the direction drops it, else its gain
+MIFX_GB_HD bool mifx_gb_mono_gain(double GL, double HL, double GR, double HR, const MifxGbParams& p, double parent, int c,
+                                  double lo, double hi, double* gain) {
+  const double wl = mifx_gb_mono_weight(GL, HL, p.lambda, lo, hi), wr = mifx_gb_mono_weight(GR, HR, p.lambda, lo, hi);
+  if ((c > 0 && wl > wr) || (c < 0 && wl < wr)) return false;
+  *gain = 0.5 * (mifx_gb_mono_score(GL, HL, p.lambda, wl) + mifx_gb_mono_score(GR, HR, p.lambda, wr) - parent) - p.gamma;
+  return true;
+}
+
+// the children's intervals after the chosen split: b = {left lo, left hi, right lo, right hi}
+MIFX_GB_HD void mifx_gb_mono_children(double GL, double HL, double GR, double HR, double lambda, int c, double lo,
+                                      double hi, double* b) {
+  b[0] = b[2] = lo;
+  b[1] = b[3] = hi;
+  if (c == 0) return;
+  const double wl = mifx_gb_mono_weight(GL, HL, lambda, lo, hi), wr = mifx_gb_mono_weight(GR, HR, lambda, lo, hi);
+  const double mid = 0.5 * (wl + wr);
+  if (c > 0) b[1] = b[2] = mid;
+  else b[0] = b[3] = mid;
+}
+
+// the fixed-point forms: quantised sums in, the functions above on their doubles
+MIFX_GB_HD double mifx_gb_mono_leaf_value(long long Qg, long long Qh, int eg, int eh, const MifxGbParams& p, double lo,
+                                          double hi) {
+  return p.eta * mifx_gb_mono_weight(mifx_gb_dequant(Qg, eg), mifx_gb_dequant(Qh, eh), p.lambda, lo, hi);
+}
+
+MIFX_GB_HD void mifx_gb_mono_children_q(const MifxGbSplit& s, long long Qg, long long Qh, int eg, int eh,
+                                        const MifxGbParams& p, int c, double lo, double hi, double* b) {
+  mifx_gb_mono_children(mifx_gb_dequant(s.gl, eg), mifx_gb_dequant(s.hl, eh), mifx_gb_dequant(Qg - s.gl, eg),
+                        mifx_gb_dequant(Qh - s.hl, eh), p.lambda, c, lo, hi, b);
+}
+
+// mifx_gb_scan under a constraint: the same candidates in the same order; parent is mifx_gb_mono_parent of the node
+MIFX_GB_HD void mifx_gb_scan_mono(const long long* hg, const long long* hh, const int* hc, int nb, int b0, int b1,
+                                  long long pg, long long ph, int pc, long long Qg, long long Qh, int eg, int eh,
+                                  int feature, const MifxGbParams& p, double parent, int c, double lo, double hi,
+                                  MifxGbSplit* bs) {
+  const long long mg = hg[nb], mh = hh[nb];
+  const int mc = hc[nb];
+  for (int b = b0; b < b1 && b + 1 < nb; ++b) {
+    pg += hg[b];
+    ph += hh[b];
+    pc += hc[b];
+    for (int dir = 0; dir < 2; ++dir) {  // dir 0: missing right, 1: missing left
+      if (dir == 1 && mc == 0) break;
+      const long long qgl = pg + (dir ? mg : 0), qhl = ph + (dir ? mh : 0);
+      const double GL = mifx_gb_dequant(qgl, eg), HL = mifx_gb_dequant(qhl, eh);
+      const double GR = mifx_gb_dequant(Qg - qgl, eg), HR = mifx_gb_dequant(Qh - qhl, eh);
+      if (HL < p.min_child_weight || HR < p.min_child_weight) continue;
+      double gain;
+      if (!mifx_gb_mono_gain(GL, HL, GR, HR, p, parent, c, lo, hi, &gain)) continue;
+      if (gain > bs->gain) {
+        bs->gain = gain;
+        bs->feature = feature;
+        bs->bin = b;
+        bs->default_left = dir;
+        bs->gl = qgl;
+        bs->hl = qhl;
+        bs->cl = pc + (dir ? mc : 0);
+      }
+    }
+  }
+}

@@ -3,7 +3,8 @@
 so a synthetic table of the same shape (1460 rows, 36 numeric features) is used.
 `--device gpu` trains on the device learner (csrc/gbdt_gpu.hip); the default is the host learner.
 `--subsample`, `--colsample-bytree`, `--colsample-bylevel` and `--seed` pass the stochastic-boosting parameters a
-hyper-parameter search over this example would tune (1.0 each: nothing is drawn)."""
+hyper-parameter search over this example would tune (1.0 each: nothing is drawn).
+`--monotone-lot-area` adds `monotone_constraints={0: 1}`: the predicted price never falls when feature 0 rises."""
 import argparse
 import logging
 import os
@@ -28,12 +29,13 @@ def read_input(test_size=TEST_FRACTION_SIZE):
     return (X[:n], y[:n]), (X[n:], y[n:])
 
 
-def run_training_and_eval(device="cpu", subsample=1.0, colsample_bytree=1.0, colsample_bylevel=1.0, seed=0, max_leaves=0):
+def run_training_and_eval(device="cpu", subsample=1.0, colsample_bytree=1.0, colsample_bylevel=1.0, seed=0, max_leaves=0,
+                          monotone=None):
     (tx, ty), (vx, vy) = read_input()
     policy = dict(grow_policy="lossguide", max_leaves=max_leaves, max_depth=0) if max_leaves else {}  # leaf-wise growth
     model = XGBRegressor(n_estimators=ESTIMATORS, learning_rate=LEARNING_RATE, device=device, subsample=subsample,
                          colsample_bytree=colsample_bytree, colsample_bylevel=colsample_bylevel, random_state=seed,
-                         **policy)
+                         monotone_constraints=monotone, **policy)
     model.fit(tx, ty, early_stopping_rounds=EARLY_STOPPING_ROUNDS, eval_set=[(vx, vy)])
     logging.info("Best RMSE on eval: %.2f with %d rounds", model.best_score, model.best_iteration + 1)
     mae = mean_absolute_error(model.predict(vx), vy)
@@ -61,8 +63,11 @@ if __name__ == "__main__":
     ap.add_argument("--seed", type=int, default=0, help="random_state of the draws")
     ap.add_argument("--max-leaves", type=int, default=0,
                     help="0 (default): depth-wise trees of depth 6; L >= 2: leaf-wise trees of L leaves (lossguide)")
+    ap.add_argument("--monotone-lot-area", action="store_true",
+                    help="monotone_constraints={0: 1}: the prediction never falls when feature 0 rises")
     args = ap.parse_args()
     fairing.config.set_builder("append", base_image="rocm/pytorch:latest", registry="local", push=False)
     fairing.config.set_deployer("local")
     print(fairing.config.fn(run_training_and_eval)(args.device, args.subsample, args.colsample_bytree,
-                                                   args.colsample_bylevel, args.seed, args.max_leaves))
+                                                   args.colsample_bylevel, args.seed, args.max_leaves,
+                                                   {0: 1} if args.monotone_lot_area else None))

@@ -66,6 +66,19 @@ int64, so the host twin `device="cpu", fixed_point=True` still equals the GPU mo
 lossguide raise ValueError. Prediction, contributions and interactions walk child indices and do not change;
 TreeSHAP's limit of 12 distinct features on a path applies to deep chains too.
 
+Monotone predictions, on all three learners, both growth policies and all three estimators:
+`monotone_constraints` is a sequence of one direction per feature in {-1, 0, +1}, or a dict {feature index: direction}
+(0 elsewhere); None or all zeros is unconstrained and takes the code paths and gives the bits it always did. The rule has
+one copy (csrc/gbdt_split.h): every node carries an interval [lo, hi] of weights, the root's unbounded; a weight is
+-G / (H + lambda) clamped into it and a leaf holds learning_rate times that; gains use the score
+-(2 G w + (H + lambda) w w) with clamped weights for parent and children; a candidate on a +1 feature with wl > wr (-1:
+wl < wr) is dropped; the children of a split on a constrained feature divide the interval at (wl + wr) / 2. So the
+margin never falls (+1) or rises (-1) when the feature rises, exactly, for every setting of the other features, NaN
+included. Candidate order and tie rules are the unconstrained ones. On the GPU: k_split_mono / k_decide_mono
+(csrc/gbdt_gpu.hip) and k_split_mono (csrc/gbdt_lossguide.hip), equal to the host twin bit for bit. With
+reg:absoluteerror / reg:quantileerror the refreshed leaves would need clamping to their intervals: not implemented,
+ValueError. A wrong length, a value outside {-1, 0, 1} or a non-integer raises ValueError before the first round.
+
 Robust loss and prediction intervals, on all three learners: `XGBRegressor(objective="reg:absoluteerror")` and
 `objective="reg:quantileerror", quantile_alpha=a` (one scalar a in (0, 1); absolute error is a = 0.5), XGBoost's
 objectives with its "adaptive tree". With d = margin - y in double the pair is g = +1 / 0 / -1 for d > 0 / = 0 / < 0
@@ -171,6 +184,10 @@ def _lib():
     a = lib.mifx_gbdt_grow_stats.argtypes  # the leaf-wise growers: max_leaves follows max_depth, the mask is [f]
     lib.mifx_gbdt_grow_lossguide_stats.argtypes = a[:7] + [ctypes.c_int] + a[7:]
     lib.mifx_gbdt_grow_fixed_lossguide_stats.argtypes = lib.mifx_gbdt_grow_lossguide_stats.argtypes
+    for name in ("", "_fixed", "_lossguide", "_fixed_lossguide"):  # the *_stats arguments, then the directions [f]
+        fn = getattr(lib, f"mifx_gbdt_grow{name}_mono")
+        fn.argtypes = getattr(lib, f"mifx_gbdt_grow{name}_stats").argtypes + [_I]
+        fn.restype = ctypes.c_int
     u64 = ctypes.c_uint64
     lib.mifx_gbdt_sample_rows.argtypes = [u64, u64, ctypes.c_double, ctypes.c_long, _U8]
     lib.mifx_gbdt_sample_rows.restype = ctypes.c_long
@@ -377,15 +394,18 @@ class _Base:
                  base_score: float | None = None, n_jobs: int | None = None, random_state: int = 0,
                  verbosity: int = 0, device: str | None = None, fixed_point: bool | None = None,
                  subsample: float = 1.0, colsample_bytree: float = 1.0, colsample_bylevel: float = 1.0,
-                 importance_type: str = "gain", grow_policy: str = "depthwise", max_leaves: int = 0):
+                 importance_type: str = "gain", grow_policy: str = "depthwise", max_leaves: int = 0,
+                 monotone_constraints=None):
         self.n_estimators, self.learning_rate, self.max_depth = n_estimators, learning_rate, max_depth
         self.min_child_weight, self.reg_lambda, self.gamma, self.max_bins = min_child_weight, reg_lambda, gamma, max_bins
         self.base_score, self.n_jobs = base_score, n_jobs
         self.random_state, self.verbosity = random_state, verbosity  # random_state: the seed of every draw
         self.subsample, self.colsample_bytree, self.colsample_bylevel = subsample, colsample_bytree, colsample_bylevel
         self.grow_policy, self.max_leaves = grow_policy, max_leaves
+        self.monotone_constraints = monotone_constraints
         self._check_rates()
         self._check_policy()
+        self._monotone(None)
         self.best_iteration, self.best_score, self.evals_result_ = None, None, {}
         self._trees: list[tuple] = []
         self._node_stats: list[tuple] = []  # per tree (gain, cover), parallel to _trees
@@ -425,6 +445,38 @@ class _Base:
             raise ValueError(f"max_depth must be >= 0 (0: no depth limit), got {self.max_depth}")
         if self._rates()[2] < 1.0:
             raise ValueError("colsample_bylevel < 1 is not defined for grow_policy='lossguide' (use colsample_bytree)")
+
+    def _monotone(self, f: int | None):
+        """monotone_constraints as int32 [f] directions, or None when nothing is constrained (None, empty, all zeros;
+        a model pickled before the argument existed): the growers then take their unconstrained paths. A sequence of f
+        integers in {-1, 0, +1} or a dict {feature index: direction}; f = None checks the values only."""
+        mc = getattr(self, "monotone_constraints", None)
+        if mc is None:
+            return None
+        if isinstance(mc, dict):
+            keys = list(mc)
+            if any(isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 0 for k in keys):
+                raise ValueError(f"monotone_constraints: the keys of a dict are feature indices, got {keys!r}")
+            if f is not None and any(k >= f for k in keys):
+                raise ValueError(f"monotone_constraints names feature {max(keys)} but the table has {f} features")
+            vals, size = list(mc.values()), (max(keys, default=-1) + 1 if f is None else f)
+        else:
+            if isinstance(mc, (str, bytes)) or np.ndim(mc) != 1:
+                raise ValueError("monotone_constraints must be a sequence of integers or a dict {feature: direction}")
+            vals, keys, size = list(mc), None, len(mc)
+            if f is not None and size != f:
+                raise ValueError(f"monotone_constraints holds {size} directions but the table has {f} features")
+        for v in vals:
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v not in (-1, 0, 1):
+                raise ValueError(f"monotone_constraints: every direction must be the integer -1, 0 or +1, got {v!r}")
+        out = np.zeros(size, np.int32)
+        out[keys if keys is not None else slice(None)] = vals
+        if not out.any():
+            return None
+        if self._refresh_alpha() is not None:
+            raise ValueError("monotone_constraints with reg:absoluteerror / reg:quantileerror is not implemented: the "
+                             "refreshed leaf values would have to be clamped to the leaves' intervals")
+        return out
 
     def _seed(self) -> int:
         return int(getattr(self, "random_state", 0) or 0) & _M64
@@ -570,8 +622,13 @@ class _Base:
         val = np.empty(cap, np.float64)
         gain, cover = np.empty(cap, np.float64), np.empty(cap, np.float64)
         grow = _lib().mifx_gbdt_grow_fixed_stats if self._fixed() else _lib().mifx_gbdt_grow_stats
+        mono = getattr(self, "_mono", None)  # fit's validated directions: the constrained entries take them last
+        if mono is not None:
+            grow = _lib().mifx_gbdt_grow_fixed_mono if self._fixed() else _lib().mifx_gbdt_grow_mono
         if lossguide:
             fn = _lib().mifx_gbdt_grow_fixed_lossguide_stats if self._fixed() else _lib().mifx_gbdt_grow_lossguide_stats
+            if mono is not None:
+                fn = _lib().mifx_gbdt_grow_fixed_lossguide_mono if self._fixed() else _lib().mifx_gbdt_grow_lossguide_mono
             grow = lambda *a: fn(*a[:7], leaves, *a[7:])  # noqa: E731
         if rows is not None:
             rows = np.ascontiguousarray(rows, np.int32)
@@ -582,7 +639,8 @@ class _Base:
                    float(self.gamma), float(self.learning_rate), self._nthreads(), cap, _p(fe, _I),
                    _p(sb, _I), _p(dl, _U8), _p(left, _I), _p(right, _I), _p(val, _D),
                    _p(leaf_of_row, _I), None if rows is None else _p(rows, _I), 0 if rows is None else len(rows),
-                   None if level_mask is None else _p(level_mask, _U8), _p(gain, _D), _p(cover, _D))
+                   None if level_mask is None else _p(level_mask, _U8), _p(gain, _D), _p(cover, _D),
+                   *(() if mono is None else (_p(mono, _I),)))
         if cnt < 0:
             raise RuntimeError("tree exceeded its node capacity")
         thr = np.zeros(cnt, np.float64)
@@ -610,6 +668,7 @@ class _Base:
             raise ValueError("X must be [n, features] with one label per row")
         w = self._row_weights(self._weights(sample_weight, y), y)
         self._nfeat = X.shape[1]
+        self._mono = self._monotone(self._nfeat)
         if gpu is not None:
             return self._fit_gpu(X, y, eval_set, early_stopping_rounds, verbose, w)
         X = np.ascontiguousarray(np.asarray(X, dtype=np.float64))
@@ -714,8 +773,8 @@ class _Base:
             masks = np.stack([level_mask(self._seed(), t, self._nfeat, int(self.max_depth), bytree, bylevel)
                               for t in range(rounds * K)])
         with torch.cuda.device(dev):
-            bst = G.LossguideBooster.from_device_bins(bins, nbins, int(self.max_depth), leaves) if lossguide else \
-                G.Booster.from_device_bins(bins, nbins, int(self.max_depth))
+            bst = G.LossguideBooster.from_device_bins(bins, nbins, int(self.max_depth), leaves, self._mono) \
+                if lossguide else G.Booster.from_device_bins(bins, nbins, int(self.max_depth), self._mono)
             yd = torch.from_numpy(y).to(dev)
             wd = None if w is None else torch.from_numpy(w).to(dev)
             masks = None if masks is None else torch.from_numpy(masks).to(dev)

@@ -58,6 +58,10 @@ def _fns():
         "grow_stats": sig(lib, "mifx_gbdt_gpu_grow_stats", [VP, LONG, I32, VP, VP, I32, VP, VP, I32, F64, F64, F64, F64,
                                                              VP, I64, VP, VP, VP, VP, VP, VP, VP, VP, VP, I32, I32, U64,
                                                              U64, U64, VP, I32, VP, VP, VP]),
+        "ws_bytes_mono": sig(lib, "mifx_gbdt_gpu_ws_bytes_mono", [LONG, I32, I32, I32], I64),
+        "grow_mono": sig(lib, "mifx_gbdt_gpu_grow_mono", [VP, LONG, I32, VP, VP, I32, VP, VP, I32, F64, F64, F64, F64,
+                                                           VP, I64, VP, VP, VP, VP, VP, VP, VP, VP, VP, I32, I32, U64,
+                                                           U64, U64, VP, I32, VP, VP, VP, VP]),
         "apply": sig(lib, "mifx_gbdt_gpu_apply", [VP, LONG, I32, VP, VP, VP, VP, VP, VP, VP, I32, VP, VP]),
         "grad_softmax": sig(lib, "mifx_gbdt_gpu_grad_softmax", [VP, VP, VP, LONG, I32, VP, VP, VP]),
     }
@@ -74,6 +78,10 @@ def _lg_fns():
         "grow": sig(lib, "mifx_gbdt_lg_grow", [VP, LONG, I32, VP, VP, I32, VP, VP, I32, I32, F64, F64, F64, F64, VP, I64,
                                                VP, VP, VP, VP, VP, VP, VP, VP, VP, I32, I32, I32, U64, U64, U64, VP, VP,
                                                VP, VP]),
+        "ws_bytes_mono": sig(lib, "mifx_gbdt_lg_ws_bytes_mono", [LONG, I32, I32, I32], I64),
+        "grow_mono": sig(lib, "mifx_gbdt_lg_grow_mono", [VP, LONG, I32, VP, VP, I32, VP, VP, I32, I32, F64, F64, F64, F64,
+                                                         VP, I64, VP, VP, VP, VP, VP, VP, VP, VP, VP, I32, I32, I32, U64,
+                                                         U64, U64, VP, VP, VP, VP, VP]),
         "apply": sig(lib, "mifx_gbdt_lg_apply", [VP, LONG, I32, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP]),
     }
 
@@ -220,27 +228,42 @@ def row_threshold(subsample: float) -> int:
 
 
 class Booster:
-    """Device-resident state of one fit: bins [n, f], per-feature bin counts, the grower's workspace."""
+    """Device-resident state of one fit: bins [n, f], per-feature bin counts, the grower's workspace.
 
-    def __init__(self, bins: np.ndarray, nbins: np.ndarray, max_depth: int, dev: torch.device):
+    `monotone` (int [f] in {-1, 0, +1}, None or all zeros = unconstrained) makes every tree of this Booster a constrained
+    one (the rule of csrc/gbdt_split.h; k_split_mono / k_decide_mono): the workspace grows by two doubles per node."""
+
+    def __init__(self, bins: np.ndarray, nbins: np.ndarray, max_depth: int, dev: torch.device, monotone=None):
         f, n = bins.shape
+        self._set_monotone(monotone, f, dev)
         self._setup(n, f, nbins, max_depth, dev, lambda: upload_bins(bins, dev))
 
     @classmethod
-    def from_device_bins(cls, bins: torch.Tensor, nbins: np.ndarray, max_depth: int) -> "Booster":
+    def from_device_bins(cls, bins: torch.Tensor, nbins: np.ndarray, max_depth: int, monotone=None) -> "Booster":
         """A Booster on bins that are on the device already: row-major [n, f] int16 (mifx.ops.gbdt_prep.device_bins),
         kept as they are."""
         if not (bins.is_cuda and bins.dim() == 2 and bins.dtype == torch.int16 and bins.is_contiguous()):
             raise ValueError("expected a contiguous [n, f] int16 tensor on the GPU")
         self = cls.__new__(cls)
+        self._set_monotone(monotone, bins.shape[1], bins.device)
         self._setup(bins.shape[0], bins.shape[1], nbins, max_depth, bins.device, lambda: bins)
         return self
+
+    def _set_monotone(self, monotone, f: int, dev: torch.device) -> None:
+        """self.mono: the directions as an int32 [f] tensor on the device, or None for an unconstrained Booster."""
+        self.mono = None
+        if monotone is None or not np.any(monotone):
+            return
+        m = np.asarray(monotone)
+        if m.shape != (f,) or m.dtype.kind not in "iu" or not np.isin(m, (-1, 0, 1)).all():
+            raise ValueError(f"monotone must hold {f} integers in {{-1, 0, +1}}")
+        self.mono = torch.from_numpy(m.astype(np.int32)).to(dev)
 
     def _setup(self, n: int, f: int, nbins: np.ndarray, max_depth: int, dev: torch.device, device_bins) -> None:
         check_limits(n, int(np.max(nbins)), max_depth)
         self._setup_data(n, f, nbins, max_depth, dev, device_bins)
         self.cap = 2 ** (self.max_depth + 1)
-        nbytes = _fns()["ws_bytes"](n, f, self.max_depth, self.hsize)
+        nbytes = _fns()["ws_bytes" if self.mono is None else "ws_bytes_mono"](n, f, self.max_depth, self.hsize)
         if nbytes < 0:
             raise ValueError("shape outside the device learner's limits")
         self.ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
@@ -298,6 +321,18 @@ class Booster:
                       and tuple(level_mask.shape) == (self.max_depth, self.f)):
                 raise ValueError(f"level_mask must be a contiguous uint8 [{self.max_depth}, {self.f}] tensor on "
                                  f"{self.dev}")
+        if self.mono is not None:  # the constrained grower: one entry, statistics or not
+            gain, cover = stats if stats is not None else (None, None)
+            for s in (gain, cover):
+                assert s is None or (s.dtype == torch.float64 and s.is_contiguous() and s.numel() == self.cap)
+            check(_fns()["grow_mono"](ptr(self.bins), self.n, self.f, ptr(self.nbins), ptr(self.hoff), self.hsize,
+                                      ptr(g), ptr(h), self.max_depth, float(min_child_weight), float(reg_lambda),
+                                      float(gamma), float(eta), ptr(self.ws), self.ws.numel(), ptr(fe), ptr(sb),
+                                      ptr(dl), ptr(le), ptr(ri), ptr(val), ptr(cnt), ptr(self.leaf_of_row),
+                                      ptr(margin), rows, tile, int(seed) & (2 ** 64 - 1), int(round) & (2 ** 64 - 1),
+                                      thr, ptr(level_mask), int(_margin_route), ptr(gain), ptr(cover), ptr(self.mono),
+                                      stream_handle(self.dev)), "mifx_gbdt_gpu_grow_mono")
+            return
         if stats is not None:
             gain, cover = stats
             for s in (gain, cover):
@@ -346,17 +381,20 @@ class LossguideBooster(Booster):
     hsize = sum over features of nbins + 1: the quantised rows and two permutation arrays, the node table, one
     expansion's per-feature candidates, and the pool of max_leaves histograms (int64 g, int64 h, int32 rows)."""
 
-    def __init__(self, bins: np.ndarray, nbins: np.ndarray, max_depth: int, max_leaves: int, dev: torch.device):
+    def __init__(self, bins: np.ndarray, nbins: np.ndarray, max_depth: int, max_leaves: int, dev: torch.device,
+                 monotone=None):
         f, n = bins.shape
         self.max_leaves = int(max_leaves)
+        self._set_monotone(monotone, f, dev)
         self._setup(n, f, nbins, max_depth, dev, lambda: upload_bins(bins, dev))
 
     @classmethod
-    def from_device_bins(cls, bins: torch.Tensor, nbins: np.ndarray, max_depth: int, max_leaves: int):
+    def from_device_bins(cls, bins: torch.Tensor, nbins: np.ndarray, max_depth: int, max_leaves: int, monotone=None):
         if not (bins.is_cuda and bins.dim() == 2 and bins.dtype == torch.int16 and bins.is_contiguous()):
             raise ValueError("expected a contiguous [n, f] int16 tensor on the GPU")
         self = cls.__new__(cls)
         self.max_leaves = int(max_leaves)
+        self._set_monotone(monotone, bins.shape[1], bins.device)
         self._setup(bins.shape[0], bins.shape[1], nbins, max_depth, bins.device, lambda: bins)
         return self
 
@@ -364,7 +402,7 @@ class LossguideBooster(Booster):
         check_limits_lossguide(n, int(np.max(nbins)), int(max_depth), self.max_leaves)
         self._setup_data(n, f, nbins, max_depth, dev, device_bins)
         self.cap = 2 * self.max_leaves - 1
-        nbytes = _lg_fns()["ws_bytes"](n, f, self.max_leaves, self.hsize)
+        nbytes = _lg_fns()["ws_bytes" if self.mono is None else "ws_bytes_mono"](n, f, self.max_leaves, self.hsize)
         if nbytes < 0:
             raise ValueError("shape outside the device learner's limits")
         self.ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
@@ -393,12 +431,15 @@ class LossguideBooster(Booster):
             assert s is None or (s.dtype == torch.float64 and s.is_contiguous() and s.numel() == self.cap)
         fe, sb, dl, le, ri, val, cnt = tree
         m64 = 2 ** 64 - 1
-        check(_lg_fns()["grow"](ptr(self.bins), self.n, self.f, ptr(self.nbins), ptr(self.hoff), self.hsize, ptr(g),
-                                ptr(h), self.max_depth, self.max_leaves, float(min_child_weight), float(reg_lambda),
-                                float(gamma), float(eta), ptr(self.ws), self.ws.numel(), ptr(fe), ptr(sb), ptr(dl),
-                                ptr(le), ptr(ri), ptr(val), ptr(cnt), ptr(self.leaf_of_row), ptr(margin), rows, tile,
-                                gx, int(seed) & m64, int(round) & m64, row_threshold(subsample), ptr(feature_mask),
-                                ptr(gain), ptr(cover), stream_handle(self.dev)), "mifx_gbdt_lg_grow")
+        args = (ptr(self.bins), self.n, self.f, ptr(self.nbins), ptr(self.hoff), self.hsize, ptr(g), ptr(h),
+                self.max_depth, self.max_leaves, float(min_child_weight), float(reg_lambda), float(gamma), float(eta),
+                ptr(self.ws), self.ws.numel(), ptr(fe), ptr(sb), ptr(dl), ptr(le), ptr(ri), ptr(val), ptr(cnt),
+                ptr(self.leaf_of_row), ptr(margin), rows, tile, gx, int(seed) & m64, int(round) & m64,
+                row_threshold(subsample), ptr(feature_mask), ptr(gain), ptr(cover))
+        if self.mono is not None:
+            check(_lg_fns()["grow_mono"](*args, ptr(self.mono), stream_handle(self.dev)), "mifx_gbdt_lg_grow_mono")
+            return
+        check(_lg_fns()["grow"](*args, stream_handle(self.dev)), "mifx_gbdt_lg_grow")
 
     def apply(self, ebins: torch.Tensor, tree, emargin: torch.Tensor) -> None:
         """emargin += tree(row) for a binned row-major [m, f] matrix; the walk is bounded by the tree's own depth."""
@@ -413,14 +454,15 @@ class LossguideBooster(Booster):
 def grow_lossguide_numpy(bins: np.ndarray, nbins: np.ndarray, g: np.ndarray, h: np.ndarray, max_depth: int,
                          max_leaves: int, min_child_weight: float = 1.0, reg_lambda: float = 1.0, gamma: float = 0.0,
                          eta: float = 0.3, device: int = 0, subsample: float = 1.0, seed: int = 0, round: int = 0,
-                         feature_mask: np.ndarray | None = None, margin: np.ndarray | None = None, **geometry):
+                         feature_mask: np.ndarray | None = None, margin: np.ndarray | None = None, monotone=None,
+                         **geometry):
     """One leaf-wise tree on the device from host arrays: (feature, split_bin, default_left, left, right, value,
     leaf_of_row, gain, cover), the outputs of the host's mifx_gbdt_grow_fixed_lossguide_stats (with subsample on the
     rows sampled for (seed, round)); with `margin` (float64 [n]) the updated margins follow as a tenth array.
     `geometry`: _rows_per_wg, _feat_tile, _grid_x."""
     dev = device_for(device)
     with torch.cuda.device(dev):
-        b = LossguideBooster(bins, nbins, max_depth, max_leaves, dev)
+        b = LossguideBooster(bins, nbins, max_depth, max_leaves, dev, monotone)
         tree = tuple(t[0] for t in b.new_trees(1))
         st = tuple(s[0] for s in b.new_stats(1))
         gd = torch.from_numpy(np.ascontiguousarray(g, np.float32)).to(dev)
@@ -439,14 +481,14 @@ def grow_numpy(bins: np.ndarray, nbins: np.ndarray, g: np.ndarray, h: np.ndarray
                min_child_weight: float = 1.0, reg_lambda: float = 1.0, gamma: float = 0.0, eta: float = 0.3,
                device: int = 0, _rows_per_wg: int | None = None, _feat_tile: int | None = None, _booster=None,
                subsample: float = 1.0, seed: int = 0, round: int = 0, level_mask: np.ndarray | None = None,
-               stats: bool = False):
+               stats: bool = False, monotone=None):
     """One tree on the device from host arrays: (feature, split_bin, default_left, left, right, value, leaf_of_row),
     the outputs of the host's mifx_gbdt_grow_fixed (with subsample / level_mask: of mifx_gbdt_grow_fixed_ex on the
     rows sampled for (seed, round); level_mask is a host [max_depth, f] uint8 array). `stats`: the nodes' (gain, cover)
     of mifx_gbdt_grow_fixed_stats follow as an eighth and ninth array."""
     dev = device_for(device)
     with torch.cuda.device(dev):
-        b = _booster or Booster(bins, nbins, max_depth, dev)
+        b = _booster or Booster(bins, nbins, max_depth, dev, monotone)
         trees = b.new_trees(1)
         tree = tuple(t[0] for t in trees)
         st = tuple(s[0] for s in b.new_stats(1)) if stats else None
