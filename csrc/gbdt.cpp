@@ -47,6 +47,7 @@
 #include <vector>
 
 #include "gbdt_auc.h"
+#include "gbdt_nodeset.h"
 #include "gbdt_quantile.h"
 #include "gbdt_rank.h"
 #include "gbdt_sample.h"
@@ -74,6 +75,7 @@ struct Node {
   double g, h;
   std::vector<Hist> hist;  // [features][nbins + 1], the last slot is "missing"
   double lo, hi;           // the weight interval of monotone_constraints (gbdt_split.h)
+  std::vector<uint64_t> S;  // the path set of gbdt_nodeset.h (kept only under a node-set spec)
 };
 
 template <class F>
@@ -107,6 +109,22 @@ bool mono_ok(const int* mono, int f) {
   for (int j = 0; j < f; ++j)
     if (mono[j] < -1 || mono[j] > 1) return false;
   return true;
+}
+
+// the *_nodeset entries' spec: a rate in (0, 1], groups over [0, f) only (the bits past f clear)
+bool nodeset_ok(const MifxNsSpec& ns, int f) {
+  if (!(ns.bynode > 0.0 && ns.bynode <= 1.0) || (ns.groups && ns.n_groups < 1)) return false;
+  const int words = mifx_ns_words(f);
+  for (int g = 0; ns.groups && g < ns.n_groups; ++g)
+    if ((f & 63) && ns.groups[(size_t)g * words + words - 1] >> (f & 63)) return false;
+  return true;
+}
+
+// a child's path set: the parent's and the split feature
+std::vector<uint64_t> child_set(const std::vector<uint64_t>& S, int feature) {
+  std::vector<uint64_t> c = S;
+  c[feature >> 6] |= (uint64_t)1 << (feature & 63);
+  return c;
 }
 
 }  // namespace
@@ -215,11 +233,13 @@ int mifx_gbdt_bin(const double* X, long n, int f, const double* cuts, const int*
 //
 // mono (null = unconstrained, and then every expression is the one it always was): [f] directions in {-1, 0, +1}, the
 // monotone_constraints rule of gbdt_split.h; every node carries its weight interval.
+// nsp (null = none): the per-node feature sets of gbdt_nodeset.h; every node carries its path set, and a feature
+// outside the node's split set yields no candidate, as a masked one.
 static int grow_double(const uint16_t* bins, long n, int f, const int* nbins, const float* g, const float* h,
                        int max_depth, double min_child_weight, double lambda, double gamma, double eta, int threads,
                        int max_nodes, int* feature, int* split_bin, uint8_t* default_left, int* left, int* right,
                        double* value, int* leaf_of_row, const int* sample, long n_rows, const uint8_t* level_mask,
-                       double* node_gain, double* node_cover, const int* mono) {
+                       double* node_gain, double* node_cover, const int* mono, const MifxNsSpec* nsp = nullptr) {
   if (!rows_ok(sample, n_rows, n)) return -2;
   const MifxGbParams prm{lambda, gamma, min_child_weight, eta};
   std::vector<int> off(f + 1, 0);
@@ -251,9 +271,15 @@ static int grow_double(const uint16_t* bins, long n, int f, const int* nbins, co
   auto best_split = [&](const Node& nd) {
     std::vector<Split> per(f);
     const double parent = mono ? mifx_gb_mono_parent(nd.g, nd.h, lambda, nd.lo, nd.hi) : score(nd.g, nd.h);
+    const uint8_t* lrow = level_mask ? level_mask + (size_t)nd.depth * f : nullptr;
+    std::vector<uint8_t> allow;  // the node's mask row
+    if (nsp) {
+      allow.resize(f);
+      mifx_ns_node_mask(*nsp, f, (uint64_t)nd.id, nd.S.data(), lrow, allow.data());
+    }
     parallel_for(f, th, [&](int j) {
       const Hist* hj = nd.hist.data() + off[j];
-      const int nb = level_mask && !level_mask[(size_t)nd.depth * f + j] ? 1 : nbins[j];
+      const int nb = (nsp ? !(allow[j] & MIFX_NS_SPLIT) : lrow && !lrow[j]) ? 1 : nbins[j];
       const double gm = hj[nbins[j]].g, hm = hj[nbins[j]].h;
       Split bs;
       double gl = 0, hl = 0;
@@ -297,7 +323,8 @@ static int grow_double(const uint16_t* bins, long n, int f, const int* nbins, co
     if (node_cover) node_cover[count] = 0.0;
     return count++;
   };
-  Node root{0, (int)ns, 0, new_node(), 0.0, 0.0, {}, -INFINITY, INFINITY};
+  Node root{0, (int)ns, 0, new_node(), 0.0, 0.0, {}, -INFINITY, INFINITY, {}};
+  if (nsp) root.S.assign(mifx_ns_words(f), 0);
   if (root.id < 0) return -1;
   if (ns == 0) return count;  // nothing sampled: the root alone, value +0.0
   for (long i = 0; i < ns; ++i) {
@@ -339,8 +366,9 @@ static int grow_double(const uint16_t* bins, long n, int f, const int* nbins, co
       right[nd.id] = ri;
       double b[4] = {nd.lo, nd.hi, nd.lo, nd.hi};  // the children's intervals
       if (mono) mifx_gb_mono_children(s.gl, s.hl, s.gr, s.hr, lambda, mono[s.feature], nd.lo, nd.hi, b);
-      Node L{nd.begin, mid, nd.depth + 1, li, s.gl, s.hl, {}, b[0], b[1]};
-      Node R{mid, nd.end, nd.depth + 1, ri, s.gr, s.hr, {}, b[2], b[3]};
+      Node L{nd.begin, mid, nd.depth + 1, li, s.gl, s.hl, {}, b[0], b[1], {}};
+      Node R{mid, nd.end, nd.depth + 1, ri, s.gr, s.hr, {}, b[2], b[3], {}};
+      if (nsp) L.S = R.S = child_set(nd.S, s.feature);
       const bool grow_more = nd.depth + 1 < max_depth;
       if (grow_more) {  // smaller child built, larger = parent - smaller
         Node& small = (L.end - L.begin) <= (R.end - R.begin) ? L : R;
@@ -415,7 +443,7 @@ static int grow_fixed(const uint16_t* bins, long n, int f, const int* nbins, con
                       int max_depth, double min_child_weight, double lambda, double gamma, double eta, int threads,
                       int max_nodes, int* feature, int* split_bin, uint8_t* default_left, int* left, int* right,
                       double* value, int* leaf_of_row, const int* sample, long n_rows, const uint8_t* level_mask,
-                      double* node_gain, double* node_cover, const int* mono) {
+                      double* node_gain, double* node_cover, const int* mono, const MifxNsSpec* nsp = nullptr) {
   if (!rows_ok(sample, n_rows, n)) return -2;
   struct QNode {
     int begin, end, depth, id;
@@ -423,6 +451,7 @@ static int grow_fixed(const uint16_t* bins, long n, int f, const int* nbins, con
     std::vector<long long> hg, hh;  // [features][nbins + 1], the last slot is "missing"
     std::vector<int> hc;            // rows per slot
     double lo, hi;                  // the weight interval of monotone_constraints
+    std::vector<uint64_t> S;        // the path set of gbdt_nodeset.h (kept only under a node-set spec, nsp)
   };
   const MifxGbParams prm{lambda, gamma, min_child_weight, eta};
   std::vector<int> off(f + 1, 0);
@@ -475,9 +504,15 @@ static int grow_fixed(const uint16_t* bins, long n, int f, const int* nbins, con
     const double parent = mono ? mifx_gb_mono_parent(mifx_gb_dequant(nd.g, eg), mifx_gb_dequant(nd.h, eh), lambda,
                                                      nd.lo, nd.hi)
                                : mifx_gb_parent_score(nd.g, nd.h, eg, eh, prm);
+    const uint8_t* lrow = level_mask ? level_mask + (size_t)nd.depth * f : nullptr;
+    std::vector<uint8_t> allow;  // the node's mask row
+    if (nsp) {
+      allow.resize(f);
+      mifx_ns_node_mask(*nsp, f, (uint64_t)nd.id, nd.S.data(), lrow, allow.data());
+    }
     parallel_for(f, th, [&](int j) {
       MifxGbSplit bs = mifx_gb_no_split();
-      const bool live = !level_mask || level_mask[(size_t)nd.depth * f + j];
+      const bool live = nsp ? (allow[j] & MIFX_NS_SPLIT) != 0 : !lrow || lrow[j];
       if (live && mono)
         mifx_gb_scan_mono(nd.hg.data() + off[j], nd.hh.data() + off[j], nd.hc.data() + off[j], nbins[j], 0, nbins[j],
                           0, 0, 0, nd.g, nd.h, eg, eh, j, prm, parent, mono[j], nd.lo, nd.hi, &bs);
@@ -504,7 +539,8 @@ static int grow_fixed(const uint16_t* bins, long n, int f, const int* nbins, con
     if (node_cover) node_cover[count] = 0.0;
     return count++;
   };
-  QNode root{0, (int)ns, 0, new_node(), 0, 0, {}, {}, {}, -INFINITY, INFINITY};
+  QNode root{0, (int)ns, 0, new_node(), 0, 0, {}, {}, {}, -INFINITY, INFINITY, {}};
+  if (nsp) root.S.assign(mifx_ns_words(f), 0);
   if (root.id < 0) return -1;
   if (ns == 0) return count;  // nothing sampled: the root alone, value +0.0
   for (long i = 0; i < ns; ++i) {
@@ -544,8 +580,9 @@ static int grow_fixed(const uint16_t* bins, long n, int f, const int* nbins, con
       right[nd.id] = ri;
       double b[4] = {nd.lo, nd.hi, nd.lo, nd.hi};  // the children's intervals
       if (mono) mifx_gb_mono_children_q(s, nd.g, nd.h, eg, eh, prm, mono[s.feature], nd.lo, nd.hi, b);
-      QNode L{nd.begin, mid, nd.depth + 1, li, s.gl, s.hl, {}, {}, {}, b[0], b[1]};
-      QNode R{mid, nd.end, nd.depth + 1, ri, nd.g - s.gl, nd.h - s.hl, {}, {}, {}, b[2], b[3]};
+      QNode L{nd.begin, mid, nd.depth + 1, li, s.gl, s.hl, {}, {}, {}, b[0], b[1], {}};
+      QNode R{mid, nd.end, nd.depth + 1, ri, nd.g - s.gl, nd.h - s.hl, {}, {}, {}, b[2], b[3], {}};
+      if (nsp) L.S = R.S = child_set(nd.S, s.feature);
       if (nd.depth + 1 < max_depth) {  // smaller child built, larger = parent - smaller (identical in integers)
         QNode& small = (L.end - L.begin) <= (R.end - R.begin) ? L : R;
         QNode& large = &small == &L ? R : L;
@@ -606,6 +643,24 @@ int mifx_gbdt_grow_fixed(const uint16_t* bins, long n, int f, const int* nbins, 
   return mifx_gbdt_grow_fixed_ex(bins, n, f, nbins, g, h, max_depth, min_child_weight, lambda, gamma, eta, threads,
                                  max_nodes, feature, split_bin, default_left, left, right, value, leaf_of_row, nullptr,
                                  0, nullptr);
+}
+
+// The depth-wise growers with per-node feature sets (interaction_constraints, colsample_bynode: the rule of
+// gbdt_nodeset.h): the arguments of mifx_gbdt_grow_mono with a nullable mono, in front of them `fixed` (0: the double
+// learner, 1: the fixed-point one, the host twin of mifx_gbdt_gpu_grow_nodeset), and after them groups (nullable)
+// [n_groups, ceil(f / 64)] uint64 bitsets, the colsample_bynode rate (1.0: no draw) and the draw's (seed, round).
+// level_mask is then every node's level set. -3: directions or a spec out of range.
+int mifx_gbdt_grow_nodeset(int fixed, const uint16_t* bins, long n, int f, const int* nbins, const float* g,
+                           const float* h, int max_depth, double min_child_weight, double lambda, double gamma,
+                           double eta, int threads, int max_nodes, int* feature, int* split_bin, uint8_t* default_left,
+                           int* left, int* right, double* value, int* leaf_of_row, const int* sample, long n_rows,
+                           const uint8_t* level_mask, double* node_gain, double* node_cover, const int* mono,
+                           const uint64_t* groups, int n_groups, double bynode, uint64_t seed, uint64_t round) {
+  const MifxNsSpec ns{groups, groups ? n_groups : 0, bynode, seed, round};
+  if ((mono && !mono_ok(mono, f)) || !nodeset_ok(ns, f)) return -3;
+  return (fixed ? grow_fixed : grow_double)(bins, n, f, nbins, g, h, max_depth, min_child_weight, lambda, gamma, eta,
+                                            threads, max_nodes, feature, split_bin, default_left, left, right, value,
+                                            leaf_of_row, sample, n_rows, level_mask, node_gain, node_cover, mono, &ns);
 }
 
 // ---- the leaf refresh of reg:absoluteerror / reg:quantileerror (gbdt_quantile.h has the rule): value[l] of every leaf
@@ -744,6 +799,7 @@ struct LgArgs {
   const uint8_t* feature_mask;  // [f], null = all
   double *node_gain, *node_cover;
   const int* mono = nullptr;  // [f] monotone_constraints (gbdt_split.h), null = unconstrained
+  const MifxNsSpec* ns = nullptr;  // per-node feature sets (gbdt_nodeset.h), null = none; feature_mask is the level set
 };
 
 struct LgCand {  // a node's candidate in either arithmetic
@@ -760,6 +816,7 @@ struct DoubleCore {
     double g = 0, h = 0, gl = 0, hl = 0;  // sums; the candidate's left sums
     std::vector<Hist> hist;
     double lo = -INFINITY, hi = INFINITY;  // the weight interval of monotone_constraints
+    std::vector<uint64_t> S;               // the path set of gbdt_nodeset.h (kept only under a spec)
   };
   const LgArgs& a;
   const std::vector<int>& off;
@@ -792,14 +849,14 @@ struct DoubleCore {
     }
   }
   void release(Node& nd) { std::vector<Hist>().swap(nd.hist); }
-  void search(Node& nd) {
+  void search(Node& nd, const uint8_t* allow) {  // allow (nullable): the node's mask row of gbdt_nodeset.h
     std::vector<Split> per(a.f);
     auto score = [&](double G, double H) { return G * G / (H + a.lambda); };
     const MifxGbParams prm{a.lambda, a.gamma, a.min_child_weight, a.eta};
     const double parent = a.mono ? mifx_gb_mono_parent(nd.g, nd.h, a.lambda, nd.lo, nd.hi) : score(nd.g, nd.h);
     parallel_for(a.f, th, [&](int j) {
       const Hist* hj = nd.hist.data() + off[j];
-      const int nb = a.feature_mask && !a.feature_mask[j] ? 1 : a.nbins[j];
+      const int nb = (allow ? !(allow[j] & MIFX_NS_SPLIT) : a.feature_mask && !a.feature_mask[j]) ? 1 : a.nbins[j];
       const double gm = hj[a.nbins[j]].g, hm = hj[a.nbins[j]].h;
       Split bs;
       double gl = 0, hl = 0;
@@ -855,6 +912,7 @@ struct FixedCore {
     std::vector<long long> hg, hh;
     std::vector<int> hc;
     double lo = -INFINITY, hi = INFINITY;  // the weight interval of monotone_constraints
+    std::vector<uint64_t> S;               // the path set of gbdt_nodeset.h (kept only under a spec)
   };
   const LgArgs& a;
   const std::vector<int>& off;
@@ -907,14 +965,14 @@ struct FixedCore {
     std::vector<long long>().swap(nd.hh);
     std::vector<int>().swap(nd.hc);
   }
-  void search(Node& nd) {
+  void search(Node& nd, const uint8_t* allow) {  // allow (nullable): the node's mask row of gbdt_nodeset.h
     std::vector<MifxGbSplit> per(a.f);
     const double parent = a.mono ? mifx_gb_mono_parent(mifx_gb_dequant(nd.g, eg), mifx_gb_dequant(nd.h, eh), a.lambda,
                                                        nd.lo, nd.hi)
                                  : mifx_gb_parent_score(nd.g, nd.h, eg, eh, prm);
     parallel_for(a.f, th, [&](int j) {
       MifxGbSplit bs = mifx_gb_no_split();
-      const bool live = !a.feature_mask || a.feature_mask[j];
+      const bool live = allow ? (allow[j] & MIFX_NS_SPLIT) != 0 : !a.feature_mask || a.feature_mask[j];
       if (live && a.mono)
         mifx_gb_scan_mono(nd.hg.data() + off[j], nd.hh.data() + off[j], nd.hc.data() + off[j], a.nbins[j], 0,
                           a.nbins[j], 0, 0, 0, nd.g, nd.h, eg, eh, j, prm, parent, a.mono[j], nd.lo, nd.hi, &bs);
@@ -984,15 +1042,21 @@ int grow_lossguide(const LgArgs& a) {
     a.value[nd.id] = nd.end > nd.begin ? core.value(nd) : 0.0;
     if (a.node_cover) a.node_cover[nd.id] = core.cover(nd);
   };
+  std::vector<uint8_t> allow(a.ns ? a.f : 0);
+  auto search = [&](Node& nd) {  // under a spec the node's mask row comes first: its draw is keyed by its id
+    if (a.ns) mifx_ns_node_mask(*a.ns, a.f, (uint64_t)nd.id, nd.S.data(), a.feature_mask, allow.data());
+    core.search(nd, a.ns ? allow.data() : nullptr);
+  };
   nodes.reserve(2 * (size_t)a.max_leaves);  // (pointers into it stay valid)
   Node* root = add(0, (int)ns, 0);
   if (!root) return -1;
+  if (a.ns) root->S.assign(mifx_ns_words(a.f), 0);
   core.start(*root);
   settle(*root);
   int leaves = 1;
   if (can_split(*root) && a.max_leaves >= 2) {
     core.build(*root);
-    core.search(*root);
+    search(*root);
     if (!root->cand.leaf) open.push_back(0);
   }
   while (leaves < a.max_leaves && !open.empty()) {
@@ -1015,6 +1079,7 @@ int grow_lossguide(const LgArgs& a) {
     a.value[p.id] = 0.0;
     if (a.node_gain) a.node_gain[p.id] = c.gain;
     core.children(p, *L, *R);
+    if (a.ns) L->S = R->S = child_set(p.S, c.feature);
     settle(*L);
     settle(*R);
     // candidates only where a child can still be split (both children share the depth; the last split of the budget
@@ -1026,7 +1091,7 @@ int grow_lossguide(const LgArgs& a) {
       core.inherit(large, p, small);
       for (Node* ch : {L, R})
         if (can_split(*ch)) {
-          core.search(*ch);
+          search(*ch);
           if (!ch->cand.leaf) open.push_back(ch->id);
         }
       for (Node* ch : {L, R})
@@ -1099,6 +1164,23 @@ int mifx_gbdt_grow_fixed_lossguide_mono(const uint16_t* bins, long n, int f, con
                                           gamma, eta, threads, max_nodes, feature, split_bin, default_left, left,
                                           right, value, leaf_of_row, sample, n_rows, feature_mask, node_gain,
                                           node_cover, mono});
+}
+
+// The leaf-wise growers with per-node feature sets: mifx_gbdt_grow_nodeset's arguments with max_leaves after max_depth,
+// feature_mask [f] in the level mask's place. fixed = 1 is the host twin of mifx_gbdt_lg_grow_nodeset.
+int mifx_gbdt_grow_lossguide_nodeset(int fixed, const uint16_t* bins, long n, int f, const int* nbins, const float* g,
+                                     const float* h, int max_depth, int max_leaves, double min_child_weight,
+                                     double lambda, double gamma, double eta, int threads, int max_nodes, int* feature,
+                                     int* split_bin, uint8_t* default_left, int* left, int* right, double* value,
+                                     int* leaf_of_row, const int* sample, long n_rows, const uint8_t* feature_mask,
+                                     double* node_gain, double* node_cover, const int* mono, const uint64_t* groups,
+                                     int n_groups, double bynode, uint64_t seed, uint64_t round) {
+  const MifxNsSpec ns{groups, groups ? n_groups : 0, bynode, seed, round};
+  if ((mono && !mono_ok(mono, f)) || !nodeset_ok(ns, f)) return -3;
+  const LgArgs a{bins, n, f, nbins, g, h, max_depth, max_leaves, min_child_weight, lambda, gamma, eta, threads, max_nodes,
+                 feature, split_bin, default_left, left, right, value, leaf_of_row, sample, n_rows, feature_mask,
+                 node_gain, node_cover, mono, &ns};
+  return fixed ? grow_lossguide<FixedCore>(a) : grow_lossguide<DoubleCore>(a);
 }
 
 // Sum of the first n_trees trees' outputs for each row of a row-major [n, f] matrix of raw values. Trees are

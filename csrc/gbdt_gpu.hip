@@ -41,6 +41,14 @@
 // candidates that order the children against the feature's direction, the decision writes the clamped leaf value and
 // the children's intervals. k_hist and k_partition are the same kernels.
 //
+// interaction_constraints / colsample_bynode (mifx_gbdt_gpu_grow_nodeset; the rule is gbdt_nodeset.h's, the host twin
+// mifx_gbdt_grow_nodeset): every node has its own feature set, so the level's one mask row becomes one row per node.
+// A second pair of tables beside lv / nx holds the nodes' path sets (bitsets); k_decide / k_decide_mono write the
+// children's. k_nodeset, one wave per node, then makes the next level's mask rows on the device (the groups that hold
+// the path set, the by-node draw ranked by cross-lane reads); k_split<true> / k_split_mono<true> read row k where they
+// read the level's row, and k_hist<true> skips, per node segment, a feature tile the node cannot use. The <false>
+// instantiations are the kernels of every other entry.
+//
 // Multi-class (multi:softprob, K >= 3 classes): k_grad_softmax computes all K gradient pairs of a round in one launch
 // from class-major [K, n] margins; the round then grows K trees with the grower above, tree k on row k of g, h and
 // the margins. The grower itself knows nothing about classes.
@@ -49,6 +57,7 @@
 
 #include <algorithm>
 
+#include "gbdt_nodeset.h"
 #include "gbdt_quant.h"  // the quantise stage (shared with csrc/gbdt_lossguide.hip), kThreads, Carver, add64
 #include "gbdt_sample.h"
 #include "gbdt_split.h"
@@ -97,11 +106,13 @@ struct Ws {
   int* hc;
   int* nsamp;  // [2] sampled rows: their count (k_amax_s), the compaction cursor (k_quant_s)
   Bounds bd[2];  // (constrained growth only) beside lv[2]
+  uint64_t* sset[2];  // (node sets only) beside lv[2]: every node's path set, words = ceil(f / 64) each
+  uint8_t* nmask;     // (node sets only) [2^(max_depth - 1), f] the current level's masks, a row per node of lv
   size_t bytes;
   Quant quant() const { return Quant{qg, qh, perm[0], amax, exps, nsamp, lv[0].qg, lv[0].qh, lv[0].end}; }
 };
 
-Ws carve(void* base, long n, int f, int max_depth, int hsize, bool mono = false) {
+Ws carve(void* base, long n, int f, int max_depth, int hsize, bool mono = false, bool nodeset = false) {
   Carver c{static_cast<char*>(base)};
   const size_t maxl = (size_t)1 << max_depth, maxh = max_depth > 0 ? (size_t)1 << (max_depth - 1) : 1;
   Ws w;
@@ -137,6 +148,8 @@ Ws carve(void* base, long n, int f, int max_depth, int hsize, bool mono = false)
     w.bd[i].lo = mono ? c.take<double>(maxl) : nullptr;
     w.bd[i].hi = mono ? c.take<double>(maxl) : nullptr;
   }
+  for (int i = 0; i < 2; ++i) w.sset[i] = nodeset ? c.take<uint64_t>(maxl * mifx_ns_words(f)) : nullptr;
+  w.nmask = nodeset ? c.take<uint8_t>(maxh * f) : nullptr;
   w.bytes = c.used;
   return w;
 }
@@ -208,11 +221,13 @@ __global__ void k_init(Ws w) {
   }
 }
 
+// kPerNode (node sets): lmask holds one row of mstride bytes per node of the level, not the level's one row
+template <bool kPerNode>
 __global__ __launch_bounds__(kThreads) void k_hist(Level lv, const int* lcount, int d, const uint16_t* bins,
                                                    const int* perm, const long long* qg, const long long* qh, long n,
                                                    int f, const int* nbins, const int* hoff, int hsize, long long* hg,
                                                    long long* hh, int* hc, int rows_per_wg, int ft,
-                                                   const uint8_t* lmask) {
+                                                   const uint8_t* lmask, int mstride) {
   extern __shared__ long long smem[];
   long long* sg = smem;
   long long* sh = smem + ft * kSlots;
@@ -220,7 +235,7 @@ __global__ __launch_bounds__(kThreads) void k_hist(Level lv, const int* lcount, 
   const int cnt = min(lcount[d], 1 << d);
   const long p0 = (long)blockIdx.x * rows_per_wg, p1 = min(n, p0 + rows_per_wg);
   const int j0 = blockIdx.y * ft, nf = min(ft, f - j0), tid = threadIdx.x;
-  if (lmask) {  // (nullable) the level's feature mask: a tile without a live feature is never searched
+  if (!kPerNode && lmask) {  // (nullable) the level's feature mask: a tile without a live feature is never searched
     bool live = false;
     for (int jj = 0; jj < nf; ++jj) live |= lmask[j0 + jj] != 0;
     if (!live) return;  // uniform over the workgroup
@@ -237,6 +252,11 @@ __global__ __launch_bounds__(kThreads) void k_hist(Level lv, const int* lcount, 
     if (e - b < 2) continue;  // a leaf whatever its histogram
     const long s0 = max((long)b, p0), s1 = min((long)e, p1);
     if (s0 >= s1) continue;
+    if (kPerNode) {  // row k of lmask: the node never searches a tile none of whose features it may use
+      bool live = false;
+      for (int jj = 0; jj < nf; ++jj) live |= (lmask[(size_t)k * mstride + j0 + jj] & MIFX_NS_SPLIT) != 0;
+      if (!live) continue;
+    }
     for (int i = tid; i < nf * kSlots; i += kThreads) {
       sg[i] = 0;
       sh[i] = 0;
@@ -269,17 +289,21 @@ __global__ __launch_bounds__(kThreads) void k_hist(Level lv, const int* lcount, 
   }
 }
 
+template <bool kPerNode>
 __global__ __launch_bounds__(kThreads) void k_split(Level lv, const int* lcount, int d, int f, const int* nbins,
                                                     const int* hoff, int hsize, const long long* hg,
                                                     const long long* hh, const int* hc, const int* exps,
-                                                    MifxGbParams prm, MifxGbSplit* cand, const uint8_t* lmask) {
+                                                    MifxGbParams prm, MifxGbSplit* cand, const uint8_t* lmask,
+                                                    int mstride) {
   const long wave = (blockIdx.x * (long)kThreads + threadIdx.x) >> 6;
   const int lane = threadIdx.x & 63;
   const int cnt = min(lcount[d], 1 << d);
   const int k = (int)(wave / f), j = (int)(wave % f);
   if (k >= cnt) return;  // uniform over the wave
   MifxGbSplit bs = mifx_gb_no_split();
-  if (lv.end[k] - lv.begin[k] >= 2 && (!lmask || lmask[j])) {  // a masked feature yields no candidate at this level
+  // a masked feature yields no candidate: lmask is the level's row, or (kPerNode) holds a row of mstride bytes per node
+  const bool open = kPerNode ? (lmask[(size_t)k * mstride + j] & MIFX_NS_SPLIT) != 0 : !lmask || lmask[j];
+  if (lv.end[k] - lv.begin[k] >= 2 && open) {
     const int nb = min(nbins[j], kMaxBins);
     const size_t o = (size_t)k * hsize + hoff[j];
     const long long *g0 = hg + o, *h0 = hh + o;
@@ -322,9 +346,20 @@ __global__ __launch_bounds__(kThreads) void k_split(Level lv, const int* lcount,
   if (lane == 0) cand[(size_t)k * f + j] = bs;
 }
 
+// node sets (gbdt_nodeset.h): the path sets of split k's children, nS rows 2 s and 2 s + 1, are the parent's S row k
+// (empty at the root, whose row is never written) with the split feature's bit set. nS null: the grower keeps no sets.
+__device__ __forceinline__ void child_sets(const uint64_t* S, uint64_t* nS, int words, int d, int k, int s, int feat) {
+  for (int w = 0; w < words; ++w) {
+    const uint64_t v = (d ? S[(size_t)k * words + w] : 0) | (w == feat >> 6 ? (uint64_t)1 << (feat & 63) : 0);
+    nS[(size_t)(2 * s) * words + w] = v;
+    nS[(size_t)(2 * s + 1) * words + w] = v;
+  }
+}
+
 __global__ __launch_bounds__(kThreads) void k_decide(Level lv, Level nx, int* lcount, int d, int force_leaf, int f,
                                                      const MifxGbSplit* cand, const int* exps, MifxGbParams prm,
-                                                     Decision dec, int* cur, TreeOut t, int cap, int* ncount) {
+                                                     Decision dec, int* cur, TreeOut t, int cap, int* ncount,
+                                                     const uint64_t* S, uint64_t* nS, int words) {
   const int cnt = min(lcount[d], 1 << d);
   for (int k = threadIdx.x; k < cnt; k += kThreads) {
     MifxGbSplit best = mifx_gb_no_split();
@@ -385,6 +420,7 @@ __global__ __launch_bounds__(kThreads) void k_decide(Level lv, Level nx, int* lc
     nx.end[2 * s + 1] = e;
     nx.qg[2 * s + 1] = lv.qg[k] - dec.gl[k];
     nx.qh[2 * s + 1] = lv.qh[k] - dec.hl[k];
+    if (nS) child_sets(S, nS, words, d, k, s, dec.feat[k]);
     ++s;
   }
   lcount[d + 1] = 2 * s;
@@ -397,18 +433,20 @@ __global__ __launch_bounds__(kThreads) void k_decide(Level lv, Level nx, int* lc
 
 // one wave per (node, feature). The node, the feature, the interval and the direction are the wave's: the wave index
 // goes through readfirstlane, so they sit in scalar registers and are loaded once, not per lane.
+template <bool kPerNode>
 __global__ __launch_bounds__(kThreads) void k_split_mono(Level lv, Bounds bd, const int* lcount, int d, int f,
                                                          const int* nbins, const int* hoff, int hsize,
                                                          const long long* hg, const long long* hh, const int* hc,
                                                          const int* exps, MifxGbParams prm, MifxGbSplit* cand,
-                                                         const uint8_t* lmask, const int* mono) {
+                                                         const uint8_t* lmask, int mstride, const int* mono) {
   const long wave = (blockIdx.x * (long)kThreads + threadIdx.x) >> 6;
   const int lane = threadIdx.x & 63;
   const int cnt = min(lcount[d], 1 << d);
   const int k = __builtin_amdgcn_readfirstlane((int)(wave / f)), j = __builtin_amdgcn_readfirstlane((int)(wave % f));
   if (k >= cnt) return;  // uniform over the wave
   MifxGbSplit bs = mifx_gb_no_split();
-  if (lv.end[k] - lv.begin[k] >= 2 && (!lmask || lmask[j])) {  // a masked feature yields no candidate at this level
+  const bool open = kPerNode ? (lmask[(size_t)k * mstride + j] & MIFX_NS_SPLIT) != 0 : !lmask || lmask[j];  // as k_split
+  if (lv.end[k] - lv.begin[k] >= 2 && open) {
     const int nb = min(nbins[j], kMaxBins);
     const size_t o = (size_t)k * hsize + hoff[j];
     const double lo = d ? bd.lo[k] : -INFINITY, hi = d ? bd.hi[k] : INFINITY;
@@ -425,7 +463,8 @@ __global__ __launch_bounds__(kThreads) void k_split_mono(Level lv, Bounds bd, co
 __global__ __launch_bounds__(kThreads) void k_decide_mono(Level lv, Level nx, Bounds bd, Bounds nbd, int* lcount, int d,
                                                           int force_leaf, int f, const MifxGbSplit* cand,
                                                           const int* exps, MifxGbParams prm, Decision dec, int* cur,
-                                                          TreeOut t, int cap, int* ncount, const int* mono) {
+                                                          TreeOut t, int cap, int* ncount, const int* mono,
+                                                          const uint64_t* S, uint64_t* nS, int words) {
   __shared__ int s_place[1 << kMaxDepth];  // per node of this level: its children are nx[2 s], nx[2 s + 1]; -1: a leaf
   const int cnt = min(lcount[d], 1 << d);
   const int eg = exps[0], eh = exps[1];
@@ -507,7 +546,21 @@ __global__ __launch_bounds__(kThreads) void k_decide_mono(Level lv, Level nx, Bo
     nbd.hi[2 * s] = b[1];
     nbd.lo[2 * s + 1] = b[2];
     nbd.hi[2 * s + 1] = b[3];
+    if (nS) child_sets(S, nS, words, d, k, s, dec.feat[k]);
   }
+}
+
+// ---- node sets (interaction_constraints, colsample_bynode; the rule and the wave's work are gbdt_nodeset.h's): the
+// mask rows of level d, one wave per node, in the order of lv. Launched for the worst case 2^d nodes; the live count, the
+// nodes' tree indices (the keys of their draws) and their path sets are read on the device. S null: the root, S empty.
+__global__ __launch_bounds__(kNsWaves * 64) void k_nodeset(MifxNsSpec ns, int f, const int* lcount, int d,
+                                                           const int* id, const uint64_t* S, const uint8_t* lset,
+                                                           uint8_t* nmask) {
+  extern __shared__ uint64_t ns_hash[];
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), k = blockIdx.x * kNsWaves + wave;
+  if (k >= min(lcount[d], 1 << d)) return;  // uniform over the wave
+  nodeset_wave(ns, f, id[k], S ? S + (size_t)k * mifx_ns_words(f) : nullptr, lset, nmask + (size_t)k * f,
+               ns_hash + (size_t)wave * f, threadIdx.x & 63);
 }
 
 __global__ __launch_bounds__(kThreads) void k_partition(Level lv, const int* lcount, int d, Decision dec, int* cur,
@@ -599,7 +652,8 @@ int grow_tree(const uint16_t* bins, long n, int f, const int* nbins, const int* 
               long long ws_bytes, int* feature, int* split_bin, uint8_t* default_left, int* left, int* right,
               double* value, int* node_count, int* leaf_of_row, double* margin, int rows_per_wg, int feat_tile,
               unsigned long long seed, unsigned long long round, unsigned long long thr, const uint8_t* level_mask,
-              int margin_route, double* node_gain, double* node_cover, const int* mono, hipStream_t stream);
+              int margin_route, double* node_gain, double* node_cover, const int* mono, const MifxNsSpec* ns,
+              hipStream_t stream);
 
 }  // namespace
 
@@ -668,7 +722,8 @@ int mifx_gbdt_gpu_grow_stats(const uint16_t* bins, long n, int f, const int* nbi
                              int margin_route, double* node_gain, double* node_cover, hipStream_t stream) {
   return grow_tree(bins, n, f, nbins, hoff, hsize, g, h, max_depth, min_child_weight, lambda, gamma, eta, ws, ws_bytes,
                    feature, split_bin, default_left, left, right, value, node_count, leaf_of_row, margin, rows_per_wg,
-                   feat_tile, seed, round, thr, level_mask, margin_route, node_gain, node_cover, nullptr, stream);
+                   feat_tile, seed, round, thr, level_mask, margin_route, node_gain, node_cover, nullptr, nullptr,
+                   stream);
 }
 
 // mifx_gbdt_gpu_grow_stats under monotone_constraints: mono (device) [f] ints in {-1, 0, +1}, the rule of gbdt_split.h;
@@ -685,7 +740,38 @@ int mifx_gbdt_gpu_grow_mono(const uint16_t* bins, long n, int f, const int* nbin
   if (!mono) return -1;
   return grow_tree(bins, n, f, nbins, hoff, hsize, g, h, max_depth, min_child_weight, lambda, gamma, eta, ws, ws_bytes,
                    feature, split_bin, default_left, left, right, value, node_count, leaf_of_row, margin, rows_per_wg,
-                   feat_tile, seed, round, thr, level_mask, margin_route, node_gain, node_cover, mono, stream);
+                   feat_tile, seed, round, thr, level_mask, margin_route, node_gain, node_cover, mono, nullptr, stream);
+}
+
+// the workspace of mifx_gbdt_gpu_grow_nodeset: the (mono: constrained) layout, then the two tables of path sets and the
+// level's mask rows. -1 as above, and for colsample_bynode's limit on f see mifx_gbdt_gpu_nodeset_max_draw_features.
+long long mifx_gbdt_gpu_ws_bytes_nodeset(long n, int f, int max_depth, int hsize, int mono) {
+  if (mifx_gbdt_gpu_ws_bytes(n, f, max_depth, hsize) < 0) return -1;
+  return (long long)carve(nullptr, n, f, max_depth, hsize, mono != 0, true).bytes;
+}
+
+int mifx_gbdt_gpu_nodeset_max_draw_features() { return kNsMaxDrawFeat; }
+
+// mifx_gbdt_gpu_grow_stats / mifx_gbdt_gpu_grow_mono (mono nullable) with per-node feature sets, the rule of
+// gbdt_nodeset.h: groups (device, nullable) [n_groups, ceil(f / 64)] uint64 bitsets are the interaction_constraints,
+// bynode the colsample_bynode rate (1.0: no draw; < 1 needs f <= mifx_gbdt_gpu_nodeset_max_draw_features()), keyed by
+// (seed, round, node index). k_nodeset makes every level's mask rows on the device (level_mask, nullable, is their
+// level set); the search, decision and histogram kernels are the same, reading one mask row per node. ws holds
+// mifx_gbdt_gpu_ws_bytes_nodeset bytes. The host twin is mifx_gbdt_grow_nodeset with fixed = 1.
+int mifx_gbdt_gpu_grow_nodeset(const uint16_t* bins, long n, int f, const int* nbins, const int* hoff, int hsize,
+                               const float* g, const float* h, int max_depth, double min_child_weight, double lambda,
+                               double gamma, double eta, void* ws, long long ws_bytes, int* feature, int* split_bin,
+                               uint8_t* default_left, int* left, int* right, double* value, int* node_count,
+                               int* leaf_of_row, double* margin, int rows_per_wg, int feat_tile,
+                               unsigned long long seed, unsigned long long round, unsigned long long thr,
+                               const uint8_t* level_mask, int margin_route, double* node_gain, double* node_cover,
+                               const int* mono, const uint64_t* groups, int n_groups, double bynode,
+                               hipStream_t stream) {
+  if (!(bynode > 0.0 && bynode <= 1.0) || (groups && n_groups < 1) || (bynode < 1.0 && f > kNsMaxDrawFeat)) return -1;
+  const MifxNsSpec ns{groups, groups ? n_groups : 0, bynode, seed, round};
+  return grow_tree(bins, n, f, nbins, hoff, hsize, g, h, max_depth, min_child_weight, lambda, gamma, eta, ws, ws_bytes,
+                   feature, split_bin, default_left, left, right, value, node_count, leaf_of_row, margin, rows_per_wg,
+                   feat_tile, seed, round, thr, level_mask, margin_route, node_gain, node_cover, mono, &ns, stream);
 }
 
 }  // extern "C"
@@ -697,15 +783,23 @@ int grow_tree(const uint16_t* bins, long n, int f, const int* nbins, const int* 
               long long ws_bytes, int* feature, int* split_bin, uint8_t* default_left, int* left, int* right,
               double* value, int* node_count, int* leaf_of_row, double* margin, int rows_per_wg, int feat_tile,
               unsigned long long seed, unsigned long long round, unsigned long long thr, const uint8_t* level_mask,
-              int margin_route, double* node_gain, double* node_cover, const int* mono, hipStream_t stream) {
+              int margin_route, double* node_gain, double* node_cover, const int* mono, const MifxNsSpec* ns,
+              hipStream_t stream) {
   if ((node_gain == nullptr) != (node_cover == nullptr)) return -1;
-  const long long need = mono ? mifx_gbdt_gpu_ws_bytes_mono(n, f, max_depth, hsize)
-                              : mifx_gbdt_gpu_ws_bytes(n, f, max_depth, hsize);
+  const long long need = ns     ? mifx_gbdt_gpu_ws_bytes_nodeset(n, f, max_depth, hsize, mono != nullptr)
+                         : mono ? mifx_gbdt_gpu_ws_bytes_mono(n, f, max_depth, hsize)
+                                : mifx_gbdt_gpu_ws_bytes(n, f, max_depth, hsize);
   if (need < 0 || ws_bytes < need || rows_per_wg < 1 || feat_tile < 1 || feat_tile > kMaxFeatTile) return -1;
   if (margin_route < 0 || margin_route > 1) return -1;
   const bool sampled = thr < MIFX_GS_KEEP_ALL;
   double* part_margin = sampled && margin_route == 1 ? nullptr : margin;
-  Ws w = carve(ws, n, f, max_depth, hsize, mono != nullptr);
+  Ws w = carve(ws, n, f, max_depth, hsize, mono != nullptr, ns != nullptr);
+  const int words = mifx_ns_words(f);
+  // the masks of level d (S null: the root's), made on the device once the level's nodes are known
+  auto node_sets = [&](int d, const Level& lv, const uint64_t* S) {
+    k_nodeset<<<((1u << d) + kNsWaves - 1) / kNsWaves, kNsWaves * 64, ns_lds_bytes(*ns, f, kNsWaves), stream>>>(
+        *ns, f, w.lcount, d, lv.id, S, level_mask ? level_mask + (size_t)d * f : nullptr, w.nmask);
+  };
   const MifxGbParams prm{lambda, gamma, min_child_weight, eta};
   const TreeOut t{feature, split_bin, default_left, left, right, value, node_gain, node_cover};
   const int cap = 1 << (max_depth + 1);
@@ -714,32 +808,38 @@ int grow_tree(const uint16_t* bins, long n, int f, const int* nbins, const int* 
   const unsigned row_blocks = (unsigned)((n + kThreads - 1) / kThreads);
   const dim3 hist_grid((unsigned)((n + rows_per_wg - 1) / rows_per_wg), (unsigned)((f + feat_tile - 1) / feat_tile));
   const size_t lds = (size_t)feat_tile * kSlots * (2 * sizeof(long long) + sizeof(int));
+  if (ns && max_depth > 0) node_sets(0, w.lv[0], nullptr);
   for (int d = 0; d <= max_depth; ++d) {
     Level &lv = w.lv[d & 1], &nx = w.lv[(d + 1) & 1];
+    uint64_t *S = w.sset[d & 1], *nS = w.sset[(d + 1) & 1];
     if (d < max_depth) {
-      const uint8_t* lmask = level_mask ? level_mask + (size_t)d * f : nullptr;
+      const uint8_t* lmask = ns ? w.nmask : level_mask ? level_mask + (size_t)d * f : nullptr;
+      const int mstride = ns ? f : 0;
       const size_t cells = ((size_t)1 << d) * hsize;
       hipError_t e = hipMemsetAsync(w.hg, 0, cells * sizeof(long long), stream);
       if (e == hipSuccess) e = hipMemsetAsync(w.hh, 0, cells * sizeof(long long), stream);
       if (e == hipSuccess) e = hipMemsetAsync(w.hc, 0, cells * sizeof(int), stream);
       if (e != hipSuccess) return (int)e;
-      k_hist<<<hist_grid, kThreads, lds, stream>>>(lv, w.lcount, d, bins, w.perm[d & 1], w.qg, w.qh, n, f, nbins, hoff,
-                                                   hsize, w.hg, w.hh, w.hc, rows_per_wg, feat_tile, lmask);
+      (ns ? k_hist<true> : k_hist<false>)<<<hist_grid, kThreads, lds, stream>>>(
+          lv, w.lcount, d, bins, w.perm[d & 1], w.qg, w.qh, n, f, nbins, hoff, hsize, w.hg, w.hh, w.hc, rows_per_wg,
+          feat_tile, lmask, mstride);
       const long waves = ((long)1 << d) * f;
       if (mono)
-        k_split_mono<<<(unsigned)((waves + 3) / 4), kThreads, 0, stream>>>(lv, w.bd[d & 1], w.lcount, d, f, nbins, hoff,
-                                                                           hsize, w.hg, w.hh, w.hc, w.exps, prm, w.cand,
-                                                                           lmask, mono);
+        (ns ? k_split_mono<true> : k_split_mono<false>)<<<(unsigned)((waves + 3) / 4), kThreads, 0, stream>>>(
+            lv, w.bd[d & 1], w.lcount, d, f, nbins, hoff, hsize, w.hg, w.hh, w.hc, w.exps, prm, w.cand, lmask, mstride,
+            mono);
       else
-        k_split<<<(unsigned)((waves + 3) / 4), kThreads, 0, stream>>>(lv, w.lcount, d, f, nbins, hoff, hsize, w.hg,
-                                                                      w.hh, w.hc, w.exps, prm, w.cand, lmask);
+        (ns ? k_split<true> : k_split<false>)<<<(unsigned)((waves + 3) / 4), kThreads, 0, stream>>>(
+            lv, w.lcount, d, f, nbins, hoff, hsize, w.hg, w.hh, w.hc, w.exps, prm, w.cand, lmask, mstride);
     }
     if (mono)
       k_decide_mono<<<1, kThreads, 0, stream>>>(lv, nx, w.bd[d & 1], w.bd[(d + 1) & 1], w.lcount, d, d == max_depth, f,
-                                                w.cand, w.exps, prm, w.dec, w.cur, t, cap, w.ncount, mono);
+                                                w.cand, w.exps, prm, w.dec, w.cur, t, cap, w.ncount, mono, S, nS,
+                                                words);
     else
       k_decide<<<1, kThreads, 0, stream>>>(lv, nx, w.lcount, d, d == max_depth, f, w.cand, w.exps, prm, w.dec, w.cur,
-                                           t, cap, w.ncount);
+                                           t, cap, w.ncount, S, nS, words);
+    if (ns && d + 1 < max_depth) node_sets(d + 1, nx, nS);
     k_partition<<<row_blocks, kThreads, 0, stream>>>(lv, w.lcount, d, w.dec, w.cur, bins, nbins, n, f, w.perm[d & 1],
                                                      w.perm[(d + 1) & 1], leaf_of_row, part_margin);
     const hipError_t e = hipGetLastError();

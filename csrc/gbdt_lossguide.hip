@@ -41,11 +41,18 @@
 // monotone_constraints (mifx_gbdt_lg_grow_mono; the rule is gbdt_split.h's, the host twin
 // mifx_gbdt_grow_fixed_lossguide_mono): the node table holds every node's weight interval (two doubles more per node);
 // k_root and k_pick write it and clamp the leaf entries, k_split_mono takes k_split's place.
+//
+// interaction_constraints / colsample_bynode (mifx_gbdt_lg_grow_nodeset; the rule is gbdt_nodeset.h's, the host twin
+// mifx_gbdt_grow_lossguide_nodeset): the node table holds every node's path set and mask row; k_root and k_pick write
+// the sets, k_nodeset (a wave per child) the rows. A row has two bits per feature: the histogram set (the level set and
+// A(S): it only shrinks down the tree, so the parent's slot serves the larger child by subtraction) decides what k_hist
+// builds and what k_split stages and subtracts, the split set (the by-node draw too) what a wave searches.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <algorithm>
 
+#include "gbdt_nodeset.h"
 #include "gbdt_quant.h"
 #include "gbdt_sample.h"
 #include "gbdt_split.h"
@@ -76,6 +83,8 @@ struct Nodes {
   long long *qg, *qh;
   MifxGbSplit* cand;
   double *lo, *hi;  // monotone_constraints: the node's weight interval (null in an unconstrained tree)
+  uint64_t* sset;   // node sets (gbdt_nodeset.h): the node's path set, words = ceil(f / 64) per node (null without)
+  uint8_t* nmask;   // node sets: the node's mask row [f], made by k_nodeset before the node's histogram and search
 };
 
 struct Ws {
@@ -91,7 +100,7 @@ struct Ws {
   Quant quant() const { return Quant{qg, qh, perm[0], amax, exps, nsamp, nd.qg, nd.qh, nd.end}; }
 };
 
-Ws carve(void* base, long n, int f, int max_leaves, int hsize, bool mono = false) {
+Ws carve(void* base, long n, int f, int max_leaves, int hsize, bool mono = false, bool nodeset = false) {
   Carver c{static_cast<char*>(base)};
   const size_t cap = 2 * (size_t)max_leaves - 1, pool = (size_t)max_leaves * hsize;
   Ws w;
@@ -118,6 +127,8 @@ Ws carve(void* base, long n, int f, int max_leaves, int hsize, bool mono = false
   w.hc = c.take<int>(pool);
   w.nd.lo = mono ? c.take<double>(cap) : nullptr;  // after everything the unconstrained grower lays out
   w.nd.hi = mono ? c.take<double>(cap) : nullptr;
+  w.nd.sset = nodeset ? c.take<uint64_t>(cap * mifx_ns_words(f)) : nullptr;
+  w.nd.nmask = nodeset ? c.take<uint8_t>(cap * f) : nullptr;
   w.bytes = c.used;
   return w;
 }
@@ -157,8 +168,11 @@ __device__ void zero_slot(const Ws& w, int slot, int hsize) {
 }
 
 // after the quantise stage (which left the root's sums and its row count in the table): node 0
-__global__ __launch_bounds__(kThreads) void k_root(Ws w, TreeOut t, MifxGbParams prm, int max_leaves, int hsize) {
+__global__ __launch_bounds__(kThreads) void k_root(Ws w, TreeOut t, MifxGbParams prm, int max_leaves, int hsize,
+                                                   int words) {
   const bool grow = w.nd.end[0] >= 2 && max_leaves >= 2;  // (read before thread 0 writes anything but the entry)
+  if (w.nd.sset)  // the root's path set is empty
+    for (int i = threadIdx.x; i < words; i += kThreads) w.nd.sset[i] = 0;
   if (threadIdx.x == 0) {
     w.nd.begin[0] = 0;
     w.nd.side[0] = 0;
@@ -179,9 +193,10 @@ __global__ __launch_bounds__(kThreads) void k_root(Ws w, TreeOut t, MifxGbParams
   if (grow) zero_slot(w, 0, hsize);
 }
 
-// mono (nullable): the constraint vector; the children then inherit their intervals here, before their leaf entries
+// mono (nullable): the constraint vector; the children then inherit their intervals here, before their leaf entries.
+// With node sets both children's path sets are the parent's with the split feature's bit set (words per node).
 __global__ __launch_bounds__(kThreads) void k_pick(Ws w, TreeOut t, MifxGbParams prm, int max_depth, int max_leaves,
-                                                   int hsize, const int* mono) {
+                                                   int hsize, const int* mono, int words) {
   __shared__ double s_gain[kWaves];
   __shared__ int s_id[kWaves], s_fresh;
   int* ctrl = w.ctrl;
@@ -230,6 +245,10 @@ __global__ __launch_bounds__(kThreads) void k_pick(Ws w, TreeOut t, MifxGbParams
       for (int s = 0; s < 2; ++s) {
         const int k = li + s;
         if (mono) w.nd.lo[k] = bd[2 * s], w.nd.hi[k] = bd[2 * s + 1];
+        if (w.nd.sset)
+          for (int i = 0; i < words; ++i)
+            w.nd.sset[(size_t)k * words + i] =
+                w.nd.sset[(size_t)p * words + i] | (i == c.feature >> 6 ? (uint64_t)1 << (c.feature & 63) : 0);
         w.nd.begin[k] = s ? mid : b;
         w.nd.end[k] = s ? e : mid;
         w.nd.side[k] = 1 - w.nd.side[p];
@@ -296,6 +315,8 @@ __global__ __launch_bounds__(kThreads) void k_part(Ws w, TreeOut t, const uint16
   }
 }
 
+// kPerNode (node sets): the masks are the nodes' own rows (w.nd.nmask), not the tree's one row
+template <bool kPerNode>
 __global__ __launch_bounds__(kThreads) void k_hist(Ws w, const uint16_t* bins, long n, int f, const int* nbins,
                                                    const int* hoff, int hsize, int rows_per_wg, int ft,
                                                    const uint8_t* mask) {
@@ -309,7 +330,11 @@ __global__ __launch_bounds__(kThreads) void k_hist(Ws w, const uint16_t* bins, l
   const long first = b + (long)blockIdx.x * rows_per_wg, stride = (long)gridDim.x * rows_per_wg;
   if (first >= e) return;  // uniform over the workgroup
   const int j0 = blockIdx.y * ft, nf = min(ft, f - j0), tid = threadIdx.x;
-  if (mask) {  // (nullable) the tree's feature mask: a tile without a live feature is never searched
+  if (kPerNode) {  // the tile holds nothing that the node's histogram keeps (its larger sibling keeps the same set)
+    bool live = false;
+    for (int jj = 0; jj < nf; ++jj) live |= (w.nd.nmask[(size_t)k * f + j0 + jj] & MIFX_NS_HIST) != 0;
+    if (!live) return;
+  } else if (mask) {  // (nullable) the tree's feature mask: a tile without a live feature is never searched
     bool live = false;
     for (int jj = 0; jj < nf; ++jj) live |= mask[j0 + jj] != 0;
     if (!live) return;
@@ -349,6 +374,7 @@ __global__ __launch_bounds__(kThreads) void k_hist(Ws w, const uint16_t* bins, l
 }
 
 // workgroup 0: the smaller child (or the root), workgroup 1: the larger one
+template <bool kPerNode>
 __global__ __launch_bounds__(kSplitWaves * 64) void k_split(Ws w, int f, const int* nbins, const int* hoff, int hsize,
                                                             MifxGbParams prm, const uint8_t* mask) {
   __shared__ long long s_g[kSplitWaves][kSlots], s_h[kSplitWaves][kSlots];
@@ -368,7 +394,11 @@ __global__ __launch_bounds__(kSplitWaves * 64) void k_split(Ws w, int f, const i
   int* c0 = s_c[wave];
   for (int jb = 0; jb < f; jb += kSplitWaves) {  // every thread takes every trip: the barriers are uniform
     const int j = jb + wave;
-    const bool live = scan && j < f && (!mask || mask[j]);  // uniform over the wave
+    // uniform over the wave. With node sets `live` is "the histogram holds the feature" (staged, and subtracted for the
+    // larger child, whose descendants may draw it) and `search` "this node may split on it"; without, they are one.
+    const int nm = kPerNode && j < f ? w.nd.nmask[(size_t)k * f + j] : MIFX_NS_HIST | MIFX_NS_SPLIT;
+    const bool live = scan && j < f && (kPerNode ? (nm & MIFX_NS_HIST) != 0 : !mask || mask[j]);
+    const bool search = live && (nm & MIFX_NS_SPLIT);
     const int nb = live ? min(nbins[j], kMaxBins) : 0;
     if (live)
       for (int s = lane; s <= nb; s += 64) {
@@ -386,7 +416,7 @@ __global__ __launch_bounds__(kSplitWaves * 64) void k_split(Ws w, int f, const i
         c0[s] = c;
       }
     __syncthreads();
-    if (live) {
+    if (search) {
       MifxGbSplit bs = mifx_gb_no_split();
       const int b0 = lane * 4;  // 64 lanes x 4 bins = kMaxBins
       long long lg = 0, lh = 0;
@@ -436,6 +466,7 @@ __global__ __launch_bounds__(kSplitWaves * 64) void k_split(Ws w, int f, const i
 // k_split under monotone_constraints (the rule is gbdt_split.h's, the wave search gbdt_wave.h's): the same two
 // workgroups, staging and in-place subtraction; the child's interval comes from the node table (k_pick wrote it), once
 // per workgroup, and every wave searches its feature with the feature's direction.
+template <bool kPerNode>
 __global__ __launch_bounds__(kSplitWaves * 64) void k_split_mono(Ws w, int f, const int* nbins, const int* hoff,
                                                                  int hsize, MifxGbParams prm, const uint8_t* mask,
                                                                  const int* mono) {
@@ -453,7 +484,11 @@ __global__ __launch_bounds__(kSplitWaves * 64) void k_split_mono(Ws w, int f, co
   MifxGbSplit* fc = w.fcand + (size_t)blockIdx.x * f;
   for (int jb = 0; jb < f; jb += kSplitWaves) {  // every thread takes every trip: the barriers are uniform
     const int j = jb + wave;
-    const bool live = scan && j < f && (!mask || mask[j]);  // uniform over the wave
+    // uniform over the wave. With node sets `live` is "the histogram holds the feature" (staged, and subtracted for the
+    // larger child, whose descendants may draw it) and `search` "this node may split on it"; without, they are one.
+    const int nm = kPerNode && j < f ? w.nd.nmask[(size_t)k * f + j] : MIFX_NS_HIST | MIFX_NS_SPLIT;
+    const bool live = scan && j < f && (kPerNode ? (nm & MIFX_NS_HIST) != 0 : !mask || mask[j]);
+    const bool search = live && (nm & MIFX_NS_SPLIT);
     const int nb = live ? min(nbins[j], kMaxBins) : 0;
     if (live)
       for (int s = lane; s <= nb; s += 64) {
@@ -471,7 +506,7 @@ __global__ __launch_bounds__(kSplitWaves * 64) void k_split_mono(Ws w, int f, co
         s_c[wave][s] = c;
       }
     __syncthreads();
-    if (live) {
+    if (search) {
       const MifxGbSplit bs = wave_search_mono(s_g[wave], s_h[wave], s_c[wave], nb, lane, Qg, Qh, eg, eh, j, prm, mono[j],
                                               lo, hi);
       if (lane == 0) fc[j] = bs;
@@ -486,6 +521,19 @@ __global__ __launch_bounds__(kSplitWaves * 64) void k_split_mono(Ws w, int f, co
     if (mifx_gb_feature_wins(fc[j], best)) best = fc[j];
   w.nd.cand[k] = best;
   w.nd.state[k] = mifx_gb_is_leaf(best) ? CLOSED : OPEN;
+}
+
+// ---- node sets (interaction_constraints, colsample_bynode; the rule and the wave's work are gbdt_nodeset.h's): the
+// mask rows of the nodes whose histograms and candidates come next -- the root (one wave), or the expansion's two children,
+// a wave each. Nothing to do once the tree is finished or when the children were closed by k_pick. tree_set (nullable):
+// the tree's colsample_bytree set, every node's level set.
+__global__ __launch_bounds__(128) void k_nodeset(Ws w, MifxNsSpec ns, int f, const uint8_t* tree_set, int root) {
+  extern __shared__ uint64_t ns_hash[];
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (w.ctrl[C_SMALL] < 0 || (root && wave != 0)) return;  // uniform over the wave
+  const int k = root ? 0 : w.ctrl[C_NODES] - 2 + wave;
+  nodeset_wave(ns, f, k, w.nd.sset + (size_t)k * mifx_ns_words(f), tree_set, w.nd.nmask + (size_t)k * f,
+               ns_hash + (size_t)wave * f, threadIdx.x & 63);
 }
 
 // every row of a leaf: leaf_of_row and margin += value. y strides over the nodes, x over a node's rows.
@@ -540,7 +588,8 @@ int grow_tree(const uint16_t* bins, long n, int f, const int* nbins, const int* 
               double eta, void* ws, long long ws_bytes, int* feature, int* split_bin, uint8_t* default_left, int* left,
               int* right, double* value, int* node_count, int* leaf_of_row, double* margin, int rows_per_wg,
               int feat_tile, int grid_x, unsigned long long seed, unsigned long long round, unsigned long long thr,
-              const uint8_t* feature_mask, double* node_gain, double* node_cover, const int* mono, hipStream_t stream);
+              const uint8_t* feature_mask, double* node_gain, double* node_cover, const int* mono,
+              const MifxNsSpec* ns, hipStream_t stream);
 
 }  // namespace
 
@@ -590,7 +639,7 @@ int mifx_gbdt_lg_grow(const uint16_t* bins, long n, int f, const int* nbins, con
   return grow_tree(bins, n, f, nbins, hoff, hsize, g, h, max_depth, max_leaves, min_child_weight, lambda, gamma, eta, ws,
                    ws_bytes, feature, split_bin, default_left, left, right, value, node_count, leaf_of_row, margin,
                    rows_per_wg, feat_tile, grid_x, seed, round, thr, feature_mask, node_gain, node_cover, nullptr,
-                   stream);
+                   nullptr, stream);
 }
 
 // mifx_gbdt_lg_grow under monotone_constraints: mono (device) [f] ints in {-1, 0, +1}, the rule of gbdt_split.h; ws
@@ -607,7 +656,37 @@ int mifx_gbdt_lg_grow_mono(const uint16_t* bins, long n, int f, const int* nbins
   if (!mono) return -1;
   return grow_tree(bins, n, f, nbins, hoff, hsize, g, h, max_depth, max_leaves, min_child_weight, lambda, gamma, eta, ws,
                    ws_bytes, feature, split_bin, default_left, left, right, value, node_count, leaf_of_row, margin,
-                   rows_per_wg, feat_tile, grid_x, seed, round, thr, feature_mask, node_gain, node_cover, mono, stream);
+                   rows_per_wg, feat_tile, grid_x, seed, round, thr, feature_mask, node_gain, node_cover, mono, nullptr,
+                   stream);
+}
+
+// the workspace of mifx_gbdt_lg_grow_nodeset: the (mono: constrained) layout, then per node its path set
+// (ceil(f / 64) * 8 bytes) and its mask row (f bytes)
+long long mifx_gbdt_lg_ws_bytes_nodeset(long n, int f, int max_leaves, int hsize, int mono) {
+  if (mifx_gbdt_lg_ws_bytes(n, f, max_leaves, hsize) < 0) return -1;
+  return (long long)carve(nullptr, n, f, max_leaves, hsize, mono != 0, true).bytes;
+}
+
+// mifx_gbdt_lg_grow / mifx_gbdt_lg_grow_mono (mono nullable) with per-node feature sets, the rule of gbdt_nodeset.h:
+// groups (device, nullable) [n_groups, ceil(f / 64)] uint64 bitsets, bynode the colsample_bynode rate (1.0: no draw;
+// < 1 needs f <= 2048), keyed by (seed, round, node id). k_pick hands the children their path sets, k_nodeset makes
+// their mask rows (feature_mask, nullable, is every node's level set); k_hist skips the tiles outside the smaller
+// child's histogram set and the split kernels search the split set only. ws holds mifx_gbdt_lg_ws_bytes_nodeset bytes.
+// The host twin is mifx_gbdt_grow_lossguide_nodeset with fixed = 1.
+int mifx_gbdt_lg_grow_nodeset(const uint16_t* bins, long n, int f, const int* nbins, const int* hoff, int hsize,
+                              const float* g, const float* h, int max_depth, int max_leaves, double min_child_weight,
+                              double lambda, double gamma, double eta, void* ws, long long ws_bytes, int* feature,
+                              int* split_bin, uint8_t* default_left, int* left, int* right, double* value,
+                              int* node_count, int* leaf_of_row, double* margin, int rows_per_wg, int feat_tile,
+                              int grid_x, unsigned long long seed, unsigned long long round, unsigned long long thr,
+                              const uint8_t* feature_mask, double* node_gain, double* node_cover, const int* mono,
+                              const uint64_t* groups, int n_groups, double bynode, hipStream_t stream) {
+  if (!(bynode > 0.0 && bynode <= 1.0) || (groups && n_groups < 1) || (bynode < 1.0 && f > kNsMaxDrawFeat)) return -1;
+  const MifxNsSpec ns{groups, groups ? n_groups : 0, bynode, seed, round};
+  return grow_tree(bins, n, f, nbins, hoff, hsize, g, h, max_depth, max_leaves, min_child_weight, lambda, gamma, eta, ws,
+                   ws_bytes, feature, split_bin, default_left, left, right, value, node_count, leaf_of_row, margin,
+                   rows_per_wg, feat_tile, grid_x, seed, round, thr, feature_mask, node_gain, node_cover, mono, &ns,
+                   stream);
 }
 
 }  // extern "C"
@@ -619,13 +698,16 @@ int grow_tree(const uint16_t* bins, long n, int f, const int* nbins, const int* 
               double eta, void* ws, long long ws_bytes, int* feature, int* split_bin, uint8_t* default_left, int* left,
               int* right, double* value, int* node_count, int* leaf_of_row, double* margin, int rows_per_wg,
               int feat_tile, int grid_x, unsigned long long seed, unsigned long long round, unsigned long long thr,
-              const uint8_t* feature_mask, double* node_gain, double* node_cover, const int* mono, hipStream_t stream) {
+              const uint8_t* feature_mask, double* node_gain, double* node_cover, const int* mono,
+              const MifxNsSpec* ns, hipStream_t stream) {
   if ((node_gain == nullptr) != (node_cover == nullptr)) return -1;
-  const long long need = mono ? mifx_gbdt_lg_ws_bytes_mono(n, f, max_leaves, hsize)
-                              : mifx_gbdt_lg_ws_bytes(n, f, max_leaves, hsize);
+  const long long need = ns     ? mifx_gbdt_lg_ws_bytes_nodeset(n, f, max_leaves, hsize, mono != nullptr)
+                         : mono ? mifx_gbdt_lg_ws_bytes_mono(n, f, max_leaves, hsize)
+                                : mifx_gbdt_lg_ws_bytes(n, f, max_leaves, hsize);
   if (need < 0 || ws_bytes < need || max_depth < 0 || max_depth > kMaxDepth) return -1;
   if (rows_per_wg < 1 || feat_tile < 1 || feat_tile > kMaxFeatTile || grid_x < 1 || grid_x > 65535) return -1;
-  Ws w = carve(ws, n, f, max_leaves, hsize, mono != nullptr);
+  Ws w = carve(ws, n, f, max_leaves, hsize, mono != nullptr, ns != nullptr);
+  const int words = mifx_ns_words(f);
   const MifxGbParams prm{lambda, gamma, min_child_weight, eta};
   const TreeOut t{feature, split_bin, default_left, left, right, value, node_gain, node_cover};
   const dim3 hist_grid((unsigned)std::min<long>((n + rows_per_wg - 1) / rows_per_wg, grid_x),
@@ -634,19 +716,22 @@ int grow_tree(const uint16_t* bins, long n, int f, const int* nbins, const int* 
   const unsigned part_grid = (unsigned)grid_for(n, grid_x);
   k_init<<<1, 64, 0, stream>>>(w);
   launch_quant(g, h, n, seed, round, thr, w.quant(), leaf_of_row, stream);
-  k_root<<<1, kThreads, 0, stream>>>(w, t, prm, max_leaves, hsize);
+  k_root<<<1, kThreads, 0, stream>>>(w, t, prm, max_leaves, hsize, words);
   for (int x = 0; x < max_leaves; ++x) {  // x = 0: the root's candidate; then max_leaves - 1 expansions
     if (x > 0) {
-      k_pick<<<1, kThreads, 0, stream>>>(w, t, prm, max_depth, max_leaves, hsize, mono);
+      k_pick<<<1, kThreads, 0, stream>>>(w, t, prm, max_depth, max_leaves, hsize, mono, words);
       k_part<<<part_grid, kThreads, 0, stream>>>(w, t, bins, nbins, n, f);
     }
     if (x + 1 < max_leaves) {  // the last expansion's children are never split
-      k_hist<<<hist_grid, kThreads, lds, stream>>>(w, bins, n, f, nbins, hoff, hsize, rows_per_wg, feat_tile,
-                                                   feature_mask);
+      if (ns) k_nodeset<<<1, 128, ns_lds_bytes(*ns, f, 2), stream>>>(w, *ns, f, feature_mask, x == 0);
+      (ns ? k_hist<true> : k_hist<false>)<<<hist_grid, kThreads, lds, stream>>>(w, bins, n, f, nbins, hoff, hsize,
+                                                                                 rows_per_wg, feat_tile, feature_mask);
       if (mono)
-        k_split_mono<<<2, kSplitWaves * 64, 0, stream>>>(w, f, nbins, hoff, hsize, prm, feature_mask, mono);
+        (ns ? k_split_mono<true> : k_split_mono<false>)<<<2, kSplitWaves * 64, 0, stream>>>(w, f, nbins, hoff, hsize,
+                                                                                             prm, feature_mask, mono);
       else
-        k_split<<<2, kSplitWaves * 64, 0, stream>>>(w, f, nbins, hoff, hsize, prm, feature_mask);
+        (ns ? k_split<true> : k_split<false>)<<<2, kSplitWaves * 64, 0, stream>>>(w, f, nbins, hoff, hsize, prm,
+                                                                                   feature_mask);
     }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return (int)e;

@@ -7,7 +7,9 @@ One integer-only, counter-based rule (uint64 wrap-around throughout):
 
 * rows (site 1): row i is in round t's sample iff (mix64(key + i * G) >> 32) < thr, thr = int(subsample * 2^32);
 * features (site 2 per tree over all features, site 3 + d for level d over the tree's set): of the candidates c the
-  k = max(1, int(rate * len(c))) with the smallest (mix64(key + j * G), j); a rate of 1.0 skips the draw.
+  k = max(1, int(rate * len(c))) with the smallest (mix64(key + j * G), j); a rate of 1.0 skips the draw;
+* colsample_bynode (csrc/gbdt_nodeset.h): the same choice per node from the node's level set, at site 2^32 + node, the
+  node's index in the tree arrays.
 
 The host learners use the C functions (mifx_gbdt_sample_rows, mifx_gbdt_level_mask in csrc/gbdt.cpp), the device
 hashes the rows itself; the tests hold all three to these functions."""
@@ -17,6 +19,7 @@ import numpy as np
 
 G = np.uint64(0x9E3779B97F4A7C15)
 SITE_ROWS, SITE_TREE, SITE_LEVEL0 = 1, 2, 3
+SITE_NODE0 = 1 << 32
 _M64 = (1 << 64) - 1
 
 
@@ -74,3 +77,22 @@ def level_mask(seed: int, round: int, f: int, max_depth: int, colsample_bytree: 
                                                                    tree)
         mask[d, lv] = 1
     return mask
+
+
+def group_bitsets(groups, f: int) -> np.ndarray:
+    """interaction_constraints as the uint64 [n_groups, ceil(f / 64)] table of csrc/gbdt_nodeset.h: feature j of a
+    group is bit j & 63 of word j >> 6. `groups`: a sequence of sequences of feature indices in [0, f)."""
+    table = np.zeros((len(groups), (f + 63) // 64), np.uint64)
+    for i, grp in enumerate(groups):
+        for j in grp:
+            if not 0 <= int(j) < f:
+                raise ValueError(f"interaction_constraints names feature {j} but the table has {f} features")
+            table[i, int(j) >> 6] |= np.uint64(1 << (int(j) & 63))
+    return table
+
+
+def node_mask(seed: int, round: int, node: int, level_set, rate: float) -> np.ndarray:
+    """colsample_bynode: the features (ascending indices) drawn for node `node` of round `round`'s tree from its level
+    set `level_set` (feature indices); a rate of 1.0 keeps the level set."""
+    c = np.sort(np.asarray(level_set, np.int64))
+    return c if rate >= 1.0 or not len(c) else choose_features(seed, round, SITE_NODE0 + int(node), rate, c)

@@ -37,8 +37,11 @@ still a pure function of data, parameters and `random_state` -- independent of `
 GPU model equals the host twin bit for bit. A round's tree is grown on exactly the sampled rows, as if the table held
 only them (quantisation exponents, the two-row leaf rule and row counts included); every row's margin then receives
 the tree's output. Weights are float32 and multiply the float32 gradient pair; the intercept is the weighted mean (or
-its log-odds). The eval metric stays unweighted (`sample_weight_eval_set` and `colsample_bynode` are not
-implemented). With the defaults nothing is drawn and no weight is applied: the models are the unsampled ones.
+its log-odds). The eval metric stays unweighted (`sample_weight_eval_set` is not implemented).
+`interaction_constraints` (groups of feature indices) and `colsample_bynode` give every node its own feature set, the
+rule of csrc/gbdt_nodeset.h: a node below the root may split on its path's features and on the groups that hold all of
+them, intersected with a per-node draw from its level set keyed by (random_state, tree index, node index); on the GPU
+the sets are made on the device (k_nodeset) and the model equals the fixed-point host twin bit for bit. With the defaults nothing is drawn and no weight is applied: the models are the unsampled ones.
 
 What the model used: every learner records each node's `gain` (the double it maximised,
 0.5 * (score_L + score_R - score_parent) - gamma, 0.0 at a leaf) and `cover` (the node's hessian sum, over the sampled
@@ -156,6 +159,8 @@ import sys
 
 import numpy as np
 
+from .sample import group_bitsets
+
 _D = ctypes.POINTER(ctypes.c_double)
 _F = ctypes.POINTER(ctypes.c_float)
 _I = ctypes.POINTER(ctypes.c_int)
@@ -189,6 +194,11 @@ def _lib():
         fn.argtypes = getattr(lib, f"mifx_gbdt_grow{name}_stats").argtypes + [_I]
         fn.restype = ctypes.c_int
     u64 = ctypes.c_uint64
+    for name in ("", "_lossguide"):  # fixed, the *_mono arguments (mono nullable), then groups, n_groups, rate, seed, round
+        fn = getattr(lib, f"mifx_gbdt_grow{name}_nodeset")
+        fn.argtypes = [ctypes.c_int] + getattr(lib, f"mifx_gbdt_grow{name}_mono").argtypes + \
+            [ctypes.POINTER(u64), ctypes.c_int, ctypes.c_double, u64, u64]
+        fn.restype = ctypes.c_int
     lib.mifx_gbdt_sample_rows.argtypes = [u64, u64, ctypes.c_double, ctypes.c_long, _U8]
     lib.mifx_gbdt_sample_rows.restype = ctypes.c_long
     lib.mifx_gbdt_sample_features.argtypes = [u64, u64, u64, ctypes.c_double, _U8, ctypes.c_int, _U8]
@@ -395,7 +405,7 @@ class _Base:
                  verbosity: int = 0, device: str | None = None, fixed_point: bool | None = None,
                  subsample: float = 1.0, colsample_bytree: float = 1.0, colsample_bylevel: float = 1.0,
                  importance_type: str = "gain", grow_policy: str = "depthwise", max_leaves: int = 0,
-                 monotone_constraints=None):
+                 monotone_constraints=None, interaction_constraints=None, colsample_bynode: float = 1.0):
         self.n_estimators, self.learning_rate, self.max_depth = n_estimators, learning_rate, max_depth
         self.min_child_weight, self.reg_lambda, self.gamma, self.max_bins = min_child_weight, reg_lambda, gamma, max_bins
         self.base_score, self.n_jobs = base_score, n_jobs
@@ -403,9 +413,11 @@ class _Base:
         self.subsample, self.colsample_bytree, self.colsample_bylevel = subsample, colsample_bytree, colsample_bylevel
         self.grow_policy, self.max_leaves = grow_policy, max_leaves
         self.monotone_constraints = monotone_constraints
+        self.interaction_constraints, self.colsample_bynode = interaction_constraints, colsample_bynode
         self._check_rates()
         self._check_policy()
         self._monotone(None)
+        self._nodeset(None)
         self.best_iteration, self.best_score, self.evals_result_ = None, None, {}
         self._trees: list[tuple] = []
         self._node_stats: list[tuple] = []  # per tree (gain, cover), parallel to _trees
@@ -477,6 +489,31 @@ class _Base:
             raise ValueError("monotone_constraints with reg:absoluteerror / reg:quantileerror is not implemented: the "
                              "refreshed leaf values would have to be clamped to the leaves' intervals")
         return out
+
+    def _nodeset(self, f: int | None):
+        """(groups, colsample_bynode) for the growers' node-set entries (csrc/gbdt_nodeset.h), or None when both options
+        are off (None or no groups, a rate of 1.0; a model pickled before the arguments existed): the growers then take
+        the paths they always took. groups: None or a list of lists of feature indices. f = None checks the values
+        only; with f an index >= f raises."""
+        ic, rate = getattr(self, "interaction_constraints", None), float(getattr(self, "colsample_bynode", 1.0))
+        if not 0.0 < rate <= 1.0:  # (a NaN fails too)
+            raise ValueError(f"colsample_bynode must be in (0, 1], got {rate}")
+        groups = None
+        if ic is not None:
+            if isinstance(ic, (str, bytes)) or not hasattr(ic, "__iter__"):
+                raise ValueError("interaction_constraints must be a sequence of sequences of feature indices")
+            groups = []
+            for grp in ic:
+                if isinstance(grp, (str, bytes)) or not hasattr(grp, "__iter__"):
+                    raise ValueError(f"interaction_constraints: every group is a sequence of feature indices, got {grp!r}")
+                grp = list(grp)
+                for j in grp:
+                    if isinstance(j, bool) or not isinstance(j, (int, np.integer)) or j < 0:
+                        raise ValueError(f"interaction_constraints: a feature index is a non-negative integer, got {j!r}")
+                    if f is not None and j >= f:
+                        raise ValueError(f"interaction_constraints names feature {j} but the table has {f} features")
+                groups.append([int(j) for j in grp])
+        return (groups or None, rate) if groups or rate < 1.0 else None
 
     def _seed(self) -> int:
         return int(getattr(self, "random_state", 0) or 0) & _M64
@@ -611,9 +648,10 @@ class _Base:
         -1 elsewhere; level_mask (uint8 [max_depth, f], None = all): the features each level may split on."""
         return self._grow_stats(bins, nbins, g, h, leaf_of_row, rows, level_mask)[0]
 
-    def _grow_stats(self, bins, nbins, g, h, leaf_of_row, rows=None, level_mask=None):
+    def _grow_stats(self, bins, nbins, g, h, leaf_of_row, rows=None, level_mask=None, round: int = 0):
         """(_grow's tree, (gain, cover)): the tree and its nodes' statistics (float64 [nodes] each). Under
-        grow_policy="lossguide" the tree is grown leaf-wise and level_mask is the tree's [f] feature mask."""
+        grow_policy="lossguide" the tree is grown leaf-wise and level_mask is the tree's [f] feature mask. `round`: the
+        tree's index, the key of its colsample_bynode draws."""
         n = bins.shape[1]
         lossguide, leaves = self._lossguide(), self._policy()[1]
         cap = 2 * leaves - 1 if lossguide else 2 ** (self.max_depth + 1)
@@ -623,13 +661,26 @@ class _Base:
         gain, cover = np.empty(cap, np.float64), np.empty(cap, np.float64)
         grow = _lib().mifx_gbdt_grow_fixed_stats if self._fixed() else _lib().mifx_gbdt_grow_stats
         mono = getattr(self, "_mono", None)  # fit's validated directions: the constrained entries take them last
+        ns = getattr(self, "_ns", None)  # fit's validated node-set spec: one entry per policy, after a nullable mono
         if mono is not None:
             grow = _lib().mifx_gbdt_grow_fixed_mono if self._fixed() else _lib().mifx_gbdt_grow_mono
+        if ns is not None:
+            nsfn, fixed = _lib().mifx_gbdt_grow_nodeset, int(self._fixed())
+            grow = lambda *a: nsfn(fixed, *a)  # noqa: E731
         if lossguide:
             fn = _lib().mifx_gbdt_grow_fixed_lossguide_stats if self._fixed() else _lib().mifx_gbdt_grow_lossguide_stats
             if mono is not None:
                 fn = _lib().mifx_gbdt_grow_fixed_lossguide_mono if self._fixed() else _lib().mifx_gbdt_grow_lossguide_mono
             grow = lambda *a: fn(*a[:7], leaves, *a[7:])  # noqa: E731
+            if ns is not None:
+                nsfn = _lib().mifx_gbdt_grow_lossguide_nodeset
+                grow = lambda *a: nsfn(fixed, *a[:7], leaves, *a[7:])  # noqa: E731
+        tail = () if mono is None else (_p(mono, _I),)
+        if ns is not None:  # groups as bitsets, the rate, and the draw's key: the seed and the tree index
+            table, rate = ns
+            tail = (None if mono is None else _p(mono, _I),
+                    None if table is None else _p(table, ctypes.POINTER(ctypes.c_uint64)),
+                    0 if table is None else len(table), rate, self._seed(), int(round) & _M64)
         if rows is not None:
             rows = np.ascontiguousarray(rows, np.int32)
         if level_mask is not None:
@@ -640,7 +691,7 @@ class _Base:
                    _p(sb, _I), _p(dl, _U8), _p(left, _I), _p(right, _I), _p(val, _D),
                    _p(leaf_of_row, _I), None if rows is None else _p(rows, _I), 0 if rows is None else len(rows),
                    None if level_mask is None else _p(level_mask, _U8), _p(gain, _D), _p(cover, _D),
-                   *(() if mono is None else (_p(mono, _I),)))
+                   *tail)
         if cnt < 0:
             raise RuntimeError("tree exceeded its node capacity")
         thr = np.zeros(cnt, np.float64)
@@ -669,6 +720,8 @@ class _Base:
         w = self._row_weights(self._weights(sample_weight, y), y)
         self._nfeat = X.shape[1]
         self._mono = self._monotone(self._nfeat)
+        ns = self._nodeset(self._nfeat)  # the host learners take the groups as the bitset table of csrc/gbdt_nodeset.h
+        self._ns = None if ns is None else (None if ns[0] is None else group_bitsets(ns[0], self._nfeat), ns[1])
         if gpu is not None:
             return self._fit_gpu(X, y, eval_set, early_stopping_rounds, verbose, w)
         X = np.ascontiguousarray(np.asarray(X, dtype=np.float64))
@@ -697,7 +750,7 @@ class _Base:
             g, h = g.reshape(K, -1), h.reshape(K, -1)
             for k in range(K):
                 rows, mask = self._round_draws(it * K + k, len(y), self._nfeat)
-                tree, stats = self._grow_stats(bins, nbins, g[k], h[k], leaf_of_row, rows, mask)
+                tree, stats = self._grow_stats(bins, nbins, g[k], h[k], leaf_of_row, rows, mask, it * K + k)
                 if alpha is not None:  # the leaves' exact quantiles of the residuals, before any margin moves
                     leaf_refresh(y - margin[k], np.ascontiguousarray(h[k]), leaf_of_row, tree[5], alpha,
                                  float(self.learning_rate), self._nthreads())
@@ -773,8 +826,9 @@ class _Base:
             masks = np.stack([level_mask(self._seed(), t, self._nfeat, int(self.max_depth), bytree, bylevel)
                               for t in range(rounds * K)])
         with torch.cuda.device(dev):
-            bst = G.LossguideBooster.from_device_bins(bins, nbins, int(self.max_depth), leaves, self._mono) \
-                if lossguide else G.Booster.from_device_bins(bins, nbins, int(self.max_depth), self._mono)
+            ns = self._nodeset(self._nfeat)  # the groups go up once, as a bitset table
+            bst = G.LossguideBooster.from_device_bins(bins, nbins, int(self.max_depth), leaves, self._mono, ns) \
+                if lossguide else G.Booster.from_device_bins(bins, nbins, int(self.max_depth), self._mono, ns)
             yd = torch.from_numpy(y).to(dev)
             wd = None if w is None else torch.from_numpy(w).to(dev)
             masks = None if masks is None else torch.from_numpy(masks).to(dev)

@@ -30,6 +30,7 @@ import functools
 import numpy as np
 import torch
 
+from ..gbdt.sample import group_bitsets
 from . import _lib
 from ._lib import I32, I64, VP, check, ptr, sig, stream_handle
 
@@ -62,6 +63,12 @@ def _fns():
         "grow_mono": sig(lib, "mifx_gbdt_gpu_grow_mono", [VP, LONG, I32, VP, VP, I32, VP, VP, I32, F64, F64, F64, F64,
                                                            VP, I64, VP, VP, VP, VP, VP, VP, VP, VP, VP, I32, I32, U64,
                                                            U64, U64, VP, I32, VP, VP, VP, VP]),
+        "ws_bytes_nodeset": sig(lib, "mifx_gbdt_gpu_ws_bytes_nodeset", [LONG, I32, I32, I32, I32], I64),
+        "max_draw_features": sig(lib, "mifx_gbdt_gpu_nodeset_max_draw_features", []),
+        "grow_nodeset": sig(lib, "mifx_gbdt_gpu_grow_nodeset", [VP, LONG, I32, VP, VP, I32, VP, VP, I32, F64, F64, F64,
+                                                                 F64, VP, I64, VP, VP, VP, VP, VP, VP, VP, VP, VP, I32,
+                                                                 I32, U64, U64, U64, VP, I32, VP, VP, VP, VP, I32, F64,
+                                                                 VP]),
         "apply": sig(lib, "mifx_gbdt_gpu_apply", [VP, LONG, I32, VP, VP, VP, VP, VP, VP, VP, I32, VP, VP]),
         "grad_softmax": sig(lib, "mifx_gbdt_gpu_grad_softmax", [VP, VP, VP, LONG, I32, VP, VP, VP]),
     }
@@ -82,6 +89,11 @@ def _lg_fns():
         "grow_mono": sig(lib, "mifx_gbdt_lg_grow_mono", [VP, LONG, I32, VP, VP, I32, VP, VP, I32, I32, F64, F64, F64, F64,
                                                          VP, I64, VP, VP, VP, VP, VP, VP, VP, VP, VP, I32, I32, I32, U64,
                                                          U64, U64, VP, VP, VP, VP, VP]),
+        "ws_bytes_nodeset": sig(lib, "mifx_gbdt_lg_ws_bytes_nodeset", [LONG, I32, I32, I32, I32], I64),
+        "grow_nodeset": sig(lib, "mifx_gbdt_lg_grow_nodeset", [VP, LONG, I32, VP, VP, I32, VP, VP, I32, I32, F64, F64,
+                                                               F64, F64, VP, I64, VP, VP, VP, VP, VP, VP, VP, VP, VP,
+                                                               I32, I32, I32, U64, U64, U64, VP, VP, VP, VP, VP, I32,
+                                                               F64, VP]),
         "apply": sig(lib, "mifx_gbdt_lg_apply", [VP, LONG, I32, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP]),
     }
 
@@ -231,23 +243,51 @@ class Booster:
     """Device-resident state of one fit: bins [n, f], per-feature bin counts, the grower's workspace.
 
     `monotone` (int [f] in {-1, 0, +1}, None or all zeros = unconstrained) makes every tree of this Booster a constrained
-    one (the rule of csrc/gbdt_split.h; k_split_mono / k_decide_mono): the workspace grows by two doubles per node."""
+    one (the rule of csrc/gbdt_split.h; k_split_mono / k_decide_mono): the workspace grows by two doubles per node.
 
-    def __init__(self, bins: np.ndarray, nbins: np.ndarray, max_depth: int, dev: torch.device, monotone=None):
+    `nodeset` = (groups, colsample_bynode) gives every node its own feature set (the rule of csrc/gbdt_nodeset.h;
+    k_nodeset makes the masks on the device): `groups` is None or interaction_constraints as a sequence of feature
+    index sequences, uploaded once as bitsets; the rate is in (0, 1]. (None, 1.0) or None: no node sets. The workspace
+    grows by the path sets (8 ceil(f / 64) bytes per node) and the mask rows (f bytes per node searched at once)."""
+
+    def __init__(self, bins: np.ndarray, nbins: np.ndarray, max_depth: int, dev: torch.device, monotone=None,
+                 nodeset=None):
         f, n = bins.shape
         self._set_monotone(monotone, f, dev)
+        self._set_nodeset(nodeset, f, dev)
         self._setup(n, f, nbins, max_depth, dev, lambda: upload_bins(bins, dev))
 
     @classmethod
-    def from_device_bins(cls, bins: torch.Tensor, nbins: np.ndarray, max_depth: int, monotone=None) -> "Booster":
+    def from_device_bins(cls, bins: torch.Tensor, nbins: np.ndarray, max_depth: int, monotone=None,
+                         nodeset=None) -> "Booster":
         """A Booster on bins that are on the device already: row-major [n, f] int16 (mifx.ops.gbdt_prep.device_bins),
         kept as they are."""
         if not (bins.is_cuda and bins.dim() == 2 and bins.dtype == torch.int16 and bins.is_contiguous()):
             raise ValueError("expected a contiguous [n, f] int16 tensor on the GPU")
         self = cls.__new__(cls)
         self._set_monotone(monotone, bins.shape[1], bins.device)
+        self._set_nodeset(nodeset, bins.shape[1], bins.device)
         self._setup(bins.shape[0], bins.shape[1], nbins, max_depth, bins.device, lambda: bins)
         return self
+
+    def _set_nodeset(self, nodeset, f: int, dev: torch.device) -> None:
+        """self.ns: None, or (groups table on the device or None, group count, rate) for the *_nodeset entries."""
+        self.ns = None
+        groups, rate = nodeset if nodeset is not None else (None, 1.0)
+        rate = float(rate)
+        if not 0.0 < rate <= 1.0:
+            raise ValueError(f"colsample_bynode must be in (0, 1], got {rate}")
+        if not groups and rate == 1.0:
+            return
+        if rate < 1.0 and f > _fns()["max_draw_features"]():
+            raise ValueError(f"device='gpu' supports colsample_bynode < 1 for up to {_fns()['max_draw_features']()} "
+                             f"features, got {f}")
+        table = torch.from_numpy(group_bitsets(groups, f).view(np.int64)).to(dev) if groups else None
+        self.ns = (table, len(groups) if groups else 0, rate)
+
+    def _nodeset_args(self):
+        table, count, rate = self.ns
+        return ptr(self.mono), ptr(table), count, rate
 
     def _set_monotone(self, monotone, f: int, dev: torch.device) -> None:
         """self.mono: the directions as an int32 [f] tensor on the device, or None for an unconstrained Booster."""
@@ -263,7 +303,10 @@ class Booster:
         check_limits(n, int(np.max(nbins)), max_depth)
         self._setup_data(n, f, nbins, max_depth, dev, device_bins)
         self.cap = 2 ** (self.max_depth + 1)
-        nbytes = _fns()["ws_bytes" if self.mono is None else "ws_bytes_mono"](n, f, self.max_depth, self.hsize)
+        if self.ns is not None:
+            nbytes = _fns()["ws_bytes_nodeset"](n, f, self.max_depth, self.hsize, int(self.mono is not None))
+        else:
+            nbytes = _fns()["ws_bytes" if self.mono is None else "ws_bytes_mono"](n, f, self.max_depth, self.hsize)
         if nbytes < 0:
             raise ValueError("shape outside the device learner's limits")
         self.ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
@@ -321,6 +364,19 @@ class Booster:
                       and tuple(level_mask.shape) == (self.max_depth, self.f)):
                 raise ValueError(f"level_mask must be a contiguous uint8 [{self.max_depth}, {self.f}] tensor on "
                                  f"{self.dev}")
+        if self.ns is not None:  # per-node feature sets: one entry, monotone or not, statistics or not
+            gain, cover = stats if stats is not None else (None, None)
+            for s in (gain, cover):
+                assert s is None or (s.dtype == torch.float64 and s.is_contiguous() and s.numel() == self.cap)
+            check(_fns()["grow_nodeset"](ptr(self.bins), self.n, self.f, ptr(self.nbins), ptr(self.hoff), self.hsize,
+                                         ptr(g), ptr(h), self.max_depth, float(min_child_weight), float(reg_lambda),
+                                         float(gamma), float(eta), ptr(self.ws), self.ws.numel(), ptr(fe), ptr(sb),
+                                         ptr(dl), ptr(le), ptr(ri), ptr(val), ptr(cnt), ptr(self.leaf_of_row),
+                                         ptr(margin), rows, tile, int(seed) & (2 ** 64 - 1),
+                                         int(round) & (2 ** 64 - 1), thr, ptr(level_mask), int(_margin_route),
+                                         ptr(gain), ptr(cover), *self._nodeset_args(), stream_handle(self.dev)),
+                  "mifx_gbdt_gpu_grow_nodeset")
+            return
         if self.mono is not None:  # the constrained grower: one entry, statistics or not
             gain, cover = stats if stats is not None else (None, None)
             for s in (gain, cover):
@@ -382,19 +438,22 @@ class LossguideBooster(Booster):
     expansion's per-feature candidates, and the pool of max_leaves histograms (int64 g, int64 h, int32 rows)."""
 
     def __init__(self, bins: np.ndarray, nbins: np.ndarray, max_depth: int, max_leaves: int, dev: torch.device,
-                 monotone=None):
+                 monotone=None, nodeset=None):
         f, n = bins.shape
         self.max_leaves = int(max_leaves)
         self._set_monotone(monotone, f, dev)
+        self._set_nodeset(nodeset, f, dev)
         self._setup(n, f, nbins, max_depth, dev, lambda: upload_bins(bins, dev))
 
     @classmethod
-    def from_device_bins(cls, bins: torch.Tensor, nbins: np.ndarray, max_depth: int, max_leaves: int, monotone=None):
+    def from_device_bins(cls, bins: torch.Tensor, nbins: np.ndarray, max_depth: int, max_leaves: int, monotone=None,
+                         nodeset=None):
         if not (bins.is_cuda and bins.dim() == 2 and bins.dtype == torch.int16 and bins.is_contiguous()):
             raise ValueError("expected a contiguous [n, f] int16 tensor on the GPU")
         self = cls.__new__(cls)
         self.max_leaves = int(max_leaves)
         self._set_monotone(monotone, bins.shape[1], bins.device)
+        self._set_nodeset(nodeset, bins.shape[1], bins.device)
         self._setup(bins.shape[0], bins.shape[1], nbins, max_depth, bins.device, lambda: bins)
         return self
 
@@ -402,7 +461,10 @@ class LossguideBooster(Booster):
         check_limits_lossguide(n, int(np.max(nbins)), int(max_depth), self.max_leaves)
         self._setup_data(n, f, nbins, max_depth, dev, device_bins)
         self.cap = 2 * self.max_leaves - 1
-        nbytes = _lg_fns()["ws_bytes" if self.mono is None else "ws_bytes_mono"](n, f, self.max_leaves, self.hsize)
+        if self.ns is not None:
+            nbytes = _lg_fns()["ws_bytes_nodeset"](n, f, self.max_leaves, self.hsize, int(self.mono is not None))
+        else:
+            nbytes = _lg_fns()["ws_bytes" if self.mono is None else "ws_bytes_mono"](n, f, self.max_leaves, self.hsize)
         if nbytes < 0:
             raise ValueError("shape outside the device learner's limits")
         self.ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
@@ -436,6 +498,10 @@ class LossguideBooster(Booster):
                 ptr(self.ws), self.ws.numel(), ptr(fe), ptr(sb), ptr(dl), ptr(le), ptr(ri), ptr(val), ptr(cnt),
                 ptr(self.leaf_of_row), ptr(margin), rows, tile, gx, int(seed) & m64, int(round) & m64,
                 row_threshold(subsample), ptr(feature_mask), ptr(gain), ptr(cover))
+        if self.ns is not None:
+            check(_lg_fns()["grow_nodeset"](*args, *self._nodeset_args(), stream_handle(self.dev)),
+                  "mifx_gbdt_lg_grow_nodeset")
+            return
         if self.mono is not None:
             check(_lg_fns()["grow_mono"](*args, ptr(self.mono), stream_handle(self.dev)), "mifx_gbdt_lg_grow_mono")
             return
